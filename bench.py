@@ -2,7 +2,11 @@
 generation on MI355X -- BASELINE.json's metric on its configs[1]
 ("parallel_wavenet.json IAF student gen, 1 MI355X, batch=1 synthetic 80-dim mel").
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, lets the clocks settle, runs W untimed and K timed steps and prints the line; nothing else.
+`--dump-outputs DIR` writes what the last timed step returned (the wav a caller receives) as DIR/wav.npy (float32);
+the inputs are seeded, so two builds run with the same arguments compare output for output.
 
 With N > 1 and no WORLD_SIZE in the environment the script launches its own N ranks (it re-executes
 itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`);
@@ -14,13 +18,14 @@ resident in HBM.  Utterances are independent, so N ranks each generate their own
 data-path collective (weak scaling); the only communication is the one-time weight broadcast from
 rank 0 (untimed).  Rank 0 prints ONE JSON line.
 
-Beside the contract's fields the line carries (N = 1): `roofline` (the dominant kernel, HIP events inside the library around
-its launches), `roofline_cond` / `roofline_deconv` (conditioning GEMM, upsampler), `roofline_b8` (eight utterances per GPU),
+Everything below is measured with `--full` only.  Beside the contract's fields the line then carries `clocks`, with
+N > 1 `config2_share` / `config4_share`, and with N = 1: `roofline` (the dominant kernel, HIP events inside the library
+around its launches), `roofline_cond` / `roofline_deconv` (conditioning GEMM, upsampler), `roofline_b8` (eight utterances per GPU),
 `roofline_f32` (the reference's own arithmetic) -- each with the same three fractions `frac_mfma_alg`, `frac_mfma_exec`,
 `frac_hbm_moved`; `kernel_us_per_call` (HIP events at the part boundaries, this process); `power` (package power, shader clock
 and energy per sample of a sustained run: the workload runs at the part's power cap); `ar_b1`, `ar_b64`,
 `teacher_forward` (BASELINE configs[3] and the teacher's full-sequence forward); `e2e_ms_per_step` (PCIe-inclusive call);
-`cpu_baseline`.  `--no-extras` keeps only the contract's fields and `roofline`.
+`cpu_baseline`.  `--full --no-extras` keeps only the contract's fields, `clocks` and `roofline`.
 """
 import argparse
 import hashlib
@@ -461,9 +466,9 @@ def settle_clocks(step, cap_s=0.3, tol=0.005, batch=10):
         prev = mean
 
 
-def measure(eng, mel, steps, warmup, rank, world, local, dev, events_every, ramp=-1):
+def measure(eng, mel, steps, warmup, rank, world, local, dev, events_every, ramp=-1, profile=True):
     """Clock settle (or `ramp` fixed extra steps) + W untimed steps, then K timed steps between barrier + synchronize
-    fences; MAX over ranks."""
+    fences; MAX over ranks.  profile=False: no HIP-event pairs around the layer kernels (layer_ms, layer_launches = None)."""
     def step(i):
         # asynchronous calls: the fp16 range guard accumulates in the workspace and is read ONCE behind the timed
         # region (eng.check_range() in main: raises if any of these calls overflowed); a per-call read-back would put a
@@ -486,18 +491,20 @@ def measure(eng, mel, steps, warmup, rank, world, local, dev, events_every, ramp
     for i in range(warmup):
         step(i)
     fence()
-    eng.profile_begin()
+    if profile:
+        eng.profile_begin()
     t0 = time.perf_counter()
     wav = None
     for i in range(steps):
         # the event pairs around the layer kernels cost the stream a bubble each: sample them
         # (not in the first step of a period: step 0 starts on an idle GPU that catches up with the host's launches)
-        n_ev = max(1, min(events_every, steps))
-        eng.profile_pause(i % n_ev != n_ev // 2)
+        if profile:
+            n_ev = max(1, min(events_every, steps))
+            eng.profile_pause(i % n_ev != n_ev // 2)
         wav = step(warmup + i)
     fence()
     elapsed = time.perf_counter() - t0
-    layer_ms, layer_launches = eng.profile_end()
+    layer_ms, layer_launches = eng.profile_end() if profile else (None, None)
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=RED_DEV or dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -780,6 +787,24 @@ def roofline_of(eng, B, F, T, layer_ms, layer_launches, clock_hz=None):
     return roof
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, cap_bytes=DUMP_CAP_BYTES):
+    """--dump-outputs: every array as float32 DIR/<name>.npy.  An array beyond its share of `cap_bytes` is written as
+    `<name>_sample.npy`: the values at a fixed set of flat indices (RandomState(0), sorted), the same for every run of the
+    same shape, so that two builds compare output for output."""
+    os.makedirs(dirname, exist_ok=True)
+    share = cap_bytes // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            n = share // a.itemsize
+            pick = np.sort(np.random.RandomState(0).choice(a.size, n, replace=False))
+            name, a = name + '_sample', a.reshape(-1)[pick]
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
 def stub_main(args, rank, world, local):
     """--stub: the launcher / rendezvous / timing protocol with a torch-CPU step and the gloo backend
     (exercised by tests/test_dist.py on machines without a GPU).  Not a measurement."""
@@ -821,11 +846,16 @@ def main():
     ap.add_argument('--batch-per-gpu', type=int, default=1)
     ap.add_argument('--frames', type=int, default=384, help='mel frames per utterance (384 -> 76800 samples = 4.8 s)')
     ap.add_argument('--config', default=os.path.join(ROOT, 'config_jsons', 'parallel_wavenet.json'))
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='measure beyond the headline figure: HIP-event layer timing in the timed steps and the `roofline` block, '
+                         'shader clocks, and (unless --no-extras / --no-cpu-baseline) every extra block and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned (rank 0: wav) as DIR/<name>.npy, float32')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no CPU baseline')
     ap.add_argument('--no-extras', action='store_true',
-                    help='skip everything behind the timed region: part timing, power sampling, the AR / teacher figures, the PCIe-inclusive call, the 8-utterance and fp32 blocks')
+                    help='with --full: skip everything behind the timed region: part timing, power sampling, the AR / teacher figures, the PCIe-inclusive call, the 8-utterance and fp32 blocks')
     ap.add_argument('--layer-events-every', type=int, default=20,
-                    help='record the HIP-event pairs around the layer kernels in every n-th timed step')
+                    help='with --full: record the HIP-event pairs around the layer kernels in every n-th timed step')
     ap.add_argument('--precision', default=None, choices=['f16x3', 'f16x3-fused', 'f16x3-hoisted', 'f32', 'f32-fused', 'f32-hoisted'],
                     help='IAF contraction arithmetic (default: f16x3 = split-fp16 on the fp16 MFMA)')
     ap.add_argument('--ar-samples', type=int, default=1600,
@@ -871,12 +901,15 @@ def main():
     T = eng.iaf_length(F)
     mel_host = np.random.RandomState(12345 + rank).uniform(0, 1, [B, F, 80]).astype(np.float32)
     mel = torch.from_numpy(mel_host).to(dev)
-    clocks_before = gpu_clocks(local) if rank == 0 else None
+    full = args.full
+    clocks_before = gpu_clocks(local) if rank == 0 and full else None
     elapsed, layer_ms, layer_launches, wav, ramp_info = measure(eng, mel, args.steps, args.warmup, rank, world, local, dev,
-                                                                args.layer_events_every, ramp=args.ramp_steps)
-    clocks_after = gpu_clocks(local) if rank == 0 else None
+                                                                args.layer_events_every, ramp=args.ramp_steps, profile=full)
+    clocks_after = gpu_clocks(local) if rank == 0 and full else None
     assert wav.shape == (B, T) and bool(torch.isfinite(wav).all())
     eng.check_range()                     # raises if a split-fp16 operand left the fp16 range during the timed calls
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'wav': wav.cpu().numpy()})
     seen = world
     if world > 1:                         # the world size the collective actually spans, not the environment's word
         ws = torch.ones(1, device=RED_DEV or dev)
@@ -887,13 +920,6 @@ def main():
     if rank == 0:
         total_samples = world * B * T * args.steps
         value = total_samples / elapsed
-        roof = roofline_of(eng, B, F, T, layer_ms, layer_launches, clock_hz_of(clocks_after))
-        # the whole call against SURVEY.md 8(d)'s layer-granular traffic model (98 484 B per generated sample; its
-        # "60 % of the HBM roofline" is 48.7 M samples/s per GPU) -- beside the dominant kernel's own figures
-        gbps = PATH_BYTES_PER_SAMPLE * (total_samples / world) / elapsed / 1e9
-        roof['path_8d_view'] = {'bytes_per_sample': PATH_BYTES_PER_SAMPLE, 'GBps': gbps, 'frac': gbps / 8000.0,
-                                'note': 'whole generate call, SURVEY 8(d) accounting (every layer reads l and enc and '
-                                        'writes l once); the shipped launch structure moves fewer bytes than this model'}
         dtype = 'f32' if eng.precision.startswith('f32') else \
             'split-fp16: activations stored as fp16 hi+lo pairs (32 bits per value, 22-bit significand, fp16 exponent ' \
             'range), contractions as 3 fp16 MFMAs per product with fp32 accumulate; conditioning term and outputs fp32'
@@ -913,7 +939,6 @@ def main():
             'vs_baseline': None,
             'dtype': dtype,
             'data': 'synthetic',
-            'clocks': {'before': clocks_before, 'after': clocks_after, 'source': 'rocm-smi --showclocks, GPU of rank 0'},
             'config': {
                 'workload': 'BASELINE.json configs[1]: parallel_wavenet.json IAF student generation, '
                             'synthetic 80-dim mel, 16 kHz, {} utterance(s) of {} frames = {} samples per GPU per step'
@@ -928,9 +953,18 @@ def main():
                 'path_achieved_tflops': PATH_FLOP_PER_SAMPLE * (total_samples / world) / elapsed / 1e12,
                 'path_algorithmic_GBps': PATH_BYTES_PER_SAMPLE * (total_samples / world) / elapsed / 1e9,
             },
-            'roofline': roof,
         }
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and full:
+        rec['clocks'] = {'before': clocks_before, 'after': clocks_after, 'source': 'rocm-smi --showclocks, GPU of rank 0'}
+        roof = roofline_of(eng, B, F, T, layer_ms, layer_launches, clock_hz_of(clocks_after))
+        # the whole call against SURVEY.md 8(d)'s layer-granular traffic model (98 484 B per generated sample; its
+        # "60 % of the HBM roofline" is 48.7 M samples/s per GPU) -- beside the dominant kernel's own figures
+        gbps = PATH_BYTES_PER_SAMPLE * (total_samples / world) / elapsed / 1e9
+        roof['path_8d_view'] = {'bytes_per_sample': PATH_BYTES_PER_SAMPLE, 'GBps': gbps, 'frac': gbps / 8000.0,
+                                'note': 'whole generate call, SURVEY 8(d) accounting (every layer reads l and enc and '
+                                        'writes l once); the shipped launch structure moves fewer bytes than this model'}
+        rec['roofline'] = roof
+    if rank == 0 and world == 1 and full and not args.no_extras:
         # Where the call's time goes, measured in THIS process (HIP events at the part boundaries of ten more calls) --
         # not replayed from a profile -- and the roofline blocks of the two parts that are not the dominant kernel.
         # (the sustained run first: the parts are then timed at the operating point the firmware settles on, not in the
@@ -948,7 +982,7 @@ def main():
                                                 'stream a few microseconds: the parts sum to slightly more than a call')
         pm_all = pmc_replay(B, F, eng.precision, eng.iaf_cond_hoisted(B, F), rec['roofline'].get('kernel', '').split(' ')[0])
         rec.update(part_rooflines(eng, hp, B, F, T, part_us, pm_all))
-    if world == 1 and not args.no_extras:
+    if world == 1 and full and not args.no_extras:
         # (0) the other BASELINE.json configs that fit one GPU, driver-timed in the same line: configs[3] (wavenet_mol.json
         #     autoregressive fastgen, one utterance) and its batched form, and the teacher's full-sequence forward
         rec.update(teacher_extras(dev, args.ar_samples))
@@ -1017,7 +1051,7 @@ def main():
                 r32['b8'] = {'error': repr(e)}
             rec['roofline_f32'] = r32
             eng32.close()
-    if world > 1 and not args.no_extras:
+    if world > 1 and full and not args.no_extras:
         # The per-GPU shares of BASELINE configs[2] (64 utterances over 8 GPUs = 8 per GPU, this model) and configs[4]
         # (parallel_wavenet_gauss.json as shipped, 128 over 8 = 16 per GPU): timed on every rank, MAX over ranks,
         # aggregate = all ranks' samples over that time.  Weak scaling like the headline figure.
@@ -1044,7 +1078,7 @@ def main():
             rec['config2_share'] = c2
             rec['config4_share'] = c4
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and full and not args.no_cpu_baseline:
             rec['cpu_baseline'] = cpu_baseline(hp_dict, F)
         print(json.dumps(rec), flush=True)
     if world > 1:

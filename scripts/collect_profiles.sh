@@ -1,9 +1,9 @@
-# Copies what scripts/final_profile.sh left under gpurun_out/ into profiles/ (tracked) under this round's names and
+# Copies what scripts/final_profile.sh left under profile_out/ (or $PROFILE_OUT) into profiles/ (tracked) under this round's names and
 # rebuilds the PMC summaries (with the source hash of the kernels they were measured on).  Usage: collect_profiles.sh r02
 set -e
 R=${1:-r06}
 cd "$(dirname "$0")/.."
-G=gpurun_out
+G=${PROFILE_OUT:-profile_out}
 cp $G/bench_f16x3.json profiles/${R}_bench_f16x3.json
 cp $G/bench_f16x3_b8.json profiles/${R}_bench_f16x3_batch8.json
 cp $G/bench_f16x3_driver_protocol.json profiles/${R}_bench_f16x3_driver_protocol.json

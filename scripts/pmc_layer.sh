@@ -2,8 +2,8 @@
 # PMC passes for the layer kernels (run on the GPU box through gpurun). $1 = tag, $2 = extra bench.py arguments
 set -u
 TAG=${1:-r01}
+OUT=${PROFILE_OUT:-$(cd "$(dirname "$0")/.." && pwd)/profile_out}/pmc_$TAG
 cd /tmp && export TMPDIR=/tmp
-OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 # the hash of the kernel sources these counters are measured on, stamped NOW (pmc_summary.py copies it and refuses a
 # directory without one: a summary regenerated later from old counters must not claim the current sources)

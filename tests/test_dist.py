@@ -156,6 +156,22 @@ def test_bench_roofline_blocks_carry_the_same_three_fractions():
     assert bench.HwmonSampler(0).summary() is None or True                     # (no GPU here: the sampler must not raise)
 
 
+def test_bench_dump_outputs_float32_capped_and_repeatable(tmp_path):
+    """--dump-outputs: float32 DIR/<name>.npy; an array beyond the cap becomes `<name>_sample.npy`, the same values at the
+    same fixed indices on every run, within the cap."""
+    import bench
+    a = np.arange(12, dtype=np.float64).reshape(3, 4)
+    bench.dump_outputs(str(tmp_path / 'a'), {'wav': a})
+    got = np.load(tmp_path / 'a' / 'wav.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, a)
+    big = np.random.RandomState(1).standard_normal([4, 1000])
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), {'wav': big}, cap_bytes=4096)
+    s, s2 = np.load(tmp_path / 'b' / 'wav_sample.npy'), np.load(tmp_path / 'c' / 'wav_sample.npy')
+    assert s.dtype == np.float32 and 0 < s.nbytes <= 4096 and np.array_equal(s, s2)
+    assert np.isin(s, big.astype(np.float32)).all() and not (tmp_path / 'b' / 'wav.npy').exists()
+
+
 def _cli_worker(rank, world, port, src, dst, ckpt, q):
     sys.path.insert(0, ROOT)
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank),
