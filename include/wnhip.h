@@ -34,7 +34,8 @@
  *   - Concurrency (SURVEY 8(b) "Threading / streams"; tests/test_gpu_threads.py drives one handle from two
  *     host threads on two streams).  After wn_finalize() the weights and every table of a handle are read-only.
  *     The WORK calls -- wn_deconv, wn_iaf_generate*, wn_iaf_range_*, wn_clip_quant, wn_ar_reset / wn_ar_step /
- *     wn_ar_generate / wn_ar_cond_vars, wn_teacher_forward / wn_teacher_log_prob -- keep all per-call state (the
+ *     wn_ar_generate / wn_ar_cond_vars, wn_teacher_forward / wn_teacher_log_prob, wn_distill_mol_xent /
+ *     wn_distill_gauss_kl -- keep all per-call state (the
  *     range-guard word, the autoregressive queues and step counter) in the caller's workspace / state buffer:
  *     any number of host threads may issue them on ONE handle at the same time, each with its own workspace
  *     and stream.  (wn_ar_generate's hipGraphs are per call; the handle only keeps them alive until their
@@ -322,6 +323,44 @@ WN_API int wn_teacher_forward(wn_handle* h, const float* wav, const float* mel, 
  * implementation; 1e-3 of a bin away from every edge the class is exact (tests/test_gpu_teacher.py). */
 WN_API int wn_teacher_log_prob(wn_handle* h, const float* out_params, const float* wav, int B, int64_t T, float* log_prob,
                         void* stream);
+
+/* ---- distillation losses (ParallelWavenet.kl_loss_logistic / kl_loss_gauss / power_loss, wavenet/parallel_wavenet.py:361-479)
+ * scored under a TEACHER handle on the out_params wn_teacher_forward wrote for the student's unclipped audio x.
+ * Each call refuses with WN_EINVAL (message in wn_last_error): a student handle; a ce teacher in the mol call; a non-gauss
+ * teacher in the gauss call; any mu-law teacher (the reference would score mu-law encoded audio unencoded there, CLIP = False);
+ * num_samples S < 1; an out_width that is not the handle's.  Asynchronous on `stream`, no allocation, no synchronisation;
+ * every sum is reduced in a fixed order, so a repeated call is bit-identical.  `sums` are two float64 values on the device. ---- */
+
+/* Workspace of wn_distill_mol_xent and wn_distill_gauss_kl for B utterances of T samples. */
+WN_API size_t wn_distill_workspace_bytes(const wn_handle* h, int B, int64_t T);
+
+/* Monte-Carlo cross entropy of kl_loss_logistic (:361-402): for every row (b, t) and draw s, x = rl[b,s,t] * scale_tot[b,t]
+ * + mean_tot[b,t] is scored by loss_func.mol_log_probs (wavenet/loss_func.py:22-63, Q = 65536, x not quantised) under
+ * out_params[b,t,:] [B,T,out_width = 3 mol_mix]; h_bl[b,t] = -mean_s log p ([B,T], the reference's H_Ps_Pt_bl);
+ * sums[0] = sum of h_bl, sums[1] = sum of log scale_tot -- H_Ps_Pt = sums[0] / (B T), H_Ps = sums[1] / (B T) + 2.
+ *   noise      [B,S,T] injected logistic draws (row b*S + s of the reference's [B*S,T] draw, utils.tf_repeat), or NULL:
+ *              drawn on the device, Philox4x32-10 keyed by (seed; b, s, t), log u - log(1-u), u ~ U(1e-5, 1-1e-5)
+ *   noise_out  [B,S,T] the draws used (optional)
+ * No [B,S,T,.] intermediate exists: each teacher row is read once and its S draws are evaluated in registers. */
+WN_API int wn_distill_mol_xent(wn_handle* h, const float* out_params, int out_width, const float* mean_tot,
+                               const float* scale_tot, int B, int64_t T, int S, const float* noise, uint64_t seed,
+                               float* h_bl, float* noise_out, double* sums, void* ws, size_t ws_bytes, void* stream);
+
+/* Closed-form Gaussian KL of kl_loss_gauss (:404-429) on out_params [B,T,2] (mean, log scale; loss_func.py:66-75):
+ * kl_bl[b,t] [B,T]; sums[0] = sum of kl_bl, sums[1] = sum of (log s_p - log s_q)^2 -- kl_loss = (sums[0] + 4 sums[1]) / (B T). */
+WN_API int wn_distill_gauss_kl(wn_handle* h, const float* out_params, int out_width, const float* mean_tot,
+                               const float* scale_tot, int B, int64_t T, float* kl_bl, double* sums, void* ws,
+                               size_t ws_bytes, void* stream);
+
+/* power_loss (:459-479) with the reference's module constants (|STFT|, squared difference, USE_PRIORITY_FREQ): pred and orig
+ * rows of L samples (row strides pred_stride / orig_stride floats: the centre trim of the longer signal, :431-436, is a
+ * pointer offset), tf.contrib.signal.stft(frame_length 800, frame_step 200, fft_length 2048, pad_end=True) -- ceil(L/200)
+ * frames of 1025 bins, periodic Hann window, not centred.  out2[0] = sum over (b, frame, bin) of (|P| - |O|)^2, out2[1] the
+ * same over the bins below 384 (mel_extractor.PRIORITY_FREQ): power_loss = 0.5 out2[0] / (B NF 1025) + 0.5 out2[1] / (B NF 384).
+ * Needs no handle; errors through wn_last_error(NULL). */
+WN_API size_t wn_power_loss_workspace_bytes(int B, int64_t L);
+WN_API int wn_power_loss(const float* pred, int64_t pred_stride, const float* orig, int64_t orig_stride, int B, int64_t L,
+                         double* out2, void* ws, size_t ws_bytes, void* stream);
 
 /* 1 when wn_iaf_generate(B, F) evaluates the per-layer conditioning 1x1s in one hoisted GEMM per
  * deconv stack (the default of the split-fp16 path: the layer kernels then stream 768 B/sample

@@ -17,6 +17,7 @@
 
 #include "wn_internal.h"
 #include "wn_codec.h"
+#include "wn_mol.h"
 #include "wn_pack_h.h"
 #include "wn_mfma_h.h"
 
@@ -427,11 +428,7 @@ namespace {
 // The discretised-logistic mass cdf(x + 1/Q) - cdf(x - 1/Q) is evaluated as sigma(a) sigma(-b) (1 - exp(-(a - b))) with
 // a - b = 2 inv_s / Q formed directly: the difference of two float32 sigmoids the reference's formula takes loses all but
 // two digits of it at Q = 65 536 (the float64 evaluation of the reference's formula is what the tests compare with).
-__device__ inline float tl_softplus(float v) { return fmaxf(v, 0.f) + log1pf(expf(-fabsf(v))); }
-__device__ inline float tl_sigmoid(float v) {
-    const float e = expf(-fabsf(v));
-    return v >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-}
+// The per-component arithmetic is wn_mol.h's, shared with the distillation cross entropy (wn_distill.hip).
 __device__ inline float tl_wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
@@ -459,10 +456,9 @@ __global__ __launch_bounds__(256) void tg_log_prob_kernel(const float* __restric
             lg = o[lane];
             const float mean = o[M + lane], ls = fmaxf(o[2 * M + lane], -7.0f);
             const float inv = expf(-ls), c = xt - mean, iq = 1.0f / (float)Q;
-            const float plus = inv * (c + iq), mn = inv * (c - iq);
-            const float max_thres = ((float)(Q - 1) - 0.5f) / ((float)Q * 0.5f) - 1.0f, min_thres = 0.5f / ((float)Q * 0.5f) - 1.0f;
-            const float delta = tl_sigmoid(plus) * tl_sigmoid(-mn) * (-expm1f(-2.0f * inv * iq));
-            v = xt < min_thres ? plus - tl_softplus(plus) : (xt > max_thres ? -tl_softplus(mn) : logf(fmaxf(delta, 1e-12f)));
+            float min_thres, max_thres;
+            wn_mol_thresholds(Q, min_thres, max_thres);
+            v = wn_mol_component_lp(xt, c, inv, iq, wn_mol_bin_factor(inv, iq), min_thres, max_thres);
         }
         const float lmax = tl_wave_max(lg);
         const float lse = lmax + logf(tl_wave_sum(lane < M ? expf(lg - lmax) : 0.f));

@@ -267,6 +267,53 @@ class Engine(object):
                                                      _ptr(lp), self._stream()))
         return lp
 
+    # ---- distillation losses (teacher handle; ParallelWavenet.kl_loss_logistic / kl_loss_gauss) ----
+    def _distill_args(self, what, out_params, mean_tot, scale_tot):
+        out_params, mean_tot, scale_tot = self._dev(out_params), self._dev(mean_tot), self._dev(scale_tot)
+        if mean_tot.dim() != 2 or out_params.dim() != 3 or tuple(scale_tot.shape) != tuple(mean_tot.shape) or \
+                tuple(out_params.shape[:2]) != tuple(mean_tot.shape):
+            raise ValueError('{}: out_params must be [B,T,out_width], mean_tot and scale_tot [B,T]'.format(what))
+        return out_params, mean_tot, scale_tot
+
+    def distill_mol_xent(self, out_params, mean_tot, scale_tot, num_samples, noise=None, seed=0, want_noise=False):
+        """The Monte-Carlo cross entropy of kl_loss_logistic (parallel_wavenet.py:361-402) under this MoL teacher:
+        out_params [B,T,3 mol_mix] (teacher_forward of the student's x), the student's mean_tot / scale_tot [B,T].
+        noise: [B,num_samples,T] injected logistic draws, or None (Philox on the device from `seed`).
+        Returns {'H_bl': [B,T] float32, 'sums': [2] float64 (sum of H_bl, sum of log scale_tot)} and 'noise' [B,S,T]
+        (the draws used) when want_noise."""
+        out_params, mean_tot, scale_tot = self._distill_args('distill_mol_xent', out_params, mean_tot, scale_tot)
+        B, T, S = int(mean_tot.shape[0]), int(mean_tot.shape[1]), int(num_samples)
+        noise = self._dev(noise)
+        if noise is not None and tuple(noise.shape) != (B, S, T):
+            raise ValueError('distill_mol_xent: noise must be [B, num_samples, T] = [{}, {}, {}]'.format(B, S, T))
+        h_bl = torch.empty((B, T), dtype=torch.float32, device=self.device)
+        sums = torch.empty(2, dtype=torch.float64, device=self.device)
+        nout = torch.empty((B, S, T), dtype=torch.float32, device=self.device) if want_noise and S > 0 else None
+        with torch.cuda.device(self.device):
+            ws = self._workspace(max(int(self.lib.wn_distill_workspace_bytes(self._h, B, T)), 256))
+            self._check(self.lib.wn_distill_mol_xent(self._h, _ptr(out_params), int(out_params.shape[2]), _ptr(mean_tot),
+                                                     _ptr(scale_tot), B, T, S, _ptr(noise), ctypes.c_uint64(seed & (2 ** 64 - 1)),
+                                                     _ptr(h_bl), _ptr(nout), _ptr(sums), _ptr(ws), ws.numel(), self._stream()))
+        out = {'H_bl': h_bl, 'sums': sums}
+        if want_noise:
+            out['noise'] = nout
+        return out
+
+    def distill_gauss_kl(self, out_params, mean_tot, scale_tot):
+        """kl_loss_gauss (parallel_wavenet.py:404-429) under this Gauss teacher: out_params [B,T,2], the student's
+        mean_tot / scale_tot [B,T].  Returns {'kl_bl': [B,T] float32, 'sums': [2] float64 (sum of kl_bl, sum of the
+        squared log-scale differences)}."""
+        out_params, mean_tot, scale_tot = self._distill_args('distill_gauss_kl', out_params, mean_tot, scale_tot)
+        B, T = int(mean_tot.shape[0]), int(mean_tot.shape[1])
+        kl_bl = torch.empty((B, T), dtype=torch.float32, device=self.device)
+        sums = torch.empty(2, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            ws = self._workspace(max(int(self.lib.wn_distill_workspace_bytes(self._h, B, T)), 256))
+            self._check(self.lib.wn_distill_gauss_kl(self._h, _ptr(out_params), int(out_params.shape[2]), _ptr(mean_tot),
+                                                     _ptr(scale_tot), B, T, _ptr(kl_bl), _ptr(sums), _ptr(ws), ws.numel(),
+                                                     self._stream()))
+        return {'kl_bl': kl_bl, 'sums': sums}
+
     def iaf_cond_hoisted(self, batch, num_frames):
         """True when iaf_generate(batch, num_frames) runs the hoisted-conditioning kernels."""
         return bool(self.lib.wn_iaf_cond_hoisted(self._h, int(batch), int(num_frames)))
@@ -479,3 +526,46 @@ class Engine(object):
         if want_out:
             out['out_params'] = torch.cat([p[5] for p in parts], 0)
         return out
+
+
+PRIORITY_FREQ = 384        # auxilaries/mel_extractor.py:27 (bins below 3 kHz)
+STFT_BINS = 1025
+STFT_HOP = 200
+
+
+def _trim(x, trim_len):
+    """ParallelWavenet._trim (parallel_wavenet.py:431-436): drop trim_len samples, trim_len // 2 of them on the left -- a view."""
+    left = int(trim_len // 2)
+    return x[:, left:left + int(x.shape[1]) - int(trim_len)]
+
+
+def power_loss(pred, orig, device=None):
+    """ParallelWavenet.power_loss (parallel_wavenet.py:459-479) on the device, with the reference's module constants:
+    pred, orig [B,L] audio (device tensors or arrays); the longer one is centre-trimmed to the shorter.  Returns the loss,
+    0.5 mean (|P| - |O|)^2 + 0.5 of the same over the bins below 3 kHz, as a 0-d float64 device tensor."""
+    lib = _lib.load()
+    dev = torch.device(device) if device is not None else (pred.device if isinstance(pred, torch.Tensor) and pred.is_cuda
+                                                             else torch.device('cuda', torch.cuda.current_device()))
+
+    def to_dev(x):
+        if isinstance(x, torch.Tensor):
+            return x.to(device=dev, dtype=torch.float32)
+        return torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32).to(dev)
+    pred, orig = to_dev(pred), to_dev(orig)
+    if pred.dim() != 2 or orig.dim() != 2 or pred.shape[0] != orig.shape[0]:
+        raise ValueError('power_loss: pred and orig must be [B,L] with equal B')
+    pred = pred if pred.stride(1) == 1 else pred.contiguous()
+    orig = orig if orig.stride(1) == 1 else orig.contiguous()
+    lp, lo = int(pred.shape[1]), int(orig.shape[1])
+    if lp > lo:
+        pred = _trim(pred, lp - lo)
+    elif lo > lp:
+        orig = _trim(orig, lo - lp)
+    B, L = int(pred.shape[0]), int(pred.shape[1])
+    out = torch.empty(2, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(int(lib.wn_power_loss_workspace_bytes(B, L)), 256), dtype=torch.uint8, device=dev)
+        _lib.check(lib.wn_power_loss(_ptr(pred), pred.stride(0), _ptr(orig), orig.stride(0), B, L, _ptr(out), _ptr(ws),
+                                     ws.numel(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    nf = (L + STFT_HOP - 1) // STFT_HOP
+    return 0.5 * out[0] / (B * nf * STFT_BINS) + 0.5 * out[1] / (B * nf * PRIORITY_FREQ)

@@ -5,6 +5,12 @@ result keys and `_clip_quant_scale` as wavenet/parallel_wavenet.py:117-141,289-3
 the reference -- but `feed_forward` is ONE call into the HIP engine instead of a TF
 graph.  The reference creates TF variables and a Saver restores them; here
 `restore(checkpoint_path)` / `load_weights(dict)` fills the engine.
+
+With a teacher (the mirror's `Wavenet`, passed as `teacher=` like the reference's), the student is scored against it:
+`kl_loss_logistic`, `kl_loss_gauss`, `power_loss`, `contrastive_loss` and `calculate_loss` (parallel_wavenet.py:361-512)
+take the reference's keys and return the reference's dicts, as 0-d float64 device tensors.  The teacher's full-sequence
+forward runs on the student's unclipped x (CLIP = False) and the loss kernels of csrc/wn_distill.hip score it; the
+Monte-Carlo draws are injected (`noise`, [B, num_samples, T]) or drawn on the device from `seed`.
 """
 import numpy as np
 import torch
@@ -28,6 +34,9 @@ class ParallelWavenet(object):
         self.quant_chann = 2 ** 8 if self.use_mu_law else 2 ** 16
         self.out_width = 2
         self.engine = Engine(hp, kind='student', device=device)
+        # the teacher scores the student in the distillation losses below; generation needs none.  The pairing the
+        # reference asserts at construction (parallel_wavenet.py:129-136) is checked where a loss uses the teacher.
+        self.teacher = teacher
 
     def load_weights(self, weights):
         self.engine.load_weights(weights)
@@ -52,3 +61,75 @@ class ParallelWavenet(object):
     def _clip_quant_scale(self, x, quant_chann=None, use_mu_law=None):
         wav, _ = self.engine.clip_quant(x)
         return wav
+
+    # ---- distillation losses (parallel_wavenet.py:361-512) ----
+    def _need_teacher(self, what):
+        if self.teacher is None:
+            raise ValueError('{} needs the teacher: ParallelWavenet(hparams, teacher=Wavenet(te_hparams))'.format(what))
+        te = self.teacher
+        if not (te.loss_type == 'mol' and self.loss_type == 'logistic' or te.loss_type == 'gauss' and self.loss_type == 'gauss'):
+            raise ValueError('{}: a {} student is distilled from a {} teacher; the reference pairs logistic with mol and gauss '
+                             'with gauss (parallel_wavenet.py:133-135)'.format(what, self.loss_type, te.loss_type))
+        if self.use_mu_law:
+            raise ValueError('{}: mu-law students are not supported by the distillation losses (the reference would '
+                             'score mu-law encoded audio unencoded, CLIP = False)'.format(what))
+        return self.teacher.engine
+
+    def kl_loss_logistic(self, ff_dict, num_samples=100, noise=None, seed=0):
+        """parallel_wavenet.py:361-402.  ff_dict: 'mel', 'x', 'mean_tot', 'scale_tot' (and 'log_scale_tot', which is
+        log(scale_tot) here: H_Ps comes from the kernel's sum of log scale_tot).  Returns kl_loss, H_Ps, H_Ps_Pt."""
+        te = self._need_teacher('kl_loss_logistic')
+        out_params = te.teacher_forward(ff_dict['x'], ff_dict['mel'])
+        r = te.distill_mol_xent(out_params, ff_dict['mean_tot'], ff_dict['scale_tot'], num_samples, noise=noise, seed=seed)
+        n = r['H_bl'].numel()
+        H_Ps = r['sums'][1] / n + 2
+        H_Ps_Pt = r['sums'][0] / n
+        return {'kl_loss': H_Ps_Pt - H_Ps, 'H_Ps': H_Ps, 'H_Ps_Pt': H_Ps_Pt}
+
+    def kl_loss_gauss(self, ff_dict):
+        """parallel_wavenet.py:404-429: mean closed-form KL + 4 * mean squared log-scale difference."""
+        te = self._need_teacher('kl_loss_gauss')
+        out_params = te.teacher_forward(ff_dict['x'], ff_dict['mel'])
+        r = te.distill_gauss_kl(out_params, ff_dict['mean_tot'], ff_dict['scale_tot'])
+        n = r['kl_bl'].numel()
+        return {'kl_loss': r['sums'][0] / n + 4.0 * (r['sums'][1] / n)}
+
+    def power_loss(self, wav_dict):
+        """parallel_wavenet.py:459-479: STFT-magnitude loss of 'x' against the real audio 'wav'."""
+        from ..engine import power_loss
+        return {'power_loss': power_loss(wav_dict['x'], wav_dict['wav'], device=self.engine.device)}
+
+    def contrastive_loss(self, ff_dict, num_samples=100, noise=None, seed=0):
+        """parallel_wavenet.py:481-490: minus the logistic KL under the mismatched 'mel_rand'."""
+        ff_dict_for_cl = {'x': ff_dict['x'], 'mel': ff_dict['mel_rand'], 'mean_tot': ff_dict['mean_tot'],
+                          'scale_tot': ff_dict['scale_tot'], 'log_scale_tot': ff_dict.get('log_scale_tot')}
+        return {'contrastive_loss': -self.kl_loss_logistic(ff_dict_for_cl, num_samples, noise=noise, seed=seed)['kl_loss']}
+
+    def calculate_loss(self, ff_dict, noise=None, seed=0, cl_noise=None, cl_seed=None):
+        """parallel_wavenet.py:492-512 with the same hparams reads (power_loss_factor; for a logistic student num_samples and
+        contrastive_loss_factor, with the reference's getattr defaults).  The contrastive term has draws of its own, like
+        the reference's second random node: `cl_noise`, or the device generator under `cl_seed` (default: derived from
+        `seed`, distinct from the KL term's stream)."""
+        hp = self.hparams
+        plf = hp.power_loss_factor
+        if self.loss_type == 'logistic':
+            clf = getattr(hp, 'contrastive_loss_factor', 0.0)
+            num_samples = getattr(hp, 'num_samples', 0)
+            loss_dict = self.kl_loss_logistic(ff_dict, num_samples, noise=noise, seed=seed)
+        else:
+            clf = 0.
+            num_samples = 0
+            loss_dict = self.kl_loss_gauss(ff_dict)
+        loss = loss_dict['kl_loss']
+        if plf > 0.0:
+            pl_dict = self.power_loss(ff_dict)
+            loss = loss + plf * pl_dict['power_loss']
+            loss_dict.update(pl_dict)
+        if clf > 0.0:
+            if cl_seed is None:
+                cl_seed = (int(seed) + 0x9E3779B97F4A7C15) % (1 << 64)
+            cl_dict = self.contrastive_loss(ff_dict, num_samples, noise=cl_noise, seed=cl_seed)
+            loss = loss + clf * cl_dict['contrastive_loss']
+            loss_dict.update(cl_dict)
+        loss_dict.update({'loss': loss})
+        return loss_dict
