@@ -362,6 +362,56 @@ WN_API size_t wn_power_loss_workspace_bytes(int B, int64_t L);
 WN_API int wn_power_loss(const float* pred, int64_t pred_stride, const float* orig, int64_t orig_stride, int B, int64_t L,
                          double* out2, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- gradients of the distillation losses with respect to the student's x, mean_tot and scale_tot.
+ * The teacher is frozen: only its input VJP runs, no weight gradient.  Work calls like the losses above: asynchronous on
+ * `stream`, no allocation, no host synchronisation, safe from several threads on one handle (own workspaces and streams);
+ * no atomics, so a repeated call is bit-identical.  `fac` is two float64 values ON THE DEVICE: the derivative of the
+ * caller's loss with respect to the two sums the matching forward call returns (sums / out2), so a backward pass reads
+ * nothing back to the host.  They refuse what the forward calls refuse (student handle, ce teacher, mu-law teacher,
+ * mismatched pairing, num_samples < 1, wrong out_width) with WN_EINVAL.
+ * Tie conventions are TensorFlow's, i.e. the gradient TF's autodiff gives for the reference's graph:
+ *   tf.maximum(log_s, -7)   passes the gradient where log_s >= -7, none below;
+ *   tf.maximum(mass, 1e-12) passes the gradient where mass >= 1e-12, none below the floor;
+ *   tf.where (edge bins)    the selected branch only;
+ *   relu                    where the pre-activation is > 0;
+ *   |z| of the STFT         gradient 0 at z = 0.
+ * The MoL bin mass is differentiated in the form the forward evaluates, sigma(a) sigma(-b) (1 - e^-(a-b)) with
+ * a - b = 2 inv_s / Q (wn_mol.h), not as a float32 difference of sigmoids: the same function, without the cancellation. ---- */
+
+/* Tape of the teacher forward for B utterances of T samples: a 256-byte header (handle identity, B, T, layer count), the
+ * pre-ReLU skip sum and out1 rows, and sigma / tanh of every gate -- 4 (2 skip_width + num_layers gate_width) bytes per
+ * sample with T rounded up to 256 (wavenet_mol.json: 30 * 512 * 4 B of gates per sample, 4.7 GB at B = 1, T = 76 800). */
+WN_API size_t wn_teacher_tape_bytes(const wn_handle* h, int B, int64_t T);
+/* wn_teacher_forward (same arguments, same workspace, bit-identical out_params) that also writes the tape. */
+WN_API int wn_teacher_forward_tape(wn_handle* h, const float* wav, const float* mel, int B, int F, int64_t T,
+                                   float* out_params, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes, void* stream);
+/* Input VJP: d_wav [B,T] = (d out_params / d wav)^T d_out_params [B,T,out_width], on a tape this handle's
+ * wn_teacher_forward_tape wrote for the same B and T (any other tape is refused with WN_EINVAL).  The transposed GEMMs run
+ * on the forward's split-fp16 MFMA kernel; d_out_params enter scaled by the power of two that brings their largest
+ * magnitude to [1, 2), found on the device.  Needs width, skip_width and gate_width / 2 multiples of 64. */
+WN_API size_t wn_teacher_backward_workspace_bytes(const wn_handle* h, int B, int64_t T);
+WN_API int wn_teacher_backward_input(wn_handle* h, const void* tape, size_t tape_bytes, const float* d_out_params, int B,
+                                     int64_t T, float* d_wav, void* ws, size_t ws_bytes, void* stream);
+
+/* Gradient of L = fac[0] sums[0] + fac[1] sums[1] of wn_distill_mol_xent (same draws: `noise`, or Philox under `seed`):
+ * d_out_params [B,T,3 mol_mix], d_mean_tot and d_scale_tot [B,T] (through x = rl scale_tot + mean_tot, and 1 / scale_tot of
+ * the log scale_tot sum).  Overwrites its outputs; no workspace. */
+WN_API int wn_distill_mol_xent_grad(wn_handle* h, const float* out_params, int out_width, const float* mean_tot,
+                                    const float* scale_tot, int B, int64_t T, int S, const float* noise, uint64_t seed,
+                                    const double* fac, float* d_out_params, float* d_mean_tot, float* d_scale_tot,
+                                    void* stream);
+/* Gradient of L = fac[0] sums[0] + fac[1] sums[1] of wn_distill_gauss_kl: d_out_params [B,T,2], d_mean_tot, d_scale_tot. */
+WN_API int wn_distill_gauss_kl_grad(wn_handle* h, const float* out_params, int out_width, const float* mean_tot,
+                                    const float* scale_tot, int B, int64_t T, const double* fac, float* d_out_params,
+                                    float* d_mean_tot, float* d_scale_tot, void* stream);
+/* Gradient of L = fac[0] out2[0] + fac[1] out2[1] of wn_power_loss with respect to pred: d_pred rows of L samples (row
+ * stride d_pred_stride).  Per frame the bins' 2 (|P| - |O|) P / |P| go back through the DFT and the window; the frames are
+ * overlap-added in a fixed order.  Needs no handle; errors through wn_last_error(NULL). */
+WN_API size_t wn_power_loss_grad_workspace_bytes(int B, int64_t L);
+WN_API int wn_power_loss_grad(const float* pred, int64_t pred_stride, const float* orig, int64_t orig_stride, int B,
+                              int64_t L, const double* fac, float* d_pred, int64_t d_pred_stride, void* ws, size_t ws_bytes,
+                              void* stream);
+
 /* 1 when wn_iaf_generate(B, F) evaluates the per-layer conditioning 1x1s in one hoisted GEMM per
  * deconv stack (the default of the split-fp16 path: the layer kernels then stream 768 B/sample
  * instead of 1536 and the small-dilation layers run two per launch; since round 6 also the default of the fp32 form:

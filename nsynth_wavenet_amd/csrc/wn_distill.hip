@@ -406,3 +406,344 @@ extern "C" int wn_power_loss(const float* pred, int64_t pred_stride, const float
     if (e != hipSuccess) return wn_fail(nullptr, WN_EIO, "%s: launch failed: %s", fn, hipGetErrorString(e));
     return WN_OK;
 }
+
+// ---- gradients of the three losses.  Each takes `fac`, two float64 values on the device: the loss's
+// derivative with respect to the two sums the forward call returns (sums / out2), so a backward pass needs no host read.
+// Tie conventions are TensorFlow's (include/wnhip.h).  No atomics: every value is written by exactly one lane. ----
+namespace {
+
+// H_bl rows as dx_mol_kernel evaluates them, differentiated: per draw the mixture weights w_k = softmax_k(v) of the
+// component log-probabilities; d/d logit_k = sum_s (w_k - p_k), d/d mean_k and d/d log_scale_k through the component,
+// d/d x_s -> d mean_tot, rl_s d/d x_s -> d scale_tot.  Same tile, row constants and draws as dx_mol_kernel; the four
+// waves' partial sums meet in LDS in a fixed order.
+template <int MM>
+__global__ __launch_bounds__(256) void dx_mol_grad_kernel(const float* __restrict__ te, const float* __restrict__ mean_st,
+                                                          const float* __restrict__ scale_st, long long T, int S, int M,
+                                                          int ow, int Q, const float* __restrict__ noise, uint64_t seed,
+                                                          const double* __restrict__ fac, float* __restrict__ d_te,
+                                                          float* __restrict__ d_mean, float* __restrict__ d_scale) {
+    __shared__ float red[DX_WAVES][DX_ROWS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.y;
+    const long long t = (long long)blockIdx.x * DX_ROWS + lane;
+    const bool live = t < T;
+    float gw[MM], gmu[MM], gin[MM], inv[MM], lsm[MM], raw_ls[MM];
+#pragma unroll
+    for (int k = 0; k < MM; ++k) gw[k] = gmu[k] = gin[k] = inv[k] = lsm[k] = raw_ls[k] = 0.f;
+    float gx = 0.f, gxr = 0.f, ss = 1.f;
+    const size_t row = live ? (size_t)b * T + t : 0;
+    if (live) {
+        const float* o = te + row * ow;
+        const float iq = 1.0f / (float)Q;
+        float min_thres, max_thres;
+        wn_mol_thresholds(Q, min_thres, max_thres);
+        float mu[MM], dd[MM];
+        float lmax = -__builtin_inff();
+#pragma unroll
+        for (int k = 0; k < MM; ++k)
+            if (k < M) { lsm[k] = o[k]; lmax = fmaxf(lmax, lsm[k]); }
+        float se = 0.f;
+#pragma unroll
+        for (int k = 0; k < MM; ++k)
+            if (k < M) se += expf(lsm[k] - lmax);
+        const float lse = lmax + logf(se);
+#pragma unroll
+        for (int k = 0; k < MM; ++k)
+            if (k < M) {
+                lsm[k] -= lse;
+                mu[k] = o[M + k];
+                raw_ls[k] = o[2 * M + k];
+                inv[k] = expf(-fmaxf(raw_ls[k], -7.0f));
+                dd[k] = wn_mol_bin_factor(inv[k], iq);
+            }
+        const float ms = mean_st[row];
+        ss = scale_st[row];
+        const int nq = (S + 3) / 4;
+        for (int q = wave; q < nq; q += DX_WAVES) {
+            float rl[4];
+            if (noise) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int s = 4 * q + e;
+                    rl[e] = s < S ? noise[((size_t)b * S + s) * T + t] : 0.f;
+                }
+            } else {
+                uint32_t c[4] = {(uint32_t)t, (uint32_t)q, (uint32_t)b, DX_PHILOX_TAG};
+                wn_philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float u = wn_u01(c[e]) * (1.f - 2e-5f) + 1e-5f;
+                    rl[e] = logf(u) - logf(1.f - u);
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int s = 4 * q + e;
+                if (s >= S) break;
+                const float x = rl[e] * ss + ms;
+                float v[MM], dxk[MM], dik[MM];
+                float vmax = -__builtin_inff();
+#pragma unroll
+                for (int k = 0; k < MM; ++k)
+                    if (k < M) {
+                        const float cc = x - mu[k];
+                        v[k] = wn_mol_component_lp(x, cc, inv[k], iq, dd[k], min_thres, max_thres) + lsm[k];
+                        vmax = fmaxf(vmax, v[k]);
+                        wn_mol_component_grad(x, cc, inv[k], iq, dd[k], min_thres, max_thres, dxk[k], dik[k]);
+                    }
+                float sv = 0.f;
+#pragma unroll
+                for (int k = 0; k < MM; ++k)
+                    if (k < M) { v[k] = expf(v[k] - vmax); sv += v[k]; }
+                const float isv = 1.f / sv;
+                float gxs = 0.f;
+#pragma unroll
+                for (int k = 0; k < MM; ++k)
+                    if (k < M) {
+                        const float w = v[k] * isv;
+                        gw[k] += w;
+                        gmu[k] -= w * dxk[k];
+                        gin[k] += w * dik[k];
+                        gxs += w * dxk[k];
+                    }
+                gx += gxs;
+                gxr += rl[e] * gxs;
+            }
+        }
+    }
+    // fixed-order sum of the four waves' partials; wave 0 writes the row
+    auto meet = [&](float v) {
+        red[wave][lane] = v;
+        __syncthreads();
+        const float r = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+        __syncthreads();
+        return r;
+    };
+    const float c = (float)(-fac[0] / (double)S);          // d loss / d log p of one draw of the row
+    float* dt = d_te + row * ow;
+#pragma unroll
+    for (int k = 0; k < MM; ++k)
+        if (k < M) {
+            const float w = meet(gw[k]), m = meet(gmu[k]), in = meet(gin[k]);
+            if (wave == 0 && live) {
+                dt[k] = c * (w - (float)S * expf(lsm[k]));
+                dt[M + k] = c * m;
+                dt[2 * M + k] = raw_ls[k] >= -7.0f ? -c * in * inv[k] : 0.f;     // tf.maximum(log_s, -7)
+            }
+        }
+    const float x1 = meet(gx), x2 = meet(gxr);
+    if (wave == 0 && live) {
+        d_mean[row] = c * x1;
+        d_scale[row] = c * x2 + (float)fac[1] / ss;         // H_Ps = mean(log scale_tot) + 2
+    }
+}
+
+// kl_bl = dl + (s_q^2 - s_p^2 + dm^2) / (2 s_p^2), reg = dl^2 with dl = log s_p - log s_q, dm = m_p - m_q
+__global__ __launch_bounds__(256) void dx_gauss_grad_kernel(const float* __restrict__ te, const float* __restrict__ mean_st,
+                                                            const float* __restrict__ scale_st, long long n,
+                                                            const double* __restrict__ fac, float* __restrict__ d_te,
+                                                            float* __restrict__ d_mean, float* __restrict__ d_scale) {
+    const long long i = (long long)blockIdx.x * DG_ROWS + threadIdx.x;
+    if (i >= n) return;
+    const float f0 = (float)fac[0], f1 = (float)fac[1];
+    const float raw = te[2 * i + 1], mp = te[2 * i];
+    const float lsp = fmaxf(raw, -7.0f), sp = expf(lsp);
+    const float mq = mean_st[i], sq = scale_st[i], lsq = logf(sq);
+    const float vp = sp * sp, dm = mp - mq, dl = lsp - lsq;
+    const float g_mp = f0 * dm / vp;
+    const float g_lsp = f0 * (1.f - (sq * sq + dm * dm) / vp) + f1 * 2.f * dl;
+    d_te[2 * i] = g_mp;
+    d_te[2 * i + 1] = raw >= -7.0f ? g_lsp : 0.f;
+    d_mean[i] = -g_mp;
+    d_scale[i] = f0 * (sq / vp - 1.f / sq) - f1 * 2.f * dl / sq;
+}
+
+// power loss transposed, per frame: c_k = 2 (|P_k| - |O_k|) (fac0 + [k < 384] fac1), then
+// d y_n = w_n sum_k c_k (re_k cos + im_k sin)(2 pi k n / 2048) / |P_k| (0 where |P_k| = 0) -> gframe[b][f][800]
+__global__ __launch_bounds__(256) void pw_grad_kernel(const float* __restrict__ pred, long long ps, const float* __restrict__ orig,
+                                                      long long os, long long L, int NF, const double* __restrict__ fac,
+                                                      float* __restrict__ gframe) {
+    __shared__ float tw[2 * PW_NFFT];
+    __shared__ float buf[2 * PW_FR * 1025];            // windowed frames [2][PW_FR][800], then coefficients [PW_FR][1025][2]
+    const int b = blockIdx.y, f0 = blockIdx.x * PW_FR;
+    const float fa = (float)fac[0], fp = (float)fac[1];
+    for (int i = threadIdx.x; i < PW_NFFT; i += 256) {
+        float s, c;
+        sincospif((float)i / (float)(PW_NFFT / 2), &s, &c);
+        tw[2 * i] = c;
+        tw[2 * i + 1] = s;
+    }
+    auto xs = [&](int p, int fr, int n) -> float& { return buf[(p * PW_FR + fr) * PW_WIN + n]; };
+    for (int i = threadIdx.x; i < PW_FR * PW_WIN; i += 256) {
+        const int fr = i / PW_WIN, n = i - fr * PW_WIN;
+        const long long j = (long long)(f0 + fr) * PW_HOP + n;
+        const float w = 0.5f - 0.5f * cospif((float)n / (float)(PW_WIN / 2));
+        const bool in = f0 + fr < NF && j < L;
+        xs(0, fr, n) = in ? pred[b * ps + j] * w : 0.f;
+        xs(1, fr, n) = in ? orig[b * os + j] * w : 0.f;
+    }
+    __syncthreads();
+    float re[2][4][PW_FR], im[2][4][PW_FR];
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int fr = 0; fr < PW_FR; ++fr) re[p][r][fr] = im[p][r][fr] = 0.f;
+    int idx[4] = {0, 0, 0, 0};
+    for (int n = 0; n < PW_WIN; ++n) {
+        float x[2][PW_FR];
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int fr = 0; fr < PW_FR; ++fr) x[p][fr] = xs(p, fr, n);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float c = tw[2 * idx[r]], s = tw[2 * idx[r] + 1];
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                for (int fr = 0; fr < PW_FR; ++fr) {
+                    re[p][r][fr] = fmaf(x[p][fr], c, re[p][r][fr]);
+                    im[p][r][fr] = fmaf(x[p][fr], s, im[p][r][fr]);
+                }
+            idx[r] = (idx[r] + (int)threadIdx.x + 256 * r) & (PW_NFFT - 1);
+        }
+    }
+    // bin 1024 (cos = (-1)^n, sin = 0): wave w on frame w
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float a0 = 0.f, a1 = 0.f;
+    for (int n = lane; n < PW_WIN; n += 64) {
+        a0 += (n & 1) ? -xs(0, wave, n) : xs(0, wave, n);
+        a1 += (n & 1) ? -xs(1, wave, n) : xs(1, wave, n);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a0 += __shfl_xor(a0, o);
+        a1 += __shfl_xor(a1, o);
+    }
+    __syncthreads();                                   // the frames are read; buf becomes the coefficients
+    auto cf = [&](int fr, int k, int c) -> float& { return buf[(fr * 1025 + k) * 2 + c]; };
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int k = threadIdx.x + 256 * r;
+#pragma unroll
+        for (int fr = 0; fr < PW_FR; ++fr) {
+            const float rp = re[0][r][fr], ip = im[0][r][fr];
+            const float mp = sqrtf(rp * rp + ip * ip);
+            const float mo = sqrtf(re[1][r][fr] * re[1][r][fr] + im[1][r][fr] * im[1][r][fr]);
+            const float g = mp > 0.f ? 2.f * (mp - mo) * (k < PW_PRIO ? fa + fp : fa) / mp : 0.f;   // |z|' = 0 at 0
+            cf(fr, k, 0) = g * rp;
+            cf(fr, k, 1) = g * ip;
+        }
+    }
+    if (lane == 0) {
+        const float mp = fabsf(a0);
+        cf(wave, 1024, 0) = mp > 0.f ? 2.f * (mp - fabsf(a1)) * fa * (a0 > 0.f ? 1.f : -1.f) : 0.f;
+        cf(wave, 1024, 1) = 0.f;
+    }
+    __syncthreads();
+    for (int n = threadIdx.x; n < PW_WIN; n += 256) {
+        float acc[PW_FR];
+#pragma unroll
+        for (int fr = 0; fr < PW_FR; ++fr) acc[fr] = 0.f;
+        int id = 0;
+        for (int k = 0; k <= 1024; ++k) {
+            const float c = tw[2 * id], s = tw[2 * id + 1];
+#pragma unroll
+            for (int fr = 0; fr < PW_FR; ++fr) acc[fr] = fmaf(cf(fr, k, 0), c, fmaf(cf(fr, k, 1), s, acc[fr]));
+            id = (id + n) & (PW_NFFT - 1);
+        }
+        const float w = 0.5f - 0.5f * cospif((float)n / (float)(PW_WIN / 2));
+#pragma unroll
+        for (int fr = 0; fr < PW_FR; ++fr)
+            if (f0 + fr < NF) gframe[((size_t)b * NF + f0 + fr) * PW_WIN + n] = acc[fr] * w;
+    }
+}
+
+// overlap-add of the frames' gradients, frames in increasing order: d pred[b][j] = sum_f gframe[b][f][j - 200 f]
+__global__ __launch_bounds__(256) void pw_ola_kernel(const float* __restrict__ gframe, long long L, int NF,
+                                                     float* __restrict__ dp, long long ds) {
+    const int b = blockIdx.y;
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= L) return;
+    const long long fhi = std::min<long long>(NF - 1, j / PW_HOP);
+    const long long flo = j >= PW_WIN ? (j - PW_WIN) / PW_HOP + 1 : 0;
+    float acc = 0.f;
+    for (long long f = flo; f <= fhi; ++f) acc += gframe[((size_t)b * NF + f) * PW_WIN + (j - f * PW_HOP)];
+    dp[b * ds + j] = acc;
+}
+
+}  // namespace
+
+extern "C" int wn_distill_mol_xent_grad(wn_handle* h, const float* out_params, int out_width, const float* mean_tot,
+                                        const float* scale_tot, int B, int64_t T, int S, const float* noise, uint64_t seed,
+                                        const double* fac, float* d_out_params, float* d_mean_tot, float* d_scale_tot,
+                                        void* stream) {
+    const char* fn = "wn_distill_mol_xent_grad";
+    int dummy = 0;
+    if (int rc = dx_check(h, fn, WN_LOSS_MOL, out_params, out_width, mean_tot, scale_tot, B, T, &dummy, &dummy, 0, 0))
+        return rc;
+    if (S < 1) return wn_fail(h, WN_EINVAL, "%s: num_samples = %d; the Monte-Carlo estimate needs at least one draw", fn, S);
+    if (!fac || !d_out_params || !d_mean_tot || !d_scale_tot) return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
+    const int M = h->cfg.mol_mix;
+    if (M < 1 || M > DX_MAX_MIX || out_width != 3 * M)
+        return wn_fail(h, WN_EINVAL, "%s: %d mixture components (1..%d supported)", fn, M, DX_MAX_MIX);
+    const WnWork work(h);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((T + DX_ROWS - 1) / DX_ROWS), (unsigned)B);
+    const int Q = 65536;
+    if (M <= 10)
+        hipLaunchKernelGGL(dx_mol_grad_kernel<10>, grid, dim3(256), 0, st, out_params, mean_tot, scale_tot, (long long)T, S, M,
+                           out_width, Q, noise, seed, fac, d_out_params, d_mean_tot, d_scale_tot);
+    else
+        hipLaunchKernelGGL(dx_mol_grad_kernel<DX_MAX_MIX>, grid, dim3(256), 0, st, out_params, mean_tot, scale_tot,
+                           (long long)T, S, M, out_width, Q, noise, seed, fac, d_out_params, d_mean_tot, d_scale_tot);
+    WN_HIP(h, hipGetLastError());
+    return WN_OK;
+}
+
+extern "C" int wn_distill_gauss_kl_grad(wn_handle* h, const float* out_params, int out_width, const float* mean_tot,
+                                        const float* scale_tot, int B, int64_t T, const double* fac, float* d_out_params,
+                                        float* d_mean_tot, float* d_scale_tot, void* stream) {
+    const char* fn = "wn_distill_gauss_kl_grad";
+    int dummy = 0;
+    if (int rc = dx_check(h, fn, WN_LOSS_GAUSS, out_params, out_width, mean_tot, scale_tot, B, T, &dummy, &dummy, 0, 0))
+        return rc;
+    if (!fac || !d_out_params || !d_mean_tot || !d_scale_tot) return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
+    const WnWork work(h);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const long long n = (long long)B * T;
+    hipLaunchKernelGGL(dx_gauss_grad_kernel, dim3((unsigned)dx_gauss_blocks(B, T)), dim3(256), 0, st, out_params, mean_tot,
+                       scale_tot, n, fac, d_out_params, d_mean_tot, d_scale_tot);
+    WN_HIP(h, hipGetLastError());
+    return WN_OK;
+}
+
+extern "C" size_t wn_power_loss_grad_workspace_bytes(int B, int64_t L) {
+    if (B < 1 || L < 1) return 0;
+    return align_up((size_t)B * pw_frames(L) * PW_WIN * sizeof(float), 256);
+}
+
+extern "C" int wn_power_loss_grad(const float* pred, int64_t pred_stride, const float* orig, int64_t orig_stride, int B,
+                                  int64_t L, const double* fac, float* d_pred, int64_t d_pred_stride, void* ws, size_t ws_bytes,
+                                  void* stream) {
+    const char* fn = "wn_power_loss_grad";
+    if (!pred || !orig || !fac || !d_pred || !ws) return wn_fail(nullptr, WN_EINVAL, "%s: null pointer", fn);
+    if (B < 1 || L < 1) return wn_fail(nullptr, WN_EINVAL, "%s: B = %d, L = %lld", fn, B, (long long)L);
+    if (pred_stride < L || orig_stride < L || d_pred_stride < L)
+        return wn_fail(nullptr, WN_EINVAL, "%s: row strides below the length %lld", fn, (long long)L);
+    if (L > 0x7fffffffll) return wn_fail(nullptr, WN_EINVAL, "%s: utterance too long", fn);
+    const size_t need = wn_power_loss_grad_workspace_bytes(B, L);
+    if (ws_bytes < need) return wn_fail(nullptr, WN_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    float* gframe = reinterpret_cast<float*>(ws);
+    const long long NF = pw_frames(L);
+    hipLaunchKernelGGL(pw_grad_kernel, dim3((unsigned)((NF + PW_FR - 1) / PW_FR), (unsigned)B), dim3(256), 0, st, pred,
+                       (long long)pred_stride, orig, (long long)orig_stride, (long long)L, (int)NF, fac, gframe);
+    hipLaunchKernelGGL(pw_ola_kernel, dim3((unsigned)((L + 255) / 256), (unsigned)B), dim3(256), 0, st, gframe, (long long)L,
+                       (int)NF, d_pred, (long long)d_pred_stride);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return wn_fail(nullptr, WN_EIO, "%s: launch failed: %s", fn, hipGetErrorString(e));
+    return WN_OK;
+}

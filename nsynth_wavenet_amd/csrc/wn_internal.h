@@ -122,11 +122,15 @@ struct TeacherGemmPack {
 };
 struct TeacherLayerPack {
     TeacherGemmPack gate, rs;
+    TeacherGemmPack gate_t, rs_t;   // input VJP (wn_teacher_backward_input): [width][3 gate], [gate/2][width + skip], zero bias
     int dilation;
 };
 struct TeacherPack {
     TeacherGemmPack skip_start, out1, out2;
+    TeacherGemmPack skip_start_t, out1_t, out2_t;   // transposes: [width][skip], [skip][skip], [skip][out_width padded to 32]
     std::vector<TeacherLayerPack> layers;
+    bool vjp_ok = false;            // the shape runs on the transposed GEMMs (width, skip, gate/2 multiples of 64)
+    uint64_t serial = 0;            // identity of the handle in the tapes it writes (wn_teacher_forward_tape)
 };
 
 struct wn_handle {

@@ -30,3 +30,23 @@ __device__ inline float wn_mol_component_lp(float x, float c, float inv, float i
     const float delta = wn_sigmoid(plus) * wn_sigmoid(-mn) * d;
     return x < min_thres ? plus - wn_softplus(plus) : (x > max_thres ? -wn_softplus(mn) : logf(fmaxf(delta, 1e-12f)));
 }
+
+// derivatives of wn_mol_component_lp at x in the same form (TensorFlow's tie conventions): dx = d lp / d x (= -d lp / d mean),
+// dinv = d lp / d inv_s.  Inside: log sigma(a) + log sigma(-b) + log(1 - e^-(a-b)) with a - b = 2 inv_s / Q, zero below the
+// 1e-12 floor; lower tail log sigma(a); upper tail log sigma(-b).
+__device__ inline void wn_mol_component_grad(float x, float c, float inv, float iq, float d, float min_thres, float max_thres,
+                                             float& dx, float& dinv) {
+    const float plus = inv * (c + iq), mn = inv * (c - iq);
+    float gp = 0.f, gm = 0.f, ge = 0.f;
+    if (x < min_thres) {
+        gp = wn_sigmoid(-plus);
+    } else if (x > max_thres) {
+        gm = -wn_sigmoid(mn);
+    } else if (wn_sigmoid(plus) * wn_sigmoid(-mn) * d >= 1e-12f) {
+        gp = wn_sigmoid(-plus);
+        gm = -wn_sigmoid(mn);
+        ge = 2.0f * iq / expm1f(2.0f * inv * iq);
+    }
+    dx = inv * (gp + gm);
+    dinv = (c + iq) * gp + (c - iq) * gm + ge;
+}

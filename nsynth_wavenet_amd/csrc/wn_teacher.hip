@@ -13,7 +13,10 @@
 // staged through LDS in double-buffered chunks shared by the four waves.  Epilogues: gate ->
 // m; residual add -> l and skip accumulate -> s; plain store; time-major out_params.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
+#include <mutex>
+#include <unordered_map>
 
 #include "wn_internal.h"
 #include "wn_codec.h"
@@ -29,7 +32,7 @@ constexpr int TG_KC = 4;                 // K-steps of weights per LDS stage
 constexpr int TG_XP = 64;                // zero left pad of the scaled input row
 
 enum { TG_SRC_G4 = 0, TG_SRC_ACC_RELU = 1 };
-enum { TG_EPI_GATE = 0, TG_EPI_RS = 1, TG_EPI_ACC = 2, TG_EPI_OUT = 3 };
+enum { TG_EPI_GATE = 0, TG_EPI_RS = 1, TG_EPI_ACC = 2, TG_EPI_OUT = 3, TG_EPI_GATE_TAPE = 4, TG_EPI_BGATE = 5, TG_EPI_MASK = 6 };
 
 struct TgSeg {
     const unsigned* base;   // G4 words or accumulator-layout floats
@@ -57,6 +60,11 @@ struct TgArgs {
     int res_mtiles;         // RS: m-tiles below this are residual rows, the rest skip rows
     float* otm;             // OUT: [B][T][ow]
     int ow;
+    // tape (accumulator layout [t/16][row block][lane][4] per batch element):  GATE_TAPE writes sigma at row block
+    // hb and tanh at tape_hoff + hb, BGATE reads them;  MASK reads the pre-ReLU rows of its own row blocks
+    float* tape;
+    long long tape_bstride;
+    int tape_nmb, tape_hoff;
 };
 
 // U = 64-row m-tiles per workgroup (1 or 2): two tiles halve the re-reads of the activation operand,
@@ -184,8 +192,9 @@ __global__ __launch_bounds__(256, 2) void tg_gemm_kernel(const TgArgs a) {
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) bv[mb] = bias4[mb * 4];
     f4 (&ac)[4][TG_NT] = *reinterpret_cast<f4 (*)[4][TG_NT]>(&acc[4 * u]);
-    if (EPI == TG_EPI_GATE) {
+    if (EPI == TG_EPI_GATE || EPI == TG_EPI_GATE_TAPE) {
         // rows 0-31: sigmoid half of gate channels 32 mt .. +31, rows 32-63: their tanh half
+        // (GATE_TAPE: the same arithmetic, and both activations go to the tape for the input VJP)
         wn_u4* o = reinterpret_cast<wn_u4*>(a.og4 + (size_t)b * a.og4_bstride) +
                    (size_t)(4 * mt + q) * a.og4_rowlen + a.og4_col0 + t0 + n;
         const size_t lo = (size_t)a.og4_ng * a.og4_rowlen;
@@ -193,19 +202,31 @@ __global__ __launch_bounds__(256, 2) void tg_gemm_kernel(const TgArgs a) {
         for (int e = 0; e < TG_NT; ++e) {
             wn_u4 gh, gl;
 #pragma unroll
-            for (int mg = 0; mg < 2; ++mg)
+            for (int mg = 0; mg < 2; ++mg) {
+                f4 sg, th;
 #pragma unroll
                 for (int rp = 0; rp < 2; ++rp) {
                     float g[2];
 #pragma unroll
-                    for (int k = 0; k < 2; ++k)
-                        g[k] = sigmoidf_(fmaf(ac[mg][e][2 * rp + k], inv, bv[mg][2 * rp + k])) *
-                               tanhf_(fmaf(ac[mg + 2][e][2 * rp + k], inv, bv[mg + 2][2 * rp + k]));
+                    for (int k = 0; k < 2; ++k) {
+                        const float sv = sigmoidf_(fmaf(ac[mg][e][2 * rp + k], inv, bv[mg][2 * rp + k]));
+                        const float tv = tanhf_(fmaf(ac[mg + 2][e][2 * rp + k], inv, bv[mg + 2][2 * rp + k]));
+                        g[k] = sv * tv;
+                        sg[2 * rp + k] = sv;
+                        th[2 * rp + k] = tv;
+                    }
                     unsigned hw, lw;
                     wn_split_pair(g[0], g[1], hw, lw);
                     gh[2 * mg + rp] = hw;
                     gl[2 * mg + rp] = lw;
                 }
+                if (EPI == TG_EPI_GATE_TAPE) {
+                    f4* tp = reinterpret_cast<f4*>(a.tape + (size_t)b * a.tape_bstride) +
+                             ((size_t)((t0 >> 4) + e) * a.tape_nmb + 2 * mt + mg) * 64 + lane;
+                    tp[0] = sg;
+                    tp[(size_t)a.tape_hoff * 64] = th;
+                }
+            }
             o[16 * e] = gh;
             o[lo + 16 * e] = gl;
         }
@@ -254,6 +275,78 @@ __global__ __launch_bounds__(256, 2) void tg_gemm_kernel(const TgArgs a) {
                 if (EPI == TG_EPI_RS) v += *p;
                 *p = v;
             }
+    } else if (EPI == TG_EPI_BGATE) {
+        // input VJP of the gate: dm rows h = 64 mt + 16 mb + 4 q + r (wavenet.py:264-269 transposed) ->
+        // dd_sigma[h] = dm tanh sigma (1 - sigma) and dd_tanh[h] = dm sigma (1 - tanh^2), G4 channels h and H + h
+        const size_t lo = (size_t)a.og4_ng * a.og4_rowlen;
+        const f4* tp = reinterpret_cast<const f4*>(a.tape + (size_t)b * a.tape_bstride) + lane;
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+            wn_u4* os = reinterpret_cast<wn_u4*>(a.og4 + (size_t)b * a.og4_bstride) +
+                        (size_t)(4 * (2 * mt + st) + q) * a.og4_rowlen + a.og4_col0 + t0 + n;
+            wn_u4* ot = os + (size_t)(2 * a.tape_hoff) * a.og4_rowlen;
+#pragma unroll
+            for (int e = 0; e < TG_NT; ++e) {
+                wn_u4 sh, sl, th, tl;
+#pragma unroll
+                for (int mg = 0; mg < 2; ++mg) {
+                    const int mb = 2 * st + mg;
+                    const size_t ti = ((size_t)((t0 >> 4) + e) * a.tape_nmb + 4 * mt + mb) * 64;
+                    const f4 sg = tp[ti], tg = tp[ti + (size_t)a.tape_hoff * 64];
+                    float vs[4], vt[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float dm = ac[mb][e][r] * inv;
+                        vs[r] = dm * tg[r] * (sg[r] * (1.f - sg[r]));
+                        vt[r] = dm * sg[r] * (1.f - tg[r] * tg[r]);
+                    }
+#pragma unroll
+                    for (int rp = 0; rp < 2; ++rp) {
+                        unsigned hw, lw;
+                        wn_split_pair(vs[2 * rp], vs[2 * rp + 1], hw, lw);
+                        sh[2 * mg + rp] = hw;
+                        sl[2 * mg + rp] = lw;
+                        wn_split_pair(vt[2 * rp], vt[2 * rp + 1], hw, lw);
+                        th[2 * mg + rp] = hw;
+                        tl[2 * mg + rp] = lw;
+                    }
+                }
+                os[16 * e] = sh;
+                os[lo + 16 * e] = sl;
+                ot[16 * e] = th;
+                ot[lo + 16 * e] = tl;
+            }
+        }
+    } else if (EPI == TG_EPI_MASK) {
+        // ReLU transposed: G4 rows 64 mt + ... = acc where the taped pre-ReLU value of the same row is > 0, else 0
+        const size_t lo = (size_t)a.og4_ng * a.og4_rowlen;
+        const f4* tp = reinterpret_cast<const f4*>(a.tape + (size_t)b * a.tape_bstride) + lane;
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+            wn_u4* o = reinterpret_cast<wn_u4*>(a.og4 + (size_t)b * a.og4_bstride) +
+                       (size_t)(4 * (2 * mt + st) + q) * a.og4_rowlen + a.og4_col0 + t0 + n;
+#pragma unroll
+            for (int e = 0; e < TG_NT; ++e) {
+                wn_u4 nh, nl;
+#pragma unroll
+                for (int mg = 0; mg < 2; ++mg) {
+                    const int mb = 2 * st + mg;
+                    const f4 mk = tp[((size_t)((t0 >> 4) + e) * a.tape_nmb + 4 * mt + mb) * 64];
+                    float v[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = mk[r] > 0.f ? ac[mb][e][r] * inv : 0.f;
+#pragma unroll
+                    for (int rp = 0; rp < 2; ++rp) {
+                        unsigned hw, lw;
+                        wn_split_pair(v[2 * rp], v[2 * rp + 1], hw, lw);
+                        nh[2 * mg + rp] = hw;
+                        nl[2 * mg + rp] = lw;
+                    }
+                }
+                o[16 * e] = nh;
+                o[lo + 16 * e] = nl;
+            }
+        }
     } else {
         // out_params, the reference's [B][T][out_width]
 #pragma unroll
@@ -417,6 +510,45 @@ int wn_pack_teacher(wn_handle* h, std::vector<float>& blob) {
     }
     T.out1 = gemm(A.wo1_off, A.bo1_off, S, S + Cd, S / 64, ident(S));
     T.out2 = gemm(A.wo2_off, A.bo2_off, OW, S, (OW + 63) / 64, ident(OW));
+
+    // transposed packs of the input VJP (wn_teacher_backward_input): A = W^T, zero bias, same fragment order and scaling
+    static std::atomic<uint64_t> next_serial{1};
+    T.serial = next_serial++;
+    T.vjp_ok = W % 64 == 0 && S % 64 == 0 && H % 64 == 0 && OW <= 64;
+    if (!T.vjp_ok) return WN_OK;
+    auto gemm_t = [&](const std::vector<float>& src, int M, int K) {
+        TeacherGemmPack g;
+        const float sc = pick_scale(src.data(), src.size());
+        g.inv_scale = 1.0f / sc;
+        g.nks = K / 32;
+        g.mtiles = M / 64;
+        g.w_off = reserve((size_t)g.mtiles * g.nks * 4 * 512);
+        pack_tiles(blob, g.w_off, src.data(), K, K, g.mtiles, sc, ident(M));
+        g.b_off = reserve((size_t)g.mtiles * 64);             // zeros
+        return g;
+    };
+    // [nc][Kp] transpose of columns c0 .. c0 + nc - 1 of the R x C row-major matrix at `off` (columns R .. Kp - 1 zero)
+    auto transpose = [&](size_t off, int R, int C, int c0, int nc, int Kp) {
+        std::vector<float> t((size_t)nc * Kp, 0.f);
+        for (int r = 0; r < R; ++r)
+            for (int j = 0; j < nc; ++j) t[(size_t)j * Kp + r] = blob[off + (size_t)r * C + c0 + j];
+        return t;
+    };
+    const int OWp = (OW + 31) / 32 * 32;
+    T.skip_start_t = gemm_t(transpose(A.wss_off, S, W, 0, W, S), W, S);
+    T.out1_t = gemm_t(transpose(A.wo1_off, S, S + Cd, 0, S, S), S, S);
+    T.out2_t = gemm_t(transpose(A.wo2_off, OW, S, 0, S, OWp), S, OWp);
+    for (size_t i = 0; i < A.layers.size(); ++i) {
+        const ArLayerPack& lp = A.layers[i];
+        T.layers[i].rs_t = gemm_t(transpose(lp.wrs_off, W + S, H, 0, H, W + S), H, W + S);
+        // [width][tap 0 gate | tap 1 gate | tap 2 gate]: dl(t) += sum_k W_dil[k]^T dd(t + (2 - k) dilation)
+        std::vector<float> t((size_t)W * 3 * G);
+        const int ld = 3 * W + Cd;
+        for (int g = 0; g < G; ++g)
+            for (int k = 0; k < 3; ++k)
+                for (int w = 0; w < W; ++w) t[(size_t)w * 3 * G + k * G + g] = blob[lp.wd_off + (size_t)g * ld + k * W + w];
+        T.layers[i].gate_t = gemm_t(t, W, 3 * G);
+    }
     return WN_OK;
 }
 
@@ -490,31 +622,40 @@ extern "C" size_t wn_teacher_workspace_bytes(const wn_handle* h, int B, int F, i
     return wn_teacher_ws_bytes(h, B, F, T);
 }
 
-extern "C" int wn_teacher_forward(wn_handle* h, const float* wav, const float* mel, int B, int F, int64_t T,
-                                  float* out_params, void* ws, size_t ws_bytes, void* stream) {
-    if (!h) return wn_fail(nullptr, WN_EINVAL, "wn_teacher_forward: null handle");
-    if (!h->finalized) return wn_fail(h, WN_ESTATE, "wn_teacher_forward: call wn_finalize first");
+// checks of the forward calls (message prefix fn)
+static int tg_forward_check(wn_handle* h, const char* fn, const float* wav, const float* mel, int B, int F, int64_t T,
+                            const float* out_params, const void* ws) {
+    if (!h) return wn_fail(nullptr, WN_EINVAL, "%s: null handle", fn);
+    if (!h->finalized) return wn_fail(h, WN_ESTATE, "%s: call wn_finalize first", fn);
     const wn_config& c = h->cfg;
-    if (c.kind != WN_KIND_TEACHER) return wn_fail(h, WN_EINVAL, "wn_teacher_forward: handle is not a Wavenet teacher");
+    if (c.kind != WN_KIND_TEACHER) return wn_fail(h, WN_EINVAL, "%s: handle is not a Wavenet teacher", fn);
     if (B < 1 || F < 1 || T < 1 || !wav || !mel || !out_params || !ws)
-        return wn_fail(h, WN_EINVAL, "wn_teacher_forward: bad argument");
-    const WnWork work(h);
+        return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
     const long long TE = (long long)F * h->frame_shift, md = 1ll << (c.num_stages - 1);
-    if (T > TE) return wn_fail(h, WN_EINVAL, "wn_teacher_forward: %lld samples need more than %d mel frames "
-                               "(wavenet.py:79 assert cond_len >= x_len)", (long long)T, F);
-    if (T % md) return wn_fail(h, WN_EINVAL, "wn_teacher_forward: length %lld is not a multiple of the largest "
-                               "dilation %lld (masked.py:188)", (long long)T, md);
-    if (TE > 2000000) return wn_fail(h, WN_EINVAL, "wn_teacher_forward: utterance too long (32-bit row offsets)");
+    if (T > TE) return wn_fail(h, WN_EINVAL, "%s: %lld samples need more than %d mel frames "
+                               "(wavenet.py:79 assert cond_len >= x_len)", fn, (long long)T, F);
+    if (T % md) return wn_fail(h, WN_EINVAL, "%s: length %lld is not a multiple of the largest "
+                               "dilation %lld (masked.py:188)", fn, (long long)T, md);
+    if (TE > 2000000) return wn_fail(h, WN_EINVAL, "%s: utterance too long (32-bit row offsets)", fn);
+    return WN_OK;
+}
+
+// the forward; with tape_s != nullptr the skip sum and out1 rows land in the tape and every gate stores its activations
+// to tape_g (layer i at i * B * gate * Tp floats) -- the same arithmetic, so out_params are the same bits either way
+static int tg_forward(wn_handle* h, const char* fn, const float* wav, const float* mel, int B, int F, int64_t T,
+                      float* out_params, void* ws, size_t ws_bytes, float* tape_s, float* tape_h1, float* tape_g,
+                      void* stream) {
+    const wn_config& c = h->cfg;
     const TLayout L = t_layout(h, B, F, T);
     if (ws_bytes < L.total)
-        return wn_fail(h, WN_ENOMEM, "wn_teacher_forward: workspace %zu < %zu bytes", ws_bytes, L.total);
+        return wn_fail(h, WN_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, L.total);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     char* base = reinterpret_cast<char*>(ws);
     float* enc = reinterpret_cast<float*>(base + L.enc);
     unsigned* l = reinterpret_cast<unsigned*>(base + L.l);
     unsigned* m = reinterpret_cast<unsigned*>(base + L.m);
-    float* s = reinterpret_cast<float*>(base + L.s);
-    float* h1 = reinterpret_cast<float*>(base + L.h1);
+    float* s = tape_s ? tape_s : reinterpret_cast<float*>(base + L.s);
+    float* h1 = tape_h1 ? tape_h1 : reinterpret_cast<float*>(base + L.h1);
     float* xs = reinterpret_cast<float*>(base + L.xs);
     const int W = c.width, S = c.skip_width, H = c.gate_width / 2, Cd = c.deconv_width;
     const TeacherPack& P = h->teacher;
@@ -560,7 +701,8 @@ extern "C" int wn_teacher_forward(wn_handle* h, const float* wav, const float* m
         a.oacc = s; a.oacc_bstride = (long long)S * L.Tp; a.oacc_nmb = S / 16;
         tg_launch<TG_EPI_ACC>(a, P.skip_start.mtiles, B, L.Tp, st);
     }
-    for (const TeacherLayerPack& tl : P.layers) {
+    for (size_t li = 0; li < P.layers.size(); ++li) {
+        const TeacherLayerPack& tl = P.layers[li];
         {   // d = dilated_conv(l) + mel_cond(enc); m = sigmoid(d[:H]) * tanh(d[H:])  (wavenet.py:243-269)
             TgArgs a = base_args(tl.gate);
             for (int tap = 0; tap < 3; ++tap) {
@@ -569,7 +711,13 @@ extern "C" int wn_teacher_forward(wn_handle* h, const float* wav, const float* m
             }
             a.seg[3] = seg_enc; a.nseg = 4;
             a.og4 = m; a.og4_bstride = (long long)H * L.Tp; a.og4_rowlen = (int)L.Tp; a.og4_col0 = 0; a.og4_ng = H / 8;
-            tg_launch<TG_EPI_GATE>(a, tl.gate.mtiles, B, L.Tp, st);
+            if (tape_g) {
+                a.tape = tape_g + li * (size_t)B * 2 * H * L.Tp;
+                a.tape_bstride = 2ll * H * L.Tp; a.tape_nmb = 2 * H / 16; a.tape_hoff = H / 16;
+                tg_launch<TG_EPI_GATE_TAPE>(a, tl.gate.mtiles, B, L.Tp, st);
+            } else {
+                tg_launch<TG_EPI_GATE>(a, tl.gate.mtiles, B, L.Tp, st);
+            }
         }
         {   // l += res(m); s += skip(m)  (wavenet.py:271-277)
             TgArgs a = base_args(tl.rs);
@@ -596,6 +744,14 @@ extern "C" int wn_teacher_forward(wn_handle* h, const float* wav, const float* m
     return WN_OK;
 }
 
+extern "C" int wn_teacher_forward(wn_handle* h, const float* wav, const float* mel, int B, int F, int64_t T,
+                                  float* out_params, void* ws, size_t ws_bytes, void* stream) {
+    const char* fn = "wn_teacher_forward";
+    if (int rc = tg_forward_check(h, fn, wav, mel, B, F, T, out_params, ws)) return rc;
+    const WnWork work(h);
+    return tg_forward(h, fn, wav, mel, B, F, T, out_params, ws, ws_bytes, nullptr, nullptr, nullptr, stream);
+}
+
 extern "C" int wn_teacher_log_prob(wn_handle* h, const float* out_params, const float* wav, int B, int64_t T, float* log_prob,
                                    void* stream) {
     if (!h) return wn_fail(nullptr, WN_EINVAL, "wn_teacher_log_prob: null handle");
@@ -609,6 +765,328 @@ extern "C" int wn_teacher_log_prob(wn_handle* h, const float* out_params, const 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(tg_log_prob_kernel, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, st, out_params, wav, log_prob,
                        n, c.out_width, c.loss_type, Q, c.use_mu_law);
+    WN_HIP(h, hipGetLastError());
+    return WN_OK;
+}
+
+// ---- input VJP of the teacher: d out_params [B,T,ow] -> d wav [B,T], weights frozen ----
+// The tape (wn_teacher_forward_tape) holds what the reverse pass reads: a header, the pre-ReLU skip sum s and out1 rows
+// (accumulator layout, as the forward keeps them), and sigma / tanh of every gate.  The reverse pass runs the forward's
+// GEMM kernel on the transposed packs: d out2 and d out1 through the ReLU masks (MASK), then per layer from the last one
+// dm = W_res^T dl + W_skip^T ds with the gate derivative in the epilogue (BGATE) and dl += sum_k W_dil[k]^T dd(t + (2-k) d)
+// in place (RS, anti-causal taps: dd rows carry a zero right pad of 2 * max dilation), then skip_start^T and the start
+// conv transposed.  The operands are split-fp16 like the forward's, so d out_params enter scaled by a power of two that
+// brings their largest magnitude to [1, 2) (found on the device) and d wav leaves unscaled: the VJP is linear.
+namespace {
+constexpr uint32_t TB_MAGIC = 0x31505457u;      // "WTP1"
+constexpr size_t TB_HEAD = 256;
+constexpr int TB_NMAX = 1024;                   // workgroups of the max-magnitude pass
+
+struct TapeRec {
+    uint64_t serial;
+    int B;
+    long long T;
+};
+std::mutex g_tape_mu;
+std::unordered_map<const void*, TapeRec> g_tapes;   // tape address -> the handle and shape that last wrote it
+
+struct TapeLayout {
+    long long Tp;
+    size_t s, h1, g, total;
+};
+TapeLayout tape_layout(const wn_handle* h, int B, long long T) {
+    const wn_config& c = h->cfg;
+    TapeLayout L;
+    L.Tp = (T + TG_TN - 1) / TG_TN * TG_TN;
+    const size_t cols = (size_t)B * L.Tp;
+    L.s = TB_HEAD;
+    L.h1 = L.s + cols * c.skip_width * sizeof(float);
+    L.g = L.h1 + cols * c.skip_width * sizeof(float);
+    L.total = L.g + h->teacher.layers.size() * cols * c.gate_width * sizeof(float);
+    return L;
+}
+
+struct BLayout {
+    long long Tp, RD;
+    int Kp;
+    size_t scal, dout, dh1, ds, dl, dd, total;
+};
+BLayout b_layout(const wn_handle* h, int B, long long T) {
+    const wn_config& c = h->cfg;
+    BLayout L;
+    L.Tp = (T + TG_TN - 1) / TG_TN * TG_TN;
+    L.RD = L.Tp + 2 * (1ll << (c.num_stages - 1));
+    L.Kp = h->teacher.out2_t.nks * 32;
+    size_t o = 0;
+    auto carve = [&](size_t words) { size_t r = o; o += align_up(words * 4, 256); return r; };
+    L.scal = carve(4 + TB_NMAX);
+    L.dout = carve((size_t)B * L.Kp * L.Tp);
+    L.dh1 = carve((size_t)B * c.skip_width * L.Tp);
+    L.ds = carve((size_t)B * c.skip_width * L.Tp);
+    L.dl = carve((size_t)B * c.width * L.Tp);
+    L.dd = carve((size_t)B * c.gate_width * L.RD);
+    L.total = o;
+    return L;
+}
+
+struct TbHead {
+    unsigned w[8];
+};
+__global__ void tb_header_kernel(TbHead v, unsigned* __restrict__ dst) {
+    if (threadIdx.x < 8) dst[threadIdx.x] = v.w[threadIdx.x];
+}
+
+__device__ inline float tb_wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+// largest |x| per workgroup, then one workgroup: scal[0] = 2^k with max |x| 2^k in [1, 2), scal[1] = 2^-k
+__global__ __launch_bounds__(256) void tb_absmax_kernel(const float* __restrict__ x, long long n, float* __restrict__ part) {
+    __shared__ float sh[4];
+    float m = 0.f;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) m = fmaxf(m, fabsf(x[i]));
+    m = tb_wave_max(m);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+}
+__global__ __launch_bounds__(256) void tb_scale_kernel(const float* __restrict__ part, int np, float* __restrict__ scal) {
+    __shared__ float sh[4];
+    float m = 0.f;
+    for (int i = threadIdx.x; i < np; i += 256) m = fmaxf(m, part[i]);
+    m = tb_wave_max(m);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        m = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+        int k = 0;
+        if (m > 0.f && m < __builtin_inff()) k = min(max(-ilogbf(m), -100), 100);
+        scal[0] = ldexpf(1.f, k);
+        scal[1] = ldexpf(1.f, -k);
+    }
+}
+
+// d out_params [B,T,ow] (scaled by scal[0]) -> G4 rows of Kp channels (zero beyond ow and from column T on)
+__global__ __launch_bounds__(256) void tb_dout_kernel(const float* __restrict__ dout, const float* __restrict__ scal,
+                                                      unsigned* __restrict__ g4, long long T, long long Tp, int ow, int Kp) {
+    const int b = blockIdx.z, gr = blockIdx.y, NG = Kp / 8;
+    const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (c >= Tp) return;
+    const float sc = scal[0];
+    const int s4 = gr >> 2, kg = gr & 3;
+    wn_u4 hw, lw;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float o[2];
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+            const int ch = 32 * s4 + 16 * (i >> 1) + 4 * kg + 2 * (i & 1) + hh;
+            o[hh] = c < T && ch < ow ? dout[((size_t)b * T + c) * ow + ch] * sc : 0.f;
+        }
+        unsigned a, a2;
+        wn_split_pair(o[0], o[1], a, a2);
+        hw[i] = a;
+        lw[i] = a2;
+    }
+    unsigned* base = g4 + (size_t)b * Kp * Tp;
+    *reinterpret_cast<wn_u4*>(base + ((size_t)gr * Tp + c) * 4) = hw;
+    *reinterpret_cast<wn_u4*>(base + ((size_t)(NG + gr) * Tp + c) * 4) = lw;
+}
+
+// conv_start transposed (tg_start_kernel: l0(t) = b + w0 x(t-3) + w1 x(t-2) + w2 x(t-1)):
+// d wav(t) = scal[1] sum_c (w0[c] dl0[c](t+3) + w1[c] dl0[c](t+2) + w2[c] dl0[c](t+1)); 64 columns x 4 waves of channels
+__global__ __launch_bounds__(256) void tb_dx_kernel(const unsigned* __restrict__ dl, const float* __restrict__ wb,
+                                                    const float* __restrict__ scal, float* __restrict__ dwav, int W,
+                                                    long long T, long long Tp) {
+    __shared__ float red[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.y, NG = W / 8;
+    const long long t = (long long)blockIdx.x * 64 + lane;
+    float acc = 0.f;
+    if (t < T) {
+        const unsigned* base = dl + (size_t)b * W * Tp;
+        for (int gr = wave; gr < NG; gr += 4) {
+            const int s4 = gr >> 2, kg = gr & 3;
+            for (int k = 0; k < 3; ++k) {
+                const long long col = t + 3 - k;
+                if (col >= T) continue;
+                const wn_u4 hw = *reinterpret_cast<const wn_u4*>(base + ((size_t)gr * Tp + col) * 4);
+                const wn_u4 lw = *reinterpret_cast<const wn_u4*>(base + ((size_t)(NG + gr) * Tp + col) * 4);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    float v0, v1;
+                    wn_join_pair(hw[i], lw[i], v0, v1);
+                    const int ch = 32 * s4 + 16 * (i >> 1) + 4 * kg + 2 * (i & 1);
+                    acc = fmaf(wb[k * W + ch], v0, acc);
+                    acc = fmaf(wb[k * W + ch + 1], v1, acc);
+                }
+            }
+        }
+    }
+    red[wave][lane] = acc;
+    __syncthreads();
+    if (wave == 0 && t < T) dwav[(size_t)b * T + t] = (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) * scal[1];
+}
+
+// what the two VJP-side calls refuse (the distillation losses' own refusals, wn_distill.hip)
+int tb_check(wn_handle* h, const char* fn) {
+    if (!h) return wn_fail(nullptr, WN_EINVAL, "%s: null handle", fn);
+    const wn_config& c = h->cfg;
+    if (c.kind != WN_KIND_TEACHER)
+        return wn_fail(h, WN_EINVAL, "%s: this is a ParallelWavenet student handle; the teacher's input VJP runs under the "
+                       "TEACHER's handle", fn);
+    if (c.loss_type == WN_LOSS_CE)
+        return wn_fail(h, WN_EINVAL, "%s: cross-entropy (ce) teacher: the distillation losses need a mol or gauss teacher "
+                       "(parallel_wavenet.py:133-135)", fn);
+    if (c.use_mu_law)
+        return wn_fail(h, WN_EINVAL, "%s: mu-law teacher: mu-law students and teachers are not supported by the "
+                       "distillation losses", fn);
+    if (!h->finalized) return wn_fail(h, WN_ESTATE, "%s: call wn_finalize first", fn);
+    if (!h->teacher.vjp_ok)
+        return wn_fail(h, WN_EINVAL, "%s: width %d, skip_width %d, gate_width / 2 = %d must be multiples of 64 and "
+                       "out_width <= 64 for the transposed GEMMs", fn, c.width, c.skip_width, c.gate_width / 2);
+    return WN_OK;
+}
+}  // namespace
+
+extern "C" size_t wn_teacher_tape_bytes(const wn_handle* h, int B, int64_t T) {
+    if (!h || !h->finalized || h->cfg.kind != WN_KIND_TEACHER || B < 1 || T < 1) return 0;
+    return tape_layout(h, B, T).total;
+}
+
+extern "C" size_t wn_teacher_backward_workspace_bytes(const wn_handle* h, int B, int64_t T) {
+    if (!h || !h->finalized || h->cfg.kind != WN_KIND_TEACHER || !h->teacher.vjp_ok || B < 1 || T < 1) return 0;
+    return b_layout(h, B, T).total;
+}
+
+extern "C" int wn_teacher_forward_tape(wn_handle* h, const float* wav, const float* mel, int B, int F, int64_t T,
+                                       float* out_params, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes,
+                                       void* stream) {
+    const char* fn = "wn_teacher_forward_tape";
+    if (int rc = tb_check(h, fn)) return rc;
+    if (int rc = tg_forward_check(h, fn, wav, mel, B, F, T, out_params, ws)) return rc;
+    if (!tape) return wn_fail(h, WN_EINVAL, "%s: bad argument (tape)", fn);
+    const TapeLayout TL = tape_layout(h, B, T);
+    if (tape_bytes < TL.total) return wn_fail(h, WN_ENOMEM, "%s: tape %zu < %zu bytes", fn, tape_bytes, TL.total);
+    const WnWork work(h);
+    char* tb = reinterpret_cast<char*>(tape);
+    TbHead hd;
+    const uint64_t ser = h->teacher.serial;
+    hd.w[0] = TB_MAGIC; hd.w[1] = (unsigned)ser; hd.w[2] = (unsigned)(ser >> 32); hd.w[3] = (unsigned)B;
+    hd.w[4] = (unsigned)T; hd.w[5] = (unsigned)((uint64_t)T >> 32); hd.w[6] = (unsigned)h->teacher.layers.size();
+    hd.w[7] = (unsigned)F;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(tb_header_kernel, dim3(1), dim3(64), 0, st, hd, reinterpret_cast<unsigned*>(tb));
+    const int rc = tg_forward(h, fn, wav, mel, B, F, T, out_params, ws, ws_bytes, reinterpret_cast<float*>(tb + TL.s),
+                              reinterpret_cast<float*>(tb + TL.h1), reinterpret_cast<float*>(tb + TL.g), stream);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(g_tape_mu);
+    g_tapes[tape] = TapeRec{ser, B, (long long)T};
+    return WN_OK;
+}
+
+extern "C" int wn_teacher_backward_input(wn_handle* h, const void* tape, size_t tape_bytes, const float* d_out_params,
+                                         int B, int64_t T, float* d_wav, void* ws, size_t ws_bytes, void* stream) {
+    const char* fn = "wn_teacher_backward_input";
+    if (int rc = tb_check(h, fn)) return rc;
+    if (B < 1 || T < 1 || !tape || !d_out_params || !d_wav || !ws) return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
+    const TapeLayout TL = tape_layout(h, B, T);
+    if (tape_bytes < TL.total)
+        return wn_fail(h, WN_EINVAL, "%s: a tape of %zu bytes cannot hold B = %d, T = %lld (%zu bytes)", fn, tape_bytes, B,
+                       (long long)T, TL.total);
+    {
+        std::lock_guard<std::mutex> lk(g_tape_mu);
+        auto it = g_tapes.find(tape);
+        if (it == g_tapes.end() || it->second.serial != h->teacher.serial)
+            return wn_fail(h, WN_EINVAL, "%s: the tape was not written by wn_teacher_forward_tape of this handle", fn);
+        if (it->second.B != B || it->second.T != (long long)T)
+            return wn_fail(h, WN_EINVAL, "%s: the tape holds B = %d, T = %lld, not B = %d, T = %lld", fn, it->second.B,
+                           it->second.T, B, (long long)T);
+    }
+    const BLayout L = b_layout(h, B, T);
+    if (ws_bytes < L.total) return wn_fail(h, WN_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, L.total);
+    const WnWork work(h);
+    const wn_config& c = h->cfg;
+    const int W = c.width, S = c.skip_width, G = c.gate_width, H = G / 2;
+    const TeacherPack& P = h->teacher;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char* base = reinterpret_cast<char*>(ws);
+    float* scal = reinterpret_cast<float*>(base + L.scal);
+    unsigned* dout = reinterpret_cast<unsigned*>(base + L.dout);
+    unsigned* dh1 = reinterpret_cast<unsigned*>(base + L.dh1);
+    unsigned* ds = reinterpret_cast<unsigned*>(base + L.ds);
+    unsigned* dl = reinterpret_cast<unsigned*>(base + L.dl);
+    unsigned* dd = reinterpret_cast<unsigned*>(base + L.dd);
+    const char* tb = reinterpret_cast<const char*>(tape);
+    float* tape_s = const_cast<float*>(reinterpret_cast<const float*>(tb + TL.s));
+    float* tape_h1 = const_cast<float*>(reinterpret_cast<const float*>(tb + TL.h1));
+    float* tape_g = const_cast<float*>(reinterpret_cast<const float*>(tb + TL.g));
+    const long long Tp = L.Tp;
+
+    // operand scale
+    const long long n = (long long)B * T * c.out_width;
+    const int nb = (int)std::min<long long>(TB_NMAX, (n + 255) / 256);
+    hipLaunchKernelGGL(tb_absmax_kernel, dim3(nb), dim3(256), 0, st, d_out_params, n, scal + 4);
+    hipLaunchKernelGGL(tb_scale_kernel, dim3(1), dim3(256), 0, st, scal + 4, nb, scal);
+    hipLaunchKernelGGL(tb_dout_kernel, dim3((unsigned)((Tp + 255) / 256), L.Kp / 8, B), dim3(256), 0, st, d_out_params, scal,
+                       dout, (long long)T, Tp, c.out_width, L.Kp);
+    WN_HIP(h, hipMemsetAsync(dl, 0, (size_t)B * W * Tp * 4, st));
+    WN_HIP(h, hipMemsetAsync(dd, 0, (size_t)B * G * L.RD * 4, st));
+
+    auto seg = [](const unsigned* p, long long bstride, long long rowlen, long long col0, int C) {
+        TgSeg sg;
+        sg.base = p; sg.bstride = bstride; sg.rowlen = (int)rowlen; sg.col0 = (int)col0; sg.nks = C / 32; sg.ng = C / 8;
+        sg.kind = TG_SRC_G4;
+        return sg;
+    };
+    auto args = [&](const TeacherGemmPack& g, unsigned* og4, long long obstride, long long orowlen, int C) {
+        TgArgs a{};
+        a.wp = reinterpret_cast<const unsigned*>(h->d_blob + g.w_off);
+        a.bias = h->d_blob + g.b_off;
+        a.inv_scale = g.inv_scale;
+        a.nks = g.nks;
+        a.T = T;
+        a.og4 = og4; a.og4_bstride = obstride; a.og4_rowlen = (int)orowlen; a.og4_col0 = 0; a.og4_ng = C / 8;
+        return a;
+    };
+    const TgSeg seg_ds = seg(ds, (long long)S * Tp, Tp, 0, S), seg_dl = seg(dl, (long long)W * Tp, Tp, 0, W);
+    {   // d relu(h1) = W_out2^T d out, masked by h1 > 0  (wavenet.py:290-292)
+        TgArgs a = args(P.out2_t, dh1, (long long)S * Tp, Tp, S);
+        a.seg[0] = seg(dout, (long long)L.Kp * Tp, Tp, 0, L.Kp); a.nseg = 1;
+        a.tape = tape_h1; a.tape_bstride = (long long)S * Tp; a.tape_nmb = S / 16;
+        tg_launch<TG_EPI_MASK>(a, P.out2_t.mtiles, B, Tp, st);
+    }
+    {   // ds = W_out1^T d h1 (its skip columns), masked by s > 0  (wavenet.py:283-289)
+        TgArgs a = args(P.out1_t, ds, (long long)S * Tp, Tp, S);
+        a.seg[0] = seg(dh1, (long long)S * Tp, Tp, 0, S); a.nseg = 1;
+        a.tape = tape_s; a.tape_bstride = (long long)S * Tp; a.tape_nmb = S / 16;
+        tg_launch<TG_EPI_MASK>(a, P.out1_t.mtiles, B, Tp, st);
+    }
+    for (size_t li = P.layers.size(); li-- > 0;) {
+        const TeacherLayerPack& tl = P.layers[li];
+        {   // dm = W_res^T dl + W_skip^T ds -> dd through the gate derivative  (wavenet.py:264-277 transposed)
+            TgArgs a = args(tl.rs_t, dd, (long long)G * L.RD, L.RD, G);
+            a.seg[0] = seg_dl; a.seg[1] = seg_ds; a.nseg = 2;
+            a.tape = tape_g + li * (size_t)B * G * Tp; a.tape_bstride = (long long)G * Tp; a.tape_nmb = G / 16;
+            a.tape_hoff = H / 16;
+            tg_launch<TG_EPI_BGATE>(a, tl.rs_t.mtiles, B, Tp, st);
+        }
+        {   // dl += sum_k W_dil[k]^T dd(t + (2 - k) dilation)  (wavenet.py:243-262 transposed)
+            TgArgs a = args(tl.gate_t, dl, (long long)W * Tp, Tp, W);
+            for (int k = 0; k < 3; ++k) a.seg[k] = seg(dd, (long long)G * L.RD, L.RD, (long long)(2 - k) * tl.dilation, G);
+            a.nseg = 3;
+            a.res_mtiles = W / 64;
+            tg_launch<TG_EPI_RS>(a, tl.gate_t.mtiles, B, Tp, st);
+        }
+    }
+    {   // dl0 += W_skip_start^T ds  (wavenet.py:231-233)
+        TgArgs a = args(P.skip_start_t, dl, (long long)W * Tp, Tp, W);
+        a.seg[0] = seg_ds; a.nseg = 1;
+        a.res_mtiles = W / 64;
+        tg_launch<TG_EPI_RS>(a, P.skip_start_t.mtiles, B, Tp, st);
+    }
+    hipLaunchKernelGGL(tb_dx_kernel, dim3((unsigned)((T + 63) / 64), B), dim3(256), 0, st, dl,
+                       h->d_blob + h->ar.start_off, scal, d_wav, W, (long long)T, Tp);
     WN_HIP(h, hipGetLastError());
     return WN_OK;
 }

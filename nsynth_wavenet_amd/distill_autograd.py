@@ -1,0 +1,98 @@
+"""torch.autograd Functions of the distillation losses.
+
+Each forward calls the HIP kernels the no-grad loss path calls (so the values are the same bits) and each backward the
+gradient kernels of csrc/wn_teacher.hip / wn_distill.hip.  The loss Functions return the raw float64 sums of their kernels;
+the scalar arithmetic of the losses stays in torch, so a backward receives d loss / d sums as a device tensor and hands it
+to the kernels without a host read.  The teacher is frozen: TeacherForward differentiates with respect to the audio only.
+"""
+import torch
+
+from . import engine as _engine
+
+
+class TeacherForward(torch.autograd.Function):
+    """wav [B,T] -> out_params [B,T,out_width] of a teacher Engine; holds the tape of wn_teacher_forward_tape."""
+
+    @staticmethod
+    def forward(ctx, wav, mel, eng):
+        out, tape = eng.teacher_forward_tape(wav.detach(), mel)
+        ctx.eng, ctx.tape = eng, tape
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        dwav = ctx.eng.teacher_backward_input(ctx.tape, g)
+        ctx.tape = None
+        return dwav, None, None
+
+
+class MolXentSums(torch.autograd.Function):
+    """(out_params, mean_tot, scale_tot) -> sums [2] of wn_distill_mol_xent: sum of H_bl, sum of log scale_tot."""
+
+    @staticmethod
+    def forward(ctx, out_params, mean_tot, scale_tot, eng, num_samples, noise, seed):
+        r = eng.distill_mol_xent(out_params.detach(), mean_tot.detach(), scale_tot.detach(), num_samples, noise=noise,
+                                 seed=seed)
+        ctx.save_for_backward(out_params.detach(), mean_tot.detach(), scale_tot.detach())
+        ctx.eng, ctx.S, ctx.noise, ctx.seed = eng, num_samples, noise, seed
+        return r['sums']
+
+    @staticmethod
+    def backward(ctx, g):
+        te, mean, scale = ctx.saved_tensors
+        d_te, d_m, d_s = ctx.eng.distill_mol_xent_grad(te, mean, scale, ctx.S, g, noise=ctx.noise, seed=ctx.seed)
+        return d_te, d_m, d_s, None, None, None, None
+
+
+class GaussKLSums(torch.autograd.Function):
+    """(out_params, mean_tot, scale_tot) -> sums [2] of wn_distill_gauss_kl: sum of kl_bl, sum of the squared log-scale
+    differences."""
+
+    @staticmethod
+    def forward(ctx, out_params, mean_tot, scale_tot, eng):
+        r = eng.distill_gauss_kl(out_params.detach(), mean_tot.detach(), scale_tot.detach())
+        ctx.save_for_backward(out_params.detach(), mean_tot.detach(), scale_tot.detach())
+        ctx.eng = eng
+        return r['sums']
+
+    @staticmethod
+    def backward(ctx, g):
+        te, mean, scale = ctx.saved_tensors
+        d_te, d_m, d_s = ctx.eng.distill_gauss_kl_grad(te, mean, scale, g)
+        return d_te, d_m, d_s, None
+
+
+class PowerSums(torch.autograd.Function):
+    """(pred, orig) [B,L] of equal length -> out2 [2] of wn_power_loss; differentiable in pred."""
+
+    @staticmethod
+    def forward(ctx, pred, orig):
+        pred = pred.detach()
+        ctx.save_for_backward(pred, orig)
+        return _engine.power_loss_sums(pred, orig)
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, orig = ctx.saved_tensors
+        return _engine.power_loss_grad(pred, orig, g), None
+
+
+def power_loss(pred, orig):
+    """engine.power_loss with a gradient to pred: the same trims, the same kernel and the same scalar arithmetic."""
+    dev = pred.device
+    orig = orig.to(device=dev, dtype=torch.float32) if isinstance(orig, torch.Tensor) else \
+        torch.as_tensor(orig, dtype=torch.float32, device=dev)
+    pred = pred.to(dtype=torch.float32)
+    if pred.dim() != 2 or orig.dim() != 2 or pred.shape[0] != orig.shape[0]:
+        raise ValueError('power_loss: pred and orig must be [B,L] with equal B')
+    pred = pred if pred.stride(1) == 1 else pred.contiguous()
+    orig = (orig if orig.stride(1) == 1 else orig.contiguous()).detach()
+    lp, lo = int(pred.shape[1]), int(orig.shape[1])
+    if lp > lo:
+        pred = _engine._trim(pred, lp - lo)
+    elif lo > lp:
+        orig = _engine._trim(orig, lo - lp)
+    B, L = int(pred.shape[0]), int(pred.shape[1])
+    out = PowerSums.apply(pred, orig)
+    nf = (L + _engine.STFT_HOP - 1) // _engine.STFT_HOP
+    return 0.5 * out[0] / (B * nf * _engine.STFT_BINS) + 0.5 * out[1] / (B * nf * _engine.PRIORITY_FREQ)

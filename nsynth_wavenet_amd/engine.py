@@ -314,6 +314,80 @@ class Engine(object):
                                                      self._stream()))
         return {'kl_bl': kl_bl, 'sums': sums}
 
+    # ---- gradients of the distillation losses (autograd Functions in distill_autograd.py) ----
+    # Every call below takes its workspace from torch's allocator per call (no shared buffer): they also run on the autograd
+    # engine's device thread, on the stream torch makes current there.
+    def teacher_tape_bytes(self, B, T):
+        return int(self.lib.wn_teacher_tape_bytes(self._h, int(B), int(T)))
+
+    def teacher_forward_tape(self, wav, mel):
+        """teacher_forward (bit-identical out_params) that also returns the tape the input VJP reads: a uint8 device tensor
+        of teacher_tape_bytes(B, T) bytes."""
+        wav, mel = self._dev(wav), self._dev(mel)
+        if wav.dim() != 2 or mel.dim() != 3 or wav.shape[0] != mel.shape[0]:
+            raise ValueError('teacher_forward_tape: wav must be [B,T] and mel [B,F,n_mel] with equal B')
+        if int(mel.shape[2]) != self.n_mel:
+            raise ValueError('teacher_forward_tape: mel has {} channels, the model expects {}'.format(
+                int(mel.shape[2]), self.n_mel))
+        B, T, F = int(wav.shape[0]), int(wav.shape[1]), int(mel.shape[1])
+        out = torch.empty((B, T, cfg.teacher_out_width(self.hp)), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            tape = torch.empty(max(self.teacher_tape_bytes(B, T), 256), dtype=torch.uint8, device=self.device)
+            ws = torch.empty(max(int(self.lib.wn_teacher_workspace_bytes(self._h, B, F, T)), 256), dtype=torch.uint8,
+                             device=self.device)
+            self._check(self.lib.wn_teacher_forward_tape(self._h, _ptr(wav), _ptr(mel), B, F, T, _ptr(out), _ptr(tape),
+                                                         tape.numel(), _ptr(ws), ws.numel(), self._stream()))
+        return out, tape
+
+    def teacher_backward_input(self, tape, d_out_params):
+        """Input VJP of the teacher: d_out_params [B,T,out_width] -> d wav [B,T] on a tape of teacher_forward_tape."""
+        g = self._dev(d_out_params)
+        if g.dim() != 3 or (self.kind == 'teacher' and int(g.shape[2]) != cfg.teacher_out_width(self.hp)):
+            raise ValueError('teacher_backward_input: d_out_params must be [B,T,{}]'.format(cfg.teacher_out_width(self.hp)))
+        B, T = int(g.shape[0]), int(g.shape[1])
+        dwav = torch.empty((B, T), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            ws = torch.empty(max(int(self.lib.wn_teacher_backward_workspace_bytes(self._h, B, T)), 256), dtype=torch.uint8,
+                             device=self.device)
+            self._check(self.lib.wn_teacher_backward_input(self._h, _ptr(tape), tape.numel(), _ptr(g), B, T, _ptr(dwav),
+                                                           _ptr(ws), ws.numel(), self._stream()))
+        return dwav
+
+    def _fac(self, fac):
+        fac = fac.to(device=self.device, dtype=torch.float64).contiguous()
+        if fac.numel() != 2:
+            raise ValueError('fac must hold two values (d loss / d sums)')
+        return fac
+
+    def distill_mol_xent_grad(self, out_params, mean_tot, scale_tot, num_samples, fac, noise=None, seed=0):
+        """Gradient of fac[0] sums[0] + fac[1] sums[1] of distill_mol_xent (same draws) -> (d out_params, d mean_tot,
+        d scale_tot).  fac: two float64 values on the device."""
+        out_params, mean_tot, scale_tot = self._distill_args('distill_mol_xent_grad', out_params, mean_tot, scale_tot)
+        B, T, S = int(mean_tot.shape[0]), int(mean_tot.shape[1]), int(num_samples)
+        noise = self._dev(noise)
+        if noise is not None and tuple(noise.shape) != (B, S, T):
+            raise ValueError('distill_mol_xent_grad: noise must be [B, num_samples, T] = [{}, {}, {}]'.format(B, S, T))
+        fac = self._fac(fac)
+        d_te, d_m, d_s = torch.empty_like(out_params), torch.empty_like(mean_tot), torch.empty_like(scale_tot)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.wn_distill_mol_xent_grad(self._h, _ptr(out_params), int(out_params.shape[2]), _ptr(mean_tot),
+                                                          _ptr(scale_tot), B, T, S, _ptr(noise),
+                                                          ctypes.c_uint64(seed & (2 ** 64 - 1)), _ptr(fac), _ptr(d_te),
+                                                          _ptr(d_m), _ptr(d_s), self._stream()))
+        return d_te, d_m, d_s
+
+    def distill_gauss_kl_grad(self, out_params, mean_tot, scale_tot, fac):
+        """Gradient of fac[0] sums[0] + fac[1] sums[1] of distill_gauss_kl -> (d out_params, d mean_tot, d scale_tot)."""
+        out_params, mean_tot, scale_tot = self._distill_args('distill_gauss_kl_grad', out_params, mean_tot, scale_tot)
+        B, T = int(mean_tot.shape[0]), int(mean_tot.shape[1])
+        fac = self._fac(fac)
+        d_te, d_m, d_s = torch.empty_like(out_params), torch.empty_like(mean_tot), torch.empty_like(scale_tot)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.wn_distill_gauss_kl_grad(self._h, _ptr(out_params), int(out_params.shape[2]), _ptr(mean_tot),
+                                                          _ptr(scale_tot), B, T, _ptr(fac), _ptr(d_te), _ptr(d_m), _ptr(d_s),
+                                                          self._stream()))
+        return d_te, d_m, d_s
+
     def iaf_cond_hoisted(self, batch, num_frames):
         """True when iaf_generate(batch, num_frames) runs the hoisted-conditioning kernels."""
         return bool(self.lib.wn_iaf_cond_hoisted(self._h, int(batch), int(num_frames)))
@@ -569,3 +643,31 @@ def power_loss(pred, orig, device=None):
                                      ws.numel(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     nf = (L + STFT_HOP - 1) // STFT_HOP
     return 0.5 * out[0] / (B * nf * STFT_BINS) + 0.5 * out[1] / (B * nf * PRIORITY_FREQ)
+
+
+def power_loss_sums(pred, orig):
+    """wn_power_loss on two device rows [B,L] of equal length (unit inner stride): the two float64 sums of power_loss."""
+    lib = _lib.load()
+    dev = pred.device
+    B, L = int(pred.shape[0]), int(pred.shape[1])
+    out = torch.empty(2, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(int(lib.wn_power_loss_workspace_bytes(B, L)), 256), dtype=torch.uint8, device=dev)
+        _lib.check(lib.wn_power_loss(_ptr(pred), pred.stride(0), _ptr(orig), orig.stride(0), B, L, _ptr(out), _ptr(ws),
+                                     ws.numel(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return out
+
+
+def power_loss_grad(pred, orig, fac):
+    """Gradient of fac[0] out2[0] + fac[1] out2[1] of power_loss_sums(pred, orig) with respect to pred -> [B,L] float32."""
+    lib = _lib.load()
+    dev = pred.device
+    B, L = int(pred.shape[0]), int(pred.shape[1])
+    fac = fac.to(device=dev, dtype=torch.float64).contiguous()
+    d = torch.empty((B, L), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(int(lib.wn_power_loss_grad_workspace_bytes(B, L)), 256), dtype=torch.uint8, device=dev)
+        _lib.check(lib.wn_power_loss_grad(_ptr(pred), pred.stride(0), _ptr(orig), orig.stride(0), B, L, _ptr(fac), _ptr(d),
+                                          d.stride(0), _ptr(ws), ws.numel(),
+                                          ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return d

@@ -11,12 +11,36 @@ With a teacher (the mirror's `Wavenet`, passed as `teacher=` like the reference'
 take the reference's keys and return the reference's dicts, as 0-d float64 device tensors.  The teacher's full-sequence
 forward runs on the student's unclipped x (CLIP = False) and the loss kernels of csrc/wn_distill.hip score it; the
 Monte-Carlo draws are injected (`noise`, [B, num_samples, T]) or drawn on the device from `seed`.
+
+The losses are differentiable with respect to the student's 'x', 'mean_tot' and 'scale_tot' (DESIGN.md 12): when grad mode is
+on and one of them requires grad, they are composed of the autograd Functions of distill_autograd.py -- the same kernels
+for the values (the same bits), the gradient kernels and the teacher's input VJP for `backward()`.  Otherwise they take the
+plain path (no tape).  H_Ps is computed from scale_tot, so its gradient goes to scale_tot: 1 / (N scale_tot), which is the
+reference's gradient through log_scale_tot wherever scale_tot = exp(log_scale_tot).
 """
 import numpy as np
 import torch
 
 from .. import config as cfg
 from ..engine import Engine
+from .. import distill_autograd as dag
+
+
+def _req(d, k):
+    return isinstance(d.get(k), torch.Tensor) and d[k].requires_grad
+
+
+def _wants_grad(d, keys=('x', 'mean_tot', 'scale_tot')):
+    return torch.is_grad_enabled() and any(_req(d, k) for k in keys)
+
+
+def _grad_inputs(te, ff_dict):
+    """the teacher's out_params (through its tape when x requires grad) and mean_tot / scale_tot as tensors"""
+    x = ff_dict['x']
+    out_params = dag.TeacherForward.apply(x, ff_dict['mel'], te) if _req(ff_dict, 'x') else te.teacher_forward(x, ff_dict['mel'])
+    mean, scale = (v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v, np.float32), device=te.device)
+                   for v in (ff_dict['mean_tot'], ff_dict['scale_tot']))
+    return out_params, mean, scale
 
 
 class ParallelWavenet(object):
@@ -79,6 +103,13 @@ class ParallelWavenet(object):
         """parallel_wavenet.py:361-402.  ff_dict: 'mel', 'x', 'mean_tot', 'scale_tot' (and 'log_scale_tot', which is
         log(scale_tot) here: H_Ps comes from the kernel's sum of log scale_tot).  Returns kl_loss, H_Ps, H_Ps_Pt."""
         te = self._need_teacher('kl_loss_logistic')
+        if _wants_grad(ff_dict):
+            out_params, mean, scale = _grad_inputs(te, ff_dict)
+            sums = dag.MolXentSums.apply(out_params, mean, scale, te, num_samples, noise, seed)
+            n = mean.numel()
+            H_Ps = sums[1] / n + 2
+            H_Ps_Pt = sums[0] / n
+            return {'kl_loss': H_Ps_Pt - H_Ps, 'H_Ps': H_Ps, 'H_Ps_Pt': H_Ps_Pt}
         out_params = te.teacher_forward(ff_dict['x'], ff_dict['mel'])
         r = te.distill_mol_xent(out_params, ff_dict['mean_tot'], ff_dict['scale_tot'], num_samples, noise=noise, seed=seed)
         n = r['H_bl'].numel()
@@ -89,6 +120,11 @@ class ParallelWavenet(object):
     def kl_loss_gauss(self, ff_dict):
         """parallel_wavenet.py:404-429: mean closed-form KL + 4 * mean squared log-scale difference."""
         te = self._need_teacher('kl_loss_gauss')
+        if _wants_grad(ff_dict):
+            out_params, mean, scale = _grad_inputs(te, ff_dict)
+            sums = dag.GaussKLSums.apply(out_params, mean, scale, te)
+            n = mean.numel()
+            return {'kl_loss': sums[0] / n + 4.0 * (sums[1] / n)}
         out_params = te.teacher_forward(ff_dict['x'], ff_dict['mel'])
         r = te.distill_gauss_kl(out_params, ff_dict['mean_tot'], ff_dict['scale_tot'])
         n = r['kl_bl'].numel()
@@ -97,6 +133,8 @@ class ParallelWavenet(object):
     def power_loss(self, wav_dict):
         """parallel_wavenet.py:459-479: STFT-magnitude loss of 'x' against the real audio 'wav'."""
         from ..engine import power_loss
+        if _wants_grad(wav_dict, ('x',)):
+            return {'power_loss': dag.power_loss(wav_dict['x'], wav_dict['wav'])}
         return {'power_loss': power_loss(wav_dict['x'], wav_dict['wav'], device=self.engine.device)}
 
     def contrastive_loss(self, ff_dict, num_samples=100, noise=None, seed=0):
