@@ -34,7 +34,7 @@
  *   - Concurrency (SURVEY 8(b) "Threading / streams"; tests/test_gpu_threads.py drives one handle from two
  *     host threads on two streams).  After wn_finalize() the weights and every table of a handle are read-only.
  *     The WORK calls -- wn_deconv, wn_iaf_generate*, wn_iaf_range_*, wn_clip_quant, wn_ar_reset / wn_ar_step /
- *     wn_ar_generate / wn_ar_cond_vars, wn_teacher_forward / wn_teacher_log_prob, wn_distill_mol_xent /
+ *     wn_ar_generate / wn_ar_cond_vars, wn_teacher_forward / wn_teacher_log_prob / wn_teacher_log_prob_grad, wn_distill_mol_xent /
  *     wn_distill_gauss_kl -- keep all per-call state (the
  *     range-guard word, the autoregressive queues and step counter) in the caller's workspace / state buffer:
  *     any number of host threads may issue them on ONE handle at the same time, each with its own workspace
@@ -323,6 +323,26 @@ WN_API int wn_teacher_forward(wn_handle* h, const float* wav, const float* mel, 
  * implementation; 1e-3 of a bin away from every edge the class is exact (tests/test_gpu_teacher.py). */
 WN_API int wn_teacher_log_prob(wn_handle* h, const float* out_params, const float* wav, int B, int64_t T, float* log_prob,
                         void* stream);
+
+/* Gradient of wn_teacher_log_prob: with g = d_log_prob[b,t] ([B,T], the derivative of the caller's loss with
+ * respect to log_prob -- -1 / (B T) everywhere for Wavenet.calculate_loss's 'loss'), d_out_params [B,T,out_width] and, when
+ * d_wav is not NULL, d_wav [B,T] through the TARGET (the path through the network input is wn_teacher_backward_input's).
+ *   mol    r_i = exp(v_i + logsoftmax(lg)_i - log_prob) with v_i the component's log-probability;
+ *          d lg_i = g (r_i - softmax(lg)_i); d mean_i = -g r_i dx_i; d log_s_i = -g r_i dinv_i inv_s_i where the raw
+ *          log-scale is >= -7, 0 below; d wav = g sum_i r_i dx_i  (dx_i = d v_i / d x, dinv_i = d v_i / d inv_s_i)
+ *   gauss  z = (x - m) e^-ls: d m = g z e^-ls; d p = g (z^2 - 1) where p >= -7, 0 below; d wav = -g z e^-ls
+ *   ce     d logit_k = g (onehot_k - softmax_k), the label formed as in the forward
+ * on the forward's targets, class count, thresholds and form of the bin mass, with the tie conventions listed under the
+ * distillation gradients below (tf.maximum at -7 and at the 1e-12 floor, tf.where at the edge bins).
+ * d_wav is ZERO for every mu-law teacher and every ce teacher: Wavenet.encode_signal quantises the audio before the target
+ * is used, the target is piecewise constant in wav and TensorFlow propagates nothing through it.
+ * A work call like the forward: asynchronous on `stream`, no workspace, no allocation, no host synchronisation, safe from
+ * several threads on one handle; every output element has one writer (no atomics), so a repeated call is bit-identical.
+ * Overwrites its outputs.  A 256-class row is read once (it stays in registers), a 65 536-class row twice (running max /
+ * sum, then the softmax) and written once.  WN_EINVAL (message in wn_last_error): a null or student handle, B or T < 1, a
+ * null out_params / wav / d_log_prob / d_out_params, and the ce width mismatch the forward refuses. */
+WN_API int wn_teacher_log_prob_grad(wn_handle* h, const float* out_params, const float* wav, int B, int64_t T,
+                                    const float* d_log_prob, float* d_out_params, float* d_wav, void* stream);
 
 /* ---- distillation losses (ParallelWavenet.kl_loss_logistic / kl_loss_gauss / power_loss, wavenet/parallel_wavenet.py:361-479)
  * scored under a TEACHER handle on the out_params wn_teacher_forward wrote for the student's unclipped audio x.

@@ -22,7 +22,7 @@ SYMBOLS = ['wn_abi_version', 'wn_create', 'wn_set_weight', 'wn_finalize', 'wn_ia
            'wn_iaf_workspace_bytes_form', 'wn_iaf_range_status', 'wn_iaf_range_reset',
            'wn_iaf_range_status_since_reset', 'wn_clip_quant',
            'wn_ar_n_rand', 'wn_ar_state_bytes', 'wn_ar_reset', 'wn_ar_step', 'wn_ar_generate', 'wn_ar_set_graph', 'wn_ar_cond_vars', 'wn_ar_cond_vars_floats',
-           'wn_iaf_cond_hoisted', 'wn_iaf_layer_groups', 'wn_iaf_set_groups', 'wn_teacher_workspace_bytes', 'wn_teacher_forward', 'wn_teacher_log_prob', 'wn_distill_workspace_bytes', 'wn_distill_mol_xent', 'wn_distill_gauss_kl', 'wn_power_loss_workspace_bytes', 'wn_power_loss', 'wn_teacher_tape_bytes', 'wn_teacher_forward_tape', 'wn_teacher_backward_workspace_bytes', 'wn_teacher_backward_input', 'wn_distill_mol_xent_grad', 'wn_distill_gauss_kl_grad', 'wn_power_loss_grad_workspace_bytes', 'wn_power_loss_grad', 'wn_profile_begin', 'wn_profile_pause', 'wn_profile_end', 'wn_profile_parts_begin', 'wn_profile_parts_end', 'wn_profile_parts_only', 'wn_mel_frames', 'wn_mel_spectrogram', 'wn_last_error', 'wn_destroy', 'wn_crc32c']
+           'wn_iaf_cond_hoisted', 'wn_iaf_layer_groups', 'wn_iaf_set_groups', 'wn_teacher_workspace_bytes', 'wn_teacher_forward', 'wn_teacher_log_prob', 'wn_teacher_log_prob_grad', 'wn_distill_workspace_bytes', 'wn_distill_mol_xent', 'wn_distill_gauss_kl', 'wn_power_loss_workspace_bytes', 'wn_power_loss', 'wn_teacher_tape_bytes', 'wn_teacher_forward_tape', 'wn_teacher_backward_workspace_bytes', 'wn_teacher_backward_input', 'wn_distill_mol_xent_grad', 'wn_distill_gauss_kl_grad', 'wn_power_loss_grad_workspace_bytes', 'wn_power_loss_grad', 'wn_profile_begin', 'wn_profile_pause', 'wn_profile_end', 'wn_profile_parts_begin', 'wn_profile_parts_end', 'wn_profile_parts_only', 'wn_mel_frames', 'wn_mel_spectrogram', 'wn_last_error', 'wn_destroy', 'wn_crc32c']
 
 
 class WnConfig(ctypes.Structure):
@@ -95,6 +95,7 @@ def load():
     lib.wn_teacher_workspace_bytes.restype = sz
     lib.wn_teacher_forward.argtypes = [vp, vp, vp, i32, i32, i64, vp, vp, sz, vp]
     lib.wn_teacher_log_prob.argtypes = [vp, vp, vp, i32, i64, vp, vp]
+    lib.wn_teacher_log_prob_grad.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp, vp]
     lib.wn_distill_workspace_bytes.argtypes = [vp, i32, i64]
     lib.wn_distill_workspace_bytes.restype = sz
     lib.wn_distill_mol_xent.argtypes = [vp, vp, i32, vp, vp, i32, i64, i32, vp, u64, vp, vp, vp, vp, sz, vp]

@@ -613,6 +613,112 @@ __global__ __launch_bounds__(256) void tg_log_prob_kernel(const float* __restric
     }
     if (lane == 0) lp[i] = res;
 }
+
+// Gradient of tg_log_prob_kernel: g = d_log_prob[i] -> d out_params[i, :] and d wav[i], in the forward's
+// layout (one wave per sample; lane i owns mixture i / the lanes stride over the classes) on the forward's xt, Q,
+// thresholds and bin factor, so it differentiates the function the forward evaluates.  Tie conventions as in wnhip.h:
+// max(log_s, -7) passes the gradient at the tie, the 1e-12 floor passes none below it, the edge bins differentiate the
+// selected branch only.  Every output element is written by exactly one lane: no atomics.
+template <int W>
+__device__ inline void tl_load(const float* __restrict__ p, float (&v)[W]) {
+    if constexpr (W == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(p);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+        v[0] = *p;
+    }
+}
+template <int W>
+__device__ inline void tl_store(float* __restrict__ p, const float (&v)[W]) {
+    if constexpr (W == 4) {
+        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+        *p = v[0];
+    }
+}
+// d logit_k = g (onehot_k - softmax_k) of one row, W consecutive classes per lane and step (ow % W == 0).  A row of 64 W
+// classes (256 at W = 4) stays in registers and is read once; a longer one is reduced with a running max / sum per lane
+// and read a second time for the softmax: two reads and one write of the row.
+template <int W>
+__device__ inline void tl_ce_grad_row(const float* __restrict__ o, float* __restrict__ d, int ow, int label, float g, int lane) {
+    float v[W], m = -__builtin_inff(), s = 0.f;
+#pragma unroll 4
+    for (int k = lane * W; k < ow; k += 64 * W) {
+        tl_load<W>(o + k, v);
+        float mn = m, a = 0.f;
+#pragma unroll
+        for (int j = 0; j < W; ++j) mn = fmaxf(mn, v[j]);
+#pragma unroll
+        for (int j = 0; j < W; ++j) a += expf(v[j] - mn);
+        s = s * expf(m - mn) + a;
+        m = mn;
+    }
+    const float mx = tl_wave_max(m);
+    const float rinv = 1.0f / tl_wave_sum(s * expf(m - mx));     // a lane without classes holds s = 0
+    const bool once = ow <= 64 * W;                              // v still holds the lane's only classes
+#pragma unroll 4
+    for (int k = lane * W; k < ow; k += 64 * W) {
+        if (!once) tl_load<W>(o + k, v);
+#pragma unroll
+        for (int j = 0; j < W; ++j) v[j] = g * ((k + j == label ? 1.0f : 0.0f) - expf(v[j] - mx) * rinv);
+        tl_store<W>(d + k, v);
+    }
+}
+__global__ __launch_bounds__(256) void tg_log_prob_grad_kernel(const float* __restrict__ out, const float* __restrict__ wav,
+                                                               const float* __restrict__ dlp, float* __restrict__ dout,
+                                                               float* __restrict__ dwav, long long n, int ow, int loss, int Q,
+                                                               int mu, int vec) {
+    const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (i >= n) return;
+    const float* o = out + (size_t)i * ow;
+    float* d = dout + (size_t)i * ow;
+    const float x = wav[i], g = dlp[i];
+    const float xt = mu ? wn_mu_law_scaled(x) : x;
+    const float NEG = -__builtin_inff();
+    float dx_tot = 0.f;                                            // d log_prob / d xt
+    if (loss == WN_LOSS_MOL) {
+        const int M = ow / 3;
+        float v = NEG, lg = NEG, raw = 0.f, inv = 0.f, dx = 0.f, dinv = 0.f;
+        if (lane < M) {
+            lg = o[lane];
+            raw = o[2 * M + lane];
+            const float mean = o[M + lane], ls = fmaxf(raw, -7.0f);
+            inv = expf(-ls);
+            const float c = xt - mean, iq = 1.0f / (float)Q, bf = wn_mol_bin_factor(inv, iq);
+            float min_thres, max_thres;
+            wn_mol_thresholds(Q, min_thres, max_thres);
+            v = wn_mol_component_lp(xt, c, inv, iq, bf, min_thres, max_thres);
+            wn_mol_component_grad(xt, c, inv, iq, bf, min_thres, max_thres, dx, dinv);
+        }
+        const float lmax = tl_wave_max(lg);
+        const float lse = lmax + logf(tl_wave_sum(lane < M ? expf(lg - lmax) : 0.f));
+        v = lane < M ? v + (lg - lse) : NEG;
+        const float vmax = tl_wave_max(v);
+        const float res = vmax + logf(tl_wave_sum(lane < M ? expf(v - vmax) : 0.f));
+        const float r = lane < M ? expf(v - res) : 0.f;           // responsibility of the component
+        dx_tot = tl_wave_sum(r * dx);
+        if (lane < M) {
+            d[lane] = g * (r - expf(lg - lse));
+            d[M + lane] = -g * r * dx;
+            d[2 * M + lane] = raw >= -7.0f ? -g * r * dinv * inv : 0.f;
+        }
+    } else if (loss == WN_LOSS_GAUSS) {
+        const float raw = o[1], einv = expf(-fmaxf(raw, -7.0f)), z = (xt - o[0]) * einv;
+        dx_tot = -z * einv;
+        if (lane == 0) {
+            d[0] = g * z * einv;
+            d[1] = raw >= -7.0f ? g * (z * z - 1.0f) : 0.f;
+        }
+    } else {
+        int label = (mu ? (int)floorf(wn_mu_law_scaled(x) * 128.0f) : (int)floorf(x * (float)Q * 0.5f)) + Q / 2;
+        label = min(max(label, 0), Q - 1);
+        if (vec) tl_ce_grad_row<4>(o, d, ow, label, g, lane);
+        else tl_ce_grad_row<1>(o, d, ow, label, g, lane);
+    }
+    // a mu-law or class target is piecewise constant in the audio (encode_signal quantises first): zero
+    if (dwav && lane == 0) dwav[i] = (mu || loss == WN_LOSS_CE) ? 0.f : g * dx_tot;
+}
 }  // namespace
 
 size_t wn_teacher_ws_bytes(const wn_handle* h, int B, int F, long long T) { return t_layout(h, B, F, T).total; }
@@ -765,6 +871,28 @@ extern "C" int wn_teacher_log_prob(wn_handle* h, const float* out_params, const 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(tg_log_prob_kernel, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, st, out_params, wav, log_prob,
                        n, c.out_width, c.loss_type, Q, c.use_mu_law);
+    WN_HIP(h, hipGetLastError());
+    return WN_OK;
+}
+
+extern "C" int wn_teacher_log_prob_grad(wn_handle* h, const float* out_params, const float* wav, int B, int64_t T,
+                                        const float* d_log_prob, float* d_out_params, float* d_wav, void* stream) {
+    const char* fn = "wn_teacher_log_prob_grad";
+    if (!h) return wn_fail(nullptr, WN_EINVAL, "%s: null handle", fn);
+    const wn_config& c = h->cfg;
+    if (c.kind != WN_KIND_TEACHER) return wn_fail(h, WN_EINVAL, "%s: handle is not a Wavenet teacher", fn);
+    if (B < 1 || T < 1 || !out_params || !wav || !d_log_prob || !d_out_params) return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
+    const int Q = c.use_mu_law ? 256 : 65536;
+    if (c.loss_type == WN_LOSS_CE && c.out_width != Q)
+        return wn_fail(h, WN_EINVAL, "%s: %d logits for %d classes", fn, c.out_width, Q);
+    const WnWork work(h);
+    const long long n = (long long)B * T;
+    // four classes per lane and load when the rows are 16-byte aligned (any torch tensor); one otherwise
+    const int vec = c.out_width % 4 == 0 &&
+                    ((reinterpret_cast<uintptr_t>(out_params) | reinterpret_cast<uintptr_t>(d_out_params)) & 15) == 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(tg_log_prob_grad_kernel, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, st, out_params, wav,
+                       d_log_prob, d_out_params, d_wav, n, c.out_width, c.loss_type, Q, c.use_mu_law, vec);
     WN_HIP(h, hipGetLastError());
     return WN_OK;
 }

@@ -26,6 +26,24 @@ class TeacherForward(torch.autograd.Function):
         return dwav, None, None
 
 
+class TeacherLogProb(torch.autograd.Function):
+    """(out_params [B,T,out_width], wav [B,T]) -> log_probs [B,T] of a teacher Engine.  The gradient to wav is
+    the one through the TARGET (zero for mu-law and ce teachers); the one through the network input is TeacherForward's."""
+
+    @staticmethod
+    def forward(ctx, out_params, wav, eng):
+        out_params, wav = eng._dev(out_params.detach()), eng._dev(wav.detach())
+        ctx.save_for_backward(out_params, wav)
+        ctx.eng = eng
+        return eng.teacher_log_prob(out_params, wav)
+
+    @staticmethod
+    def backward(ctx, g):
+        out_params, wav = ctx.saved_tensors
+        d_out, d_wav = ctx.eng.teacher_log_prob_grad(out_params, wav, g, want_wav=ctx.needs_input_grad[1])
+        return d_out, d_wav, None
+
+
 class MolXentSums(torch.autograd.Function):
     """(out_params, mean_tot, scale_tot) -> sums [2] of wn_distill_mol_xent: sum of H_bl, sum of log scale_tot."""
 

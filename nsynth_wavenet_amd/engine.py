@@ -254,18 +254,37 @@ class Engine(object):
                                                     ws.numel(), self._stream()))
         return out
 
+    def _log_prob_args(self, what, out_params, wav):
+        out_params, wav = self._dev(out_params), self._dev(wav)
+        ow = cfg.teacher_out_width(self.hp) if self.kind == 'teacher' else None    # a student handle: the library refuses
+        if wav.dim() != 2 or out_params.dim() != 3 or tuple(out_params.shape[:2]) != tuple(wav.shape) or \
+                (ow is not None and int(out_params.shape[2]) != ow):
+            raise ValueError('{}: out_params must be [B,T,{}] and wav [B,T]'.format(what, ow))
+        return out_params, wav
+
     def teacher_log_prob(self, out_params, wav):
         """Per-sample log-likelihood of wav [B,T] under out_params [B,T,out_width] (loss_func.py:22-63,104-119,128-133 on the
         targets of Wavenet.encode_signal, wavenet.py:157-178) -> [B,T]; Wavenet.calculate_loss's 'loss' is minus its mean."""
-        out_params, wav = self._dev(out_params), self._dev(wav)
-        if wav.dim() != 2 or out_params.dim() != 3 or tuple(out_params.shape[:2]) != tuple(wav.shape) or \
-                int(out_params.shape[2]) != cfg.teacher_out_width(self.hp):
-            raise ValueError('teacher_log_prob: out_params must be [B,T,{}] and wav [B,T]'.format(cfg.teacher_out_width(self.hp)))
+        out_params, wav = self._log_prob_args('teacher_log_prob', out_params, wav)
         lp = torch.empty(tuple(wav.shape), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             self._check(self.lib.wn_teacher_log_prob(self._h, _ptr(out_params), _ptr(wav), int(wav.shape[0]), int(wav.shape[1]),
                                                      _ptr(lp), self._stream()))
         return lp
+
+    def teacher_log_prob_grad(self, out_params, wav, d_log_prob, want_wav=True):
+        """Gradient of teacher_log_prob: d_log_prob [B,T] -> (d out_params [B,T,out_width], d wav [B,T] through
+        the target, or None without want_wav).  d wav is zero for mu-law and ce teachers (the target is quantised audio)."""
+        out_params, wav = self._log_prob_args('teacher_log_prob_grad', out_params, wav)
+        g = self._dev(d_log_prob)
+        if tuple(g.shape) != tuple(wav.shape):
+            raise ValueError('teacher_log_prob_grad: d_log_prob must be [B,T] = {}, got {}'.format(tuple(wav.shape), tuple(g.shape)))
+        d_out = torch.empty_like(out_params)
+        d_wav = torch.empty_like(wav) if want_wav else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.wn_teacher_log_prob_grad(self._h, _ptr(out_params), _ptr(wav), int(wav.shape[0]),
+                                                          int(wav.shape[1]), _ptr(g), _ptr(d_out), _ptr(d_wav), self._stream()))
+        return d_out, d_wav
 
     # ---- distillation losses (teacher handle; ParallelWavenet.kl_loss_logistic / kl_loss_gauss) ----
     def _distill_args(self, what, out_params, mean_tot, scale_tot):

@@ -7,6 +7,11 @@ from .. import config as cfg
 from ..engine import Engine
 
 
+def _wants_grad(x):
+    """a torch tensor that autograd would track now"""
+    return isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled()
+
+
 class _TeacherBase(object):
     def __init__(self, hparams, device=None, engine=None):
         self.hparams = cfg.load_hparams(hparams)
@@ -59,7 +64,15 @@ class Wavenet(_TeacherBase):
             raise ValueError('data-dependent initialisation is a training-time feature')
         # 'wav' is passed through so that the reference's own call sequence (train_wavenet.py:104-108, tests/test_wavenet.py:38-42:
         # ff_dict = feed_forward(inputs); ff_dict.update(encode_signal(inputs)); calculate_loss(ff_dict)) runs unchanged
-        return {'out_params': self.engine.teacher_forward(inputs['wav'], inputs['mel']), 'wav': inputs['wav']}
+        # A 'wav' that requires grad (a student's sample scored by the frozen teacher) takes the tape forward, whose backward is
+        # the engine's input VJP: the same out_params bits, and the engine's own refusals (mu-law teachers,
+        # widths that are no multiple of 64).  'wav' goes on undetached: calculate_loss adds the gradient through the target.
+        wav = inputs['wav']
+        if _wants_grad(wav):
+            from .. import distill_autograd as dag
+            wav = wav.to(device=self.engine.device, dtype=torch.float32)
+            return {'out_params': dag.TeacherForward.apply(wav, inputs['mel'], self.engine), 'wav': wav}
+        return {'out_params': self.engine.teacher_forward(wav, inputs['mel']), 'wav': wav}
 
     def calculate_loss(self, ff_dict):
         """wavenet.py:293-316 for scoring audio under the teacher.  ff_dict holds 'out_params' (feed_forward) and the audio: the
@@ -68,7 +81,9 @@ class Wavenet(_TeacherBase):
         the class index is handed back as the centre of its bin, inv_mu_law(i), which the device's mu_law maps to the same index
         and the same real target i / 128 (the codec round trip of SURVEY K7, tests/test_ref_codec.py).
         Returns {'loss': -mean log-likelihood, 'log_probs': [B,T]}.  The mixture-of-logistics score is the float64-accurate
-        value of the bin mass, not the float32 difference of two sigmoids TensorFlow evaluates (include/wnhip.h)."""
+        value of the bin mass, not the float32 difference of two sigmoids TensorFlow evaluates (include/wnhip.h).
+        With grad mode on and an 'out_params' or audio tensor that requires grad, the result is differentiable (the same values):
+        to out_params, and to the audio through the target -- zero for mu-law and ce teachers, whose targets are quantised."""
         if 'wav' in ff_dict:
             wav = ff_dict['wav']
         elif self.use_mu_law and 'cate_targets' in ff_dict:
@@ -80,7 +95,15 @@ class Wavenet(_TeacherBase):
             wav = ff_dict['real_targets']
         else:
             raise KeyError("calculate_loss needs 'wav', or encode_signal's 'real_targets' / 'cate_targets', beside 'out_params'")
-        lp = self.engine.teacher_log_prob(ff_dict['out_params'], wav)
+        out_params = ff_dict['out_params']
+        if _wants_grad(out_params) or _wants_grad(wav):
+            # the same kernel on the same values (the same bits), with wn_teacher_log_prob_grad as its backward
+            from .. import distill_autograd as dag
+            dev = self.engine.device
+            lp = dag.TeacherLogProb.apply(torch.as_tensor(out_params).to(device=dev, dtype=torch.float32),
+                                          torch.as_tensor(wav).to(device=dev, dtype=torch.float32), self.engine)
+        else:
+            lp = self.engine.teacher_log_prob(out_params, wav)
         return {'loss': -lp.mean(), 'log_probs': lp}
 
 
