@@ -287,6 +287,9 @@ __global__ __launch_bounds__(256, 2) void tg_gemm_kernel(const TgArgs a) {
             wn_u4* ot = os + (size_t)(2 * a.tape_hoff) * a.og4_rowlen;
 #pragma unroll
             for (int e = 0; e < TG_NT; ++e) {
+                // columns >= T: the tape holds what the forward made of its pad operands (possibly NaN) and dm is 0 --
+                // a select, not the product, so dd is 0 there and the anti-causal taps of the next GEMM read zeros
+                const bool live = t0 + 16 * e + n < a.T;
                 wn_u4 sh, sl, th, tl;
 #pragma unroll
                 for (int mg = 0; mg < 2; ++mg) {
@@ -297,8 +300,8 @@ __global__ __launch_bounds__(256, 2) void tg_gemm_kernel(const TgArgs a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const float dm = ac[mb][e][r] * inv;
-                        vs[r] = dm * tg[r] * (sg[r] * (1.f - sg[r]));
-                        vt[r] = dm * sg[r] * (1.f - tg[r] * tg[r]);
+                        vs[r] = live ? dm * tg[r] * (sg[r] * (1.f - sg[r])) : 0.f;
+                        vt[r] = live ? dm * sg[r] * (1.f - tg[r] * tg[r]) : 0.f;
                     }
 #pragma unroll
                     for (int rp = 0; rp < 2; ++rp) {
