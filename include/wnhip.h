@@ -413,6 +413,40 @@ WN_API size_t wn_teacher_backward_workspace_bytes(const wn_handle* h, int B, int
 WN_API int wn_teacher_backward_input(wn_handle* h, const void* tape, size_t tape_bytes, const float* d_out_params, int B,
                                      int64_t T, float* d_wav, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- weight gradients of the teacher: the reverse pass of wn_teacher_backward_input, run once, that also
+ * returns the gradient of every variable of the residual stack and output head, and the cotangent of the conditioning.
+ * MoL and Gauss teachers without mu-law, as the input VJP; mu-law and ce teachers stay out of scope (the ce head fails
+ * out_width <= 64), and so do weight-norm configurations and shapes whose width, skip_width or gate_width / 2 is no
+ * multiple of 64: all refused with WN_EINVAL.  Work calls: asynchronous on `stream`, no allocation, no host
+ * synchronisation, no atomics -- every output element has one writer and a repeated call is bit-identical.
+ *
+ * The gradients live in ONE flat float32 buffer of wn_teacher_grad_floats(h) floats.  wn_teacher_grad_count /
+ * wn_teacher_grad_info give, in a fixed order (conv_start, skip_start, per layer dilated_conv_i, mel_cond_i, res_i, skip_i,
+ * then out1, mel_cond_out1, out2; W before biases), the TensorFlow variable name (NUL-terminated into name[name_cap]), the
+ * float offset and the TF shape (shape4[0 .. ndim-1]; [1, K, in, out] kernels, [out] biases) of gradient i. ---- */
+WN_API int wn_teacher_grad_count(const wn_handle* h);
+WN_API int wn_teacher_grad_info(const wn_handle* h, int i, char* name, size_t name_cap, int64_t* offset, int64_t* shape4,
+                                int* ndim);
+WN_API size_t wn_teacher_grad_floats(const wn_handle* h);
+/* Training tape: the tape of wn_teacher_forward_tape (the same bytes at the same offsets) followed by the input l_i of every
+ * residual layer (split-fp16 rows with their zero left pad), the conditioning as deconvolved for F mel frames, and the
+ * scaled audio row.  wn_teacher_backward_input accepts it in place of a plain tape.  This and the workspace query below
+ * return 0 for a handle the work calls refuse. */
+WN_API size_t wn_teacher_train_tape_bytes(const wn_handle* h, int B, int F, int64_t T);
+/* wn_teacher_forward (same arguments, same workspace, bit-identical out_params) that also writes the training tape. */
+WN_API int wn_teacher_forward_train_tape(wn_handle* h, const float* wav, const float* mel, int B, int F, int64_t T,
+                                         float* out_params, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes,
+                                         void* stream);
+WN_API size_t wn_teacher_backward_weights_workspace_bytes(const wn_handle* h, int B, int F, int64_t T);
+/* d_out_params [B,T,out_width] -> grads (every element overwritten; grads_floats >= wn_teacher_grad_floats), and when not
+ * NULL d_encoding [B, F frame_shift, deconv_width] (zero outside the centre crop of T columns; needs deconv_width % 64 == 0)
+ * and d_wav [B,T] -- the bits wn_teacher_backward_input returns.  The tape must be a TRAINING tape this handle wrote for
+ * the same B, F and T; a plain tape is refused.  The time reductions walk valid columns only: nothing the tape or the
+ * workspace holds at columns [T, round_up(T, 256)) reaches a result. */
+WN_API int wn_teacher_backward_weights(wn_handle* h, const void* tape, size_t tape_bytes, const float* d_out_params, int B,
+                                       int F, int64_t T, float* grads, size_t grads_floats, float* d_encoding, float* d_wav,
+                                       void* ws, size_t ws_bytes, void* stream);
+
 /* Gradient of L = fac[0] sums[0] + fac[1] sums[1] of wn_distill_mol_xent (same draws: `noise`, or Philox under `seed`):
  * d_out_params [B,T,3 mol_mix], d_mean_tot and d_scale_tot [B,T] (through x = rl scale_tot + mean_tot, and 1 / scale_tot of
  * the log scale_tot sum).  Overwrites its outputs; no workspace. */

@@ -123,12 +123,15 @@ struct TeacherGemmPack {
 struct TeacherLayerPack {
     TeacherGemmPack gate, rs;
     TeacherGemmPack gate_t, rs_t;   // input VJP (wn_teacher_backward_input): [width][3 gate], [gate/2][width + skip], zero bias
+    TeacherGemmPack cond_t;         // d enc (wn_teacher_backward_weights): mel_cond_i transposed, [deconv_width][gate]
     int dilation;
 };
 struct TeacherPack {
     TeacherGemmPack skip_start, out1, out2;
     TeacherGemmPack skip_start_t, out1_t, out2_t;   // transposes: [width][skip], [skip][skip], [skip][out_width padded to 32]
     std::vector<TeacherLayerPack> layers;
+    TeacherGemmPack cond_out1_t;    // mel_cond_out1 transposed, [deconv_width][skip]
+    bool denc_ok = false;           // vjp_ok and deconv_width a multiple of 64: cond_t / cond_out1_t are packed
     bool vjp_ok = false;            // the shape runs on the transposed GEMMs (width, skip, gate/2 multiples of 64)
     uint64_t serial = 0;            // identity of the handle in the tapes it writes (wn_teacher_forward_tape)
 };

@@ -372,6 +372,72 @@ class Engine(object):
                                                            _ptr(ws), ws.numel(), self._stream()))
         return dwav
 
+    # ---- weight gradients of the teacher (DESIGN.md 14) ----
+    def teacher_train_tape_bytes(self, B, F, T):
+        return int(self.lib.wn_teacher_train_tape_bytes(self._h, int(B), int(F), int(T)))
+
+    def teacher_grad_table(self):
+        """[(tf variable name, float offset, TF shape)] of the flat gradient buffer, in the library's fixed order."""
+        out = []
+        name = ctypes.create_string_buffer(128)
+        off, nd, shape = ctypes.c_int64(0), ctypes.c_int(0), (ctypes.c_int64 * 4)()
+        for i in range(int(self.lib.wn_teacher_grad_count(self._h))):
+            self._check(self.lib.wn_teacher_grad_info(self._h, i, name, 128, ctypes.byref(off), shape, ctypes.byref(nd)))
+            out.append((name.value.decode(), int(off.value), tuple(int(shape[k]) for k in range(nd.value))))
+        return out
+
+    def teacher_forward_train_tape(self, wav, mel):
+        """teacher_forward (bit-identical out_params) that also returns the TRAINING tape teacher_backward_weights reads: the
+        tape of teacher_forward_tape plus every layer's input, the conditioning and the scaled audio.  teacher_backward_input
+        accepts it too.  The engine remembers the tape's frame count by its address."""
+        wav, mel = self._dev(wav), self._dev(mel)
+        if wav.dim() != 2 or mel.dim() != 3 or wav.shape[0] != mel.shape[0]:
+            raise ValueError('teacher_forward_train_tape: wav must be [B,T] and mel [B,F,n_mel] with equal B')
+        if int(mel.shape[2]) != self.n_mel:
+            raise ValueError('teacher_forward_train_tape: mel has {} channels, the model expects {}'.format(
+                int(mel.shape[2]), self.n_mel))
+        B, T, F = int(wav.shape[0]), int(wav.shape[1]), int(mel.shape[1])
+        out = torch.empty((B, T, cfg.teacher_out_width(self.hp)), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            tape = torch.empty(max(self.teacher_train_tape_bytes(B, F, T), 256), dtype=torch.uint8, device=self.device)
+            ws = torch.empty(max(int(self.lib.wn_teacher_workspace_bytes(self._h, B, F, T)), 256), dtype=torch.uint8,
+                             device=self.device)
+            self._check(self.lib.wn_teacher_forward_train_tape(self._h, _ptr(wav), _ptr(mel), B, F, T, _ptr(out), _ptr(tape),
+                                                               tape.numel(), _ptr(ws), ws.numel(), self._stream()))
+        # the library identifies a tape by its address (a copy is refused), so the frame count is kept by address too
+        frames = self.__dict__.setdefault('_train_frames', {})
+        if len(frames) >= 256:
+            frames.clear()
+        frames[tape.data_ptr()] = F
+        return out, tape
+
+    def teacher_backward_weights(self, tape, d_out_params, n_frames=None, want_encoding=False, want_wav=False):
+        """One reverse pass on a tape of teacher_forward_train_tape: d_out_params [B,T,out_width] ->
+        {'grads': {tf name: device tensor in the TF shape} (views into 'flat_grads'), 'flat_grads': [n] float32,
+        'd_encoding': [B, F frame_shift, deconv_width] or None, 'd_wav': [B,T] (teacher_backward_input's bits) or None}."""
+        g = self._dev(d_out_params)
+        if g.dim() != 3 or (self.kind == 'teacher' and int(g.shape[2]) != cfg.teacher_out_width(self.hp)):
+            raise ValueError('teacher_backward_weights: d_out_params must be [B,T,{}]'.format(cfg.teacher_out_width(self.hp)))
+        F = int(n_frames if n_frames is not None else self.__dict__.get('_train_frames', {}).get(tape.data_ptr(), 0))
+        if F < 1:
+            raise ValueError('teacher_backward_weights: pass n_frames for a tape this engine object did not write')
+        B, T = int(g.shape[0]), int(g.shape[1])
+        with torch.cuda.device(self.device):
+            n = int(self.lib.wn_teacher_grad_floats(self._h))
+            flat = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
+            denc = torch.empty((B, F * self.frame_shift, int(self.hp.deconv_width)), dtype=torch.float32, device=self.device) \
+                if want_encoding else None
+            dwav = torch.empty((B, T), dtype=torch.float32, device=self.device) if want_wav else None
+            ws = torch.empty(max(int(self.lib.wn_teacher_backward_weights_workspace_bytes(self._h, B, F, T)), 256),
+                             dtype=torch.uint8, device=self.device)
+            self._check(self.lib.wn_teacher_backward_weights(self._h, _ptr(tape), tape.numel(), _ptr(g), B, F, T, _ptr(flat), n,
+                                                             _ptr(denc), _ptr(dwav), _ptr(ws), ws.numel(), self._stream()))
+            grads = {}
+            for name, off, shape in self.teacher_grad_table():
+                cnt = int(np.prod(shape))
+                grads[name] = flat[off:off + cnt].view(shape)
+        return {'grads': grads, 'flat_grads': flat[:n], 'd_encoding': denc, 'd_wav': dwav}
+
     def _fac(self, fac):
         fac = fac.to(device=self.device, dtype=torch.float64).contiguous()
         if fac.numel() != 2:

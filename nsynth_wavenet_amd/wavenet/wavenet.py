@@ -106,6 +106,25 @@ class Wavenet(_TeacherBase):
             lp = self.engine.teacher_log_prob(out_params, wav)
         return {'loss': -lp.mean(), 'log_probs': lp}
 
+    def loss_and_weight_grads(self, inputs):
+        """The loss train_wavenet.py minimises and its gradient: 'wav' [B,T] raw audio and 'mel' [B,F,80] ->
+        {'loss': -mean log p (the bits of the no-grad calculate_loss(feed_forward(.))), 'log_probs': [B,T],
+         'grads': {tf variable name: d loss / d variable, in the TF shape} for every loaded variable of the residual stack and
+         output head, 'flat_grads': the same values as one float32 vector (Engine.teacher_grad_table gives the offsets),
+         'd_encoding': d loss / d encoding [B, F frame_shift, deconv_width], the cotangent the upsampler's variables need}.
+        One training-tape forward and one reverse pass on the device.  MoL and Gauss teachers without mu-law
+        and without weight norm.  `dropout_inputs` / `dropout_all` are training-time perturbations and are NOT applied: the
+        gradient is that of the deterministic forward feed_forward evaluates."""
+        eng = self.engine
+        wav = eng._dev(inputs['wav'])
+        out, tape = eng.teacher_forward_train_tape(wav, inputs['mel'])
+        lp = eng.teacher_log_prob(out, wav)
+        d_lp = torch.full_like(lp, -1.0 / lp.numel())
+        d_out, _ = eng.teacher_log_prob_grad(out, wav, d_lp, want_wav=False)
+        res = eng.teacher_backward_weights(tape, d_out, want_encoding=True)
+        return {'loss': -lp.mean(), 'log_probs': lp, 'grads': res['grads'], 'flat_grads': res['flat_grads'],
+                'd_encoding': res['d_encoding']}
+
 
 class Fastgen(_TeacherBase):
     """Incremental teacher: `sample({'wav': [B,1], 'encoding': [B,Cd]})` is one step.
