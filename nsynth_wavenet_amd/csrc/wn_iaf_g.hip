@@ -177,21 +177,34 @@ __global__ __launch_bounds__(GK_THREADS, 1) void iaf_group_kernel(const GArgs A)
         auto time_of = [&](int i) -> int { return A.in_dec ? r + GK_DEC * (16 * (blk0 + i) + n) : 16 * (blk0 + i) + n; };
 
         // The accumulators of a layer START from its hoisted tile: requested as soon as the previous layer's epilogue
-        // arithmetic has released the registers (layer 0: here), one 16-byte load per row block.
+        // arithmetic has released the registers (layer 0: here), one 16-byte load per row block.  Only for the blocks the
+        // consumer computes (its `first`, inside the unit): the tile of any other block is requested past the end of the
+        // descriptor -- zeros, nothing moves, and every wave still issues its eight loads (the prologue's wait counts them;
+        // a branch around a load makes the compiler drain vmcnt at the join).  Those accumulators are never read.
+        constexpr int OOB = 0x40000000;
         f4 acc[GK_HN][4];
-        auto load_c = [&](const float* Cbase) {
+        auto load_c = [&](const float* Cbase, int firstblk) {
             const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(
                 (void*)(Cbase + (size_t)b * A.c_bstride), 0, A.nb_tot * 4096, 0x00020000);
 #pragma unroll
-            for (int e = 0; e < GK_HN; ++e)
+            for (int e = 0; e < GK_HN; ++e) {
+                const int vo = blk_of(e) >= firstblk && active(blk_of(e)) ? (cblk0 + blk_of(e)) * 4096 + lane * 16 : OOB;
 #pragma unroll
-                for (int mb = 0; mb < 4; ++mb)      // blocks outside the row block fall outside the descriptor: zeros
-                    acc[e][mb] = buf_ldf4(rc, (cblk0 + blk_of(e)) * 4096 + lane * 16, mb * 1024);
+                for (int mb = 0; mb < 4; ++mb) acc[e][mb] = buf_ldf4(rc, vo, mb * 1024);
+            }
         };
         // ---- prologue: l segment, first layer's image, first C tiles ----
+        // The kernel sits at the 168 registers of three waves per SIMD.  Everything the compiler can derive from the lane
+        // index alone -- the per-lane source addresses of the image DMA, the start conv's LDS offsets -- it hoists out of the
+        // task loop and keeps in registers through the layer loop, and then spills something else.  The prologue therefore
+        // works on a copy of the lane index the compiler cannot see through: a handful of integer instructions per task
+        // again, and no instantiation needs scratch.
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
         if (FIRST) {
             // l0 = start_conv(shift_right(x)) (parallel_wavenet.py:222-225), zero left of the utterance
             const f4* wq = reinterpret_cast<const f4*>(lds + GK_S_OFF);
+            const int pown = (ln >> 4) * 256 + (ln & 15) * 16;
             __syncthreads();                               // start weights staged (and the previous task's readers are done)
             const float* xb = A.x + (size_t)b * A.XR + IAF_XP;
 #pragma unroll
@@ -205,7 +218,7 @@ __global__ __launch_bounds__(GK_THREADS, 1) void iaf_group_kernel(const GArgs A)
                     wn_u4 hw, lw;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const int c = 2 * (16 * s + 8 * (k >> 1) + 2 * q + (k & 1));
+                        const int c = 2 * (16 * s + 8 * (k >> 1) + 2 * (ln >> 4) + (k & 1));
                         const f4 wa = wq[c], wb = wq[c + 1];
                         float v0 = wa[3] + wa[0] * x0 + wa[1] * x1 + wa[2] * x2;
                         float v1 = wb[3] + wb[0] * x0 + wb[1] * x1 + wb[2] * x2;
@@ -215,8 +228,8 @@ __global__ __launch_bounds__(GK_THREADS, 1) void iaf_group_kernel(const GArgs A)
                         hw[k] = a;
                         lw[k] = c2;
                     }
-                    *reinterpret_cast<wn_u4*>(lds + (i + 1) * GK_BLK_BYTES + s * 1024 + own) = hw;
-                    *reinterpret_cast<wn_u4*>(lds + GK_PLANE + (i + 1) * GK_BLK_BYTES + s * 1024 + own) = lw;
+                    *reinterpret_cast<wn_u4*>(lds + (i + 1) * GK_BLK_BYTES + s * 1024 + pown) = hw;
+                    *reinterpret_cast<wn_u4*>(lds + GK_PLANE + (i + 1) * GK_BLK_BYTES + s * 1024 + pown) = lw;
                 }
             }
         } else {
@@ -229,9 +242,9 @@ __global__ __launch_bounds__(GK_THREADS, 1) void iaf_group_kernel(const GArgs A)
                 g_dma16(src + ((size_t)(pl * 8 + g0 + q) * A.RS + col) * 4, lds_base + pl * GK_PLANE + (blk + 1) * GK_BLK_BYTES + g0 * 256);
             }
         }
-        g_dma_image(A.L[0].w, lds_base + GK_A_OFF, LC_A_WORDS, wave, lane);
-        g_dma_image(A.L[0].w + IAF_P_FLOATS, lds_base + GK_T_OFF, LC_TAIL_WORDS, wave, lane);
-        load_c(A.L[0].C);
+        g_dma_image(A.L[0].w, lds_base + GK_A_OFF, LC_A_WORDS, wave, ln);
+        g_dma_image(A.L[0].w + IAF_P_FLOATS, lds_base + GK_T_OFF, LC_TAIL_WORDS, wave, ln);
+        load_c(A.L[0].C, A.L[0].first);
         // the segment and the first image have landed (LDS-DMA the compiler does not track: an explicit wait); the eight tile
         // loads are the youngest requests of the wave and vmcnt retires in order, so they stay in flight across the barrier
         g_dma_wait_but<4 * GK_HN>();
@@ -240,7 +253,11 @@ __global__ __launch_bounds__(GK_THREADS, 1) void iaf_group_kernel(const GArgs A)
         for (int j = 0; j < A.nl; ++j) {
             const bool fin = j + 1 == A.nl;
             const int d = A.L[j].d;
-            const bool run = blk_of(GK_HN - 1) >= A.L[j].first;   // any block of this wave still needed from this layer
+            // the blocks of this wave a later layer (or the output) still needs from this layer, inside the unit: only they
+            // take part in the K loop, the epilogue and the writes (wave-uniform: scalar branches)
+            bool on[GK_HN];
+#pragma unroll
+            for (int e = 0; e < GK_HN; ++e) on[e] = blk_of(e) >= A.L[j].first && active(blk_of(e));
             // ---- the NEXT image (the next layer's fragments and tail, or the head's) is requested in front of the K loop,
             // where the vector-memory port is idle, and staged through registers: it cannot go to LDS before the last K loop
             // of this layer has read the current one, and an LDS-DMA issued at that point would put its 2-3 k cycles of
@@ -261,26 +278,30 @@ __global__ __launch_bounds__(GK_THREADS, 1) void iaf_group_kernel(const GArgs A)
                 n_tail = (HC_TAIL_WORDS + 3) / 4;
                 d_tail = GK_A_OFF + HC_A_WORDS * 4;
             }
+            int tid = (int)threadIdx.x;                    // opaque for the same reason as `ln`: the ten staging offsets are
+            asm volatile("" : "+v"(tid));                  // recomputed per layer instead of living in registers all along
             wn_u4 st[GK_ST], stt = {0u, 0u, 0u, 0u};
 #pragma unroll
             for (int i = 0; i < GK_ST; ++i) {
-                const int idx = i * GK_THREADS + (int)threadIdx.x;
+                const int idx = i * GK_THREADS + tid;
                 st[i] = (wn_u4){0u, 0u, 0u, 0u};
                 if (idx < n_img) st[i] = *reinterpret_cast<const wn_u4*>(s_img + (size_t)idx * 4);
             }
-            if ((int)threadIdx.x < n_tail) stt = *reinterpret_cast<const wn_u4*>(s_tail + (size_t)threadIdx.x * 4);
+            if (tid < n_tail) stt = *reinterpret_cast<const wn_u4*>(s_tail + (size_t)tid * 4);
 
             // ---- K loop: dilated conv of this wave's blocks on top of the hoisted tile ----
-            if (run) {
-                // B operands: column 16 i + n - shift of the layer input, one 16-byte LDS word per (tap, half, plane)
+            // B operands: column 16 i + n - shift of the layer input, one 16-byte LDS word per (tap, half, plane)
+            auto b_addr = [&](int i, int tap) {
+                const int c = 16 * i + n - (2 - tap) * d;
+                return (max(c >> 4, -1) + 1) * GK_BLK_BYTES + q * 256 + (c & 15) * 16;
+            };
+            if (on[0] && on[1]) {
+                // both blocks: they share every fragment read
                 int ba[GK_HN][3];
 #pragma unroll
                 for (int e = 0; e < GK_HN; ++e)
 #pragma unroll
-                    for (int tap = 0; tap < 3; ++tap) {
-                        const int c = 16 * blk_of(e) + n - (2 - tap) * d;
-                        ba[e][tap] = (max(c >> 4, -1) + 1) * GK_BLK_BYTES + q * 256 + (c & 15) * 16;
-                    }
+                    for (int tap = 0; tap < 3; ++tap) ba[e][tap] = b_addr(blk_of(e), tap);
 #pragma unroll
                 for (int ks = 0; ks < 6; ++ks) {
                     wn_u4 a[4][2];
@@ -297,10 +318,25 @@ __global__ __launch_bounds__(GK_THREADS, 1) void iaf_group_kernel(const GArgs A)
                         for (int mb = 0; mb < 4; ++mb) acc[e][mb] = mfma3(a[mb][0], a[mb][1], bh, bl, acc[e][mb]);
                     }
                 }
-            }
-            bool on[GK_HN];
+            } else if (on[0] || on[1]) {
+                // one block (the other lies in the halo a later layer no longer reads, or outside the unit): the same
+                // products in the same order for it, nothing for the other
+                auto k_one = [&](int i, f4 (&ac)[4]) {
+                    int ba[3];
 #pragma unroll
-            for (int e = 0; e < GK_HN; ++e) on[e] = blk_of(e) >= A.L[j].first && active(blk_of(e));
+                    for (int tap = 0; tap < 3; ++tap) ba[tap] = b_addr(i, tap);
+#pragma unroll
+                    for (int ks = 0; ks < 6; ++ks) {
+                        const wn_u4 bh = *reinterpret_cast<const wn_u4*>(lds + ba[ks >> 1] + (ks & 1) * 1024);
+                        const wn_u4 bl = *reinterpret_cast<const wn_u4*>(lds + GK_PLANE + ba[ks >> 1] + (ks & 1) * 1024);
+#pragma unroll
+                        for (int mb = 0; mb < 4; ++mb)
+                            ac[mb] = mfma3(Pl[((ks * 4 + mb) * 2 + 0) * 64], Pl[((ks * 4 + mb) * 2 + 1) * 64], bh, bl, ac[mb]);
+                    }
+                };
+                if (on[0]) k_one(blk_of(0), acc[0]);
+                else k_one(blk_of(1), acc[1]);
+            }
             wn_u4 oh[GK_HN][2], ol[GK_HN][2];
             // Epilogue arithmetic of the wave's blocks.  Nothing is written in place here -- other waves' K loops may still
             // read this layer's input -- the outputs wait in registers.  The accumulators are free afterwards: the next
@@ -320,8 +356,8 @@ __global__ __launch_bounds__(GK_THREADS, 1) void iaf_group_kernel(const GArgs A)
                     }
                     pair_epilogue(W, acc[e], lh, ll, oh[e], ol[e], amax);
                 }
-                if (!fin) load_c(A.L[j + 1].C);
-                else if (LAST) load_c(A.Ch);
+                if (!fin) load_c(A.L[j + 1].C, A.L[j + 1].first);
+                else if (LAST) load_c(A.Ch, A.hb);         // the head runs on the output blocks only
             };
             // The waves of a SIMD get the matrix pipe in the order of their age, so a wave that runs its epilogue arithmetic
             // STRAIGHT behind its own K loop -- no barrier in between -- does it in the shadow of the younger waves' MFMAs
@@ -366,11 +402,11 @@ __global__ __launch_bounds__(GK_THREADS, 1) void iaf_group_kernel(const GArgs A)
             // ... the staged fragments (only K loops read that buffer: all done) ...
 #pragma unroll
             for (int i = 0; i < GK_ST; ++i) {
-                const int idx = i * GK_THREADS + (int)threadIdx.x;
+                const int idx = i * GK_THREADS + tid;
                 if (idx < n_img) *reinterpret_cast<wn_u4*>(lds + GK_A_OFF + idx * 16) = st[i];
             }
             // ... and the staged tail
-            if ((int)threadIdx.x < n_tail) *reinterpret_cast<wn_u4*>(lds + d_tail + threadIdx.x * 16) = stt;
+            if (tid < n_tail) *reinterpret_cast<wn_u4*>(lds + d_tail + tid * 16) = stt;
             __syncthreads();                               // layer output and next image in LDS
         }
 
