@@ -447,6 +447,31 @@ WN_API int wn_teacher_backward_weights(wn_handle* h, const void* tape, size_t ta
                                        int F, int64_t T, float* grads, size_t grads_floats, float* d_encoding, float* d_wav,
                                        void* ws, size_t ws_bytes, void* stream);
 
+/* ---- reverse pass of the upsampler: the gradients of trans_conv_j/kernel and trans_conv_j/bias of the deconv
+ * stack `scope` ("" for a teacher; "iaf_share", "iaf_1" ... for a student, as in wn_deconv) from mel [B,F,n_mel] and a
+ * cotangent d_enc [B, F frame_shift, deconv_width] of wn_deconv's output, e.g. d_encoding of wn_teacher_backward_weights.
+ * A separate call: it reruns the stack's forward into its own workspace and neither reads nor changes a teacher tape; the
+ * wn_teacher_grad_* table is not affected.  Split-fp16 arithmetic whatever the handle's precision; the cotangent enters
+ * scaled by the power of two that brings its largest magnitude to [1, 2), so a cotangent scaled by 2^k gives the same
+ * gradients scaled bit for bit.  No atomics, one writer per element: a repeated call is bit-identical.  A work call:
+ * asynchronous on `stream`, no allocation, no host synchronisation.
+ * Refused with WN_EINVAL (message in wn_last_error): use_resize_conv, use_weight_norm, a deconv_width that is no multiple of
+ * 64, a layer without split-fp16 pack, a stride above 30, an unknown scope, grads_floats or ws_bytes too small.  The count
+ * and size queries return 0 for what the work call refuses.  A handle that is not finalized: WN_ESTATE, as wn_deconv.
+ * Cost for every handle, trained or not: wn_finalize packs a transposed split-fp16 copy of the kernel of every deconv
+ * layer but the first of a stack (K Cin Cout 4 bytes: 21 MB for the shipped 80 x 256 x 256 layer, once per stack) at the end
+ * of the handle's device blob; no existing offset moves.
+ * Table, per layer j = 1 .. in order: "<scope/>trans_conv_j/kernel" [1, K, Cout, Cin], then "<scope/>trans_conv_j/bias"
+ * [Cout]; name / offset / shape as in wn_teacher_grad_info. ---- */
+WN_API int wn_deconv_grad_count(const wn_handle* h, const char* scope);
+WN_API int wn_deconv_grad_info(const wn_handle* h, const char* scope, int i, char* name, size_t name_cap, int64_t* offset,
+                               int64_t* shape4, int* ndim);
+WN_API size_t wn_deconv_grad_floats(const wn_handle* h, const char* scope);
+WN_API size_t wn_deconv_backward_workspace_bytes(const wn_handle* h, const char* scope, int B, int F);
+/* grads: every element of the first wn_deconv_grad_floats floats is overwritten.  d mel is not computed. */
+WN_API int wn_deconv_backward(wn_handle* h, const char* scope, const float* mel, const float* d_enc, int B, int F, float* grads,
+                              size_t grads_floats, void* ws, size_t ws_bytes, void* stream);
+
 /* Gradient of L = fac[0] sums[0] + fac[1] sums[1] of wn_distill_mol_xent (same draws: `noise`, or Philox under `seed`):
  * d_out_params [B,T,3 mol_mix], d_mean_tot and d_scale_tot [B,T] (through x = rl scale_tot + mean_tot, and 1 / scale_tot of
  * the log scale_tot sum).  Overwrites its outputs; no workspace. */

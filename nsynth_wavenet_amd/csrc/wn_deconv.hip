@@ -924,6 +924,19 @@ size_t wn_deconv_scratch_bytes(const wn_handle* h, int B, int F) {
     return align_up(fl * sizeof(float), 256);
 }
 
+const void* wn_deconv_hidden(const wn_handle* h, int B, int F, int j, const void* scratch, int64_t* ys, int* yoff) {
+    const wn_config& c = h->cfg;
+    const float* at = reinterpret_cast<const float*>(scratch) + (size_t)B * c.n_mel * dc_row_stride(F);
+    int L = F;
+    for (int i = 0; i < j; ++i) {
+        L *= c.deconv_stride[i];
+        at += (size_t)B * c.deconv_width * dc_row_stride(L);
+    }
+    *ys = dc_row_stride(L * c.deconv_stride[j]);
+    *yoff = DC_XOFF;
+    return at;
+}
+
 int wn_run_deconv(wn_handle* h, int si, const float* mel, int B, int F, float* enc_cm,
                   int64_t enc_stride, void* scratch, hipStream_t st, bool split_out, unsigned* status, int prec) {
     const wn_config& c = h->cfg;

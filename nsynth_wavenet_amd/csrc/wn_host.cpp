@@ -284,6 +284,8 @@ extern "C" int wn_finalize(wn_handle* h) {
         rc = wn_pack_teacher(h, blob);
         if (rc) return rc;
     }
+    rc = wn_pack_deconv_bwd(h, blob);   // last: the packs above keep their offsets
+    if (rc) return rc;
     WN_HIP(h, hipSetDevice(h->device));
     h->blob_floats = blob.size();
     WN_HIP(h, hipMalloc((void**)&h->d_blob, blob.size() * sizeof(float)));

@@ -41,6 +41,10 @@ struct DeconvLayerPack {
     // {float offset of the row block's first K-group inside w_off's pack, (phase << 8) | input column shift d}; 0 = not available
     size_t tab_f_off = 0;
     int tab_f_R = 0;
+    // reverse pass (wn_deconv_bwd.hip): W^T as two planes of halves [k][cin][cout], prescaled by 1 / wt_inv_scale; 0 = not
+    // available (the first layer of a stack needs none)
+    size_t wt_off = 0;
+    float wt_inv_scale = 1.f;
 };
 
 struct DeconvStackPack {
@@ -261,6 +265,11 @@ size_t wn_deconv_scratch_bytes(const wn_handle* h, int B, int F);
 int wn_run_deconv(wn_handle* h, int si, const float* mel, int B, int F,
                   float* enc_cm, int64_t enc_stride, void* scratch, hipStream_t st, bool split_out = false,
                   unsigned* status = nullptr, int prec = -1);
+
+// the G4 rows wn_run_deconv (split-fp16 run) left in `scratch` for hidden layer j: row stride in 16-byte words and the column
+// of sample 0
+const void* wn_deconv_hidden(const wn_handle* h, int B, int F, int j, const void* scratch, int64_t* ys, int* yoff);
+int wn_pack_deconv_bwd(wn_handle* h, std::vector<float>& blob);   // after every other pack (wn_deconv_bwd.hip)
 
 int wn_pack_iaf_h(wn_handle* h, std::vector<float>& blob);
 // ---- generic-width student (wn_iaf_x.hip) ----

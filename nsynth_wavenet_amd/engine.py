@@ -438,6 +438,45 @@ class Engine(object):
                 grads[name] = flat[off:off + cnt].view(shape)
         return {'grads': grads, 'flat_grads': flat[:n], 'd_encoding': denc, 'd_wav': dwav}
 
+    # ---- reverse pass of the upsampler (DESIGN.md 15) ----
+    def deconv_grad_table(self, scope=''):
+        """[(tf variable name, float offset, TF shape)] of deconv_backward's flat gradient buffer: per layer
+        '<scope/>trans_conv_j/kernel' [1,K,Cout,Cin], then '<scope/>trans_conv_j/bias' [Cout].  Empty for a stack the call
+        refuses."""
+        sc = scope.encode()
+        out = []
+        name = ctypes.create_string_buffer(160)
+        off, nd, shape = ctypes.c_int64(0), ctypes.c_int(0), (ctypes.c_int64 * 4)()
+        for i in range(int(self.lib.wn_deconv_grad_count(self._h, sc))):
+            self._check(self.lib.wn_deconv_grad_info(self._h, sc, i, name, 160, ctypes.byref(off), shape, ctypes.byref(nd)))
+            out.append((name.value.decode(), int(off.value), tuple(int(shape[k]) for k in range(nd.value))))
+        return out
+
+    def deconv_backward(self, mel, d_encoding, scope=''):
+        """VJP of deconv(mel, scope) with respect to the stack's variables: mel [B,F,n_mel] and a cotangent d_encoding
+        [B, F frame_shift, deconv_width] -> {'grads': {tf name: device tensor in the TF shape} (views into 'flat_grads'),
+        'flat_grads': [n] float32}.  Reruns the stack's forward; no tape."""
+        mel, g = self._dev(mel), self._dev(d_encoding)
+        if mel.dim() != 3 or int(mel.shape[2]) != self.n_mel:
+            raise ValueError('deconv_backward: mel must be [B,F,{}]'.format(self.n_mel))
+        B, F = int(mel.shape[0]), int(mel.shape[1])
+        want = (B, F * self.frame_shift, int(self.hp.deconv_width))
+        if tuple(g.shape) != want:
+            raise ValueError('deconv_backward: d_encoding must be [B, F frame_shift, deconv_width] = {}, got {}'.format(
+                list(want), list(g.shape)))
+        sc = scope.encode()
+        with torch.cuda.device(self.device):
+            n = int(self.lib.wn_deconv_grad_floats(self._h, sc))
+            flat = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
+            ws = torch.empty(max(int(self.lib.wn_deconv_backward_workspace_bytes(self._h, sc, B, F)), 256), dtype=torch.uint8,
+                             device=self.device)
+            self._check(self.lib.wn_deconv_backward(self._h, sc, _ptr(mel), _ptr(g), B, F, _ptr(flat), n, _ptr(ws), ws.numel(),
+                                                    self._stream()))
+            grads = {}
+            for name, off, shape in self.deconv_grad_table(scope):
+                grads[name] = flat[off:off + int(np.prod(shape))].view(shape)
+        return {'grads': grads, 'flat_grads': flat[:n]}
+
     def _fac(self, fac):
         fac = fac.to(device=self.device, dtype=torch.float64).contiguous()
         if fac.numel() != 2:

@@ -106,7 +106,7 @@ class Wavenet(_TeacherBase):
             lp = self.engine.teacher_log_prob(out_params, wav)
         return {'loss': -lp.mean(), 'log_probs': lp}
 
-    def loss_and_weight_grads(self, inputs):
+    def loss_and_weight_grads(self, inputs, upsampler=False):
         """The loss train_wavenet.py minimises and its gradient: 'wav' [B,T] raw audio and 'mel' [B,F,80] ->
         {'loss': -mean log p (the bits of the no-grad calculate_loss(feed_forward(.))), 'log_probs': [B,T],
          'grads': {tf variable name: d loss / d variable, in the TF shape} for every loaded variable of the residual stack and
@@ -114,7 +114,10 @@ class Wavenet(_TeacherBase):
          'd_encoding': d loss / d encoding [B, F frame_shift, deconv_width], the cotangent the upsampler's variables need}.
         One training-tape forward and one reverse pass on the device.  MoL and Gauss teachers without mu-law
         and without weight norm.  `dropout_inputs` / `dropout_all` are training-time perturbations and are NOT applied: the
-        gradient is that of the deterministic forward feed_forward evaluates."""
+        gradient is that of the deterministic forward feed_forward evaluates.
+        upsampler=True: 'grads' also holds trans_conv_j/kernel and trans_conv_j/bias, from one Engine.deconv_backward on this
+        call's own d_encoding, and 'flat_upsampler_grads' is that call's flat vector
+        (Engine.deconv_grad_table gives the offsets).  Everything else is the bits of the default call."""
         eng = self.engine
         wav = eng._dev(inputs['wav'])
         out, tape = eng.teacher_forward_train_tape(wav, inputs['mel'])
@@ -122,8 +125,14 @@ class Wavenet(_TeacherBase):
         d_lp = torch.full_like(lp, -1.0 / lp.numel())
         d_out, _ = eng.teacher_log_prob_grad(out, wav, d_lp, want_wav=False)
         res = eng.teacher_backward_weights(tape, d_out, want_encoding=True)
-        return {'loss': -lp.mean(), 'log_probs': lp, 'grads': res['grads'], 'flat_grads': res['flat_grads'],
-                'd_encoding': res['d_encoding']}
+        ret = {'loss': -lp.mean(), 'log_probs': lp, 'grads': res['grads'], 'flat_grads': res['flat_grads'],
+               'd_encoding': res['d_encoding']}
+        if upsampler:
+            up = eng.deconv_backward(inputs['mel'], res['d_encoding'])
+            ret['grads'] = dict(res['grads'])
+            ret['grads'].update(up['grads'])
+            ret['flat_upsampler_grads'] = up['flat_grads']
+        return ret
 
 
 class Fastgen(_TeacherBase):
