@@ -19,7 +19,8 @@
 #include <algorithm>
 
 #include "wn_internal.h"
-#include "wn_codec.h"
+#include "wn_g4.h"
+#include "wn_mfma_h.h"
 #include "wn_pack_h.h"
 
 namespace {
@@ -31,7 +32,6 @@ constexpr int DB_CT = 32;             // channels per de-interleave tile (one 32
 constexpr int DB_MAXS = 30;           // largest stride: S * DB_FT * (DB_CT + 1) words of LDS
 constexpr int DB_LP = 32;             // frames per batch row are padded to a multiple of the 32-wide K-step
 constexpr int DB_SLAB = 4096;         // columns (batch x padded frames) per partial sum of a weight-gradient GEMM
-constexpr int DB_NPART = 1024;        // blocks of the absmax reduction
 constexpr int DB_WGS = 1024;          // workgroups the data-gradient GEMM aims at (four per CU)
 
 struct LayerDims {
@@ -82,7 +82,7 @@ BwdLayout bwd_layout(const wn_handle* h, const DeconvStackPack& sp, int B, int F
     size_t p = 0;
     auto take = [&](size_t bytes) { const size_t at = p; p += align_up(std::max<size_t>(bytes, 16), 256); return at; };
     o.scal = take(sp.layers.size() * 4 * sizeof(float));
-    o.part_amax = take(DB_NPART * sizeof(float));
+    o.part_amax = take(WN_NPART * sizeof(float));
     o.enc = take((size_t)B * h->cfg.deconv_width * (size_t)L * sizeof(float));
     o.fwd = take(wn_deconv_scratch_bytes(h, B, F));
     o.dzc = take(dzc);
@@ -92,39 +92,6 @@ BwdLayout bwd_layout(const wn_handle* h, const DeconvStackPack& sp, int B, int F
     o.part = take(part);
     o.total = p;
     return o;
-}
-
-// ---- scale of a cotangent: the power of two that brings its largest magnitude to [1, 2) ----
-__device__ inline float db_wave_max(float m) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    return m;
-}
-__global__ __launch_bounds__(256) void db_absmax_kernel(const float* __restrict__ x, long long n, float* __restrict__ part) {
-    __shared__ float sh[4];
-    float m = 0.f;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) m = fmaxf(m, fabsf(x[i]));
-    m = db_wave_max(m);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-}
-// scal[0] = 2^k applied to this layer's cotangent, scal[1] = what undoes every scale applied so far (prev: the layer above's)
-__global__ __launch_bounds__(256) void db_scale_kernel(const float* __restrict__ part, int np, float* __restrict__ scal,
-                                                       const float* __restrict__ prev) {
-    __shared__ float sh[4];
-    float m = 0.f;
-    for (int i = threadIdx.x; i < np; i += 256) m = fmaxf(m, part[i]);
-    m = db_wave_max(m);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-        int k = 0;
-        if (m > 0.f && m < __builtin_inff()) k = min(max(-ilogbf(m), -100), 100);
-        scal[0] = ldexpf(1.f, k);
-        scal[1] = (prev ? prev[1] : 1.f) * ldexpf(1.f, -k);
-    }
 }
 
 // ---- shifted split-fp16 images of a layer's input: xs[plane][s][ci][b Lp + f] = x[ci][f + s - (taps - 1)] ----
@@ -147,8 +114,8 @@ __global__ __launch_bounds__(256) void db_xs_kernel(const void* __restrict__ src
     if (ci < cin) {
         if (G4) {
             const unsigned* y = reinterpret_cast<const unsigned*>(src) + (size_t)b * C_src * ys;
-            const int cc = ci & 31;
-            const int g = (ci >> 5) * 4 + ((cc & 15) >> 2), slot = ((cc >> 4) << 1) | ((cc >> 1) & 1), sh = 16 * (cc & 1);
+            int g, slot, sh;
+            wn_g4_slot(ci, g, slot, sh);
             const size_t lo_plane = (size_t)(C_src / 8) * ys * 4;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
@@ -216,7 +183,8 @@ __global__ __launch_bounds__(256) void db_deint_kernel(const float* __restrict__
         float y0 = 0.f, y1 = 0.f;
         if (t < T) {
             const unsigned* y = yv + (size_t)b * C * ys;
-            const int gq = (c0 >> 5) * 4 + ((cc & 15) >> 2), slot = ((cc >> 4) << 1) | ((cc >> 1) & 1);
+            int gq, slot, sh;                                       // sh = 0: cc is even
+            wn_g4_slot(c0 + cc, gq, slot, sh);
             const size_t at = ((size_t)gq * ys + yoff + t) * 4 + slot;
             wn_join_pair(y[at], y[at + (size_t)(C / 8) * ys * 4], y0, y1);
         }
@@ -259,9 +227,6 @@ __global__ __launch_bounds__(256) void db_deint_kernel(const float* __restrict__
 // ---- the shared GEMM body: a wave owns 32 x 32 of the workgroup's 64 x 64 tile (2 x 2 MFMA blocks) ----
 // a / b: this lane's row of the first block of each operand at the lane's k offset (8 halves = one 16-byte load);
 // a16 / b16: halves between the two blocks' rows (16 rows); alo / blo: halves from the hi plane to the lo plane.
-__device__ inline f4 db_mfma(wn_u4 a, wn_u4 b, f4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(wn_h8, a), __builtin_bit_cast(wn_h8, b), c, 0, 0, 0);
-}
 __device__ inline void nt_tile_steps(const hf* __restrict__ a, size_t a16, size_t alo, const hf* __restrict__ b, size_t b16,
                                      size_t blo, int nks, f4 (&acc)[2][2]) {
     // operands one K-step ahead of the MFMAs that consume them
@@ -286,9 +251,9 @@ __device__ inline void nt_tile_steps(const hf* __restrict__ a, size_t a16, size_
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 f4 c = acc[i][j];
-                c = db_mfma(ah[i], bh[j], c);
-                c = db_mfma(ah[i], bl[j], c);
-                c = db_mfma(al[i], bh[j], c);
+                c = mfma_h(ah[i], bh[j], c);
+                c = mfma_h(ah[i], bl[j], c);
+                c = mfma_h(al[i], bh[j], c);
                 acc[i][j] = c;
             }
     }
@@ -430,28 +395,19 @@ int bwd_check(const wn_handle* h, const char* fn, const char* scope, int* si, bo
 #undef DB_REFUSE
 }
 
-struct DGradEntry {
-    std::string name;
-    size_t off;
-    int64_t shape[4];
-    int ndim;
-};
-std::vector<DGradEntry> dgrad_table(const wn_handle* h, int si) {
-    std::vector<DGradEntry> t;
+std::vector<WnGradEntry> dgrad_table(const wn_handle* h, int si) {
+    std::vector<WnGradEntry> t;
     const DeconvStackPack& sp = h->stacks[si];
     size_t off = 0;
     for (size_t j = 0; j < sp.layers.size(); ++j) {
         const DeconvLayerPack& lp = sp.layers[j];
         const std::string base = (sp.prefix.empty() ? std::string() : sp.prefix + "/") + "trans_conv_" + std::to_string(j + 1);
-        t.push_back(DGradEntry{base + "/kernel", off, {1, lp.K, lp.cout, lp.cin}, 4});
+        t.push_back(WnGradEntry{base + "/kernel", off, {1, lp.K, lp.cout, lp.cin}, 4});
         off += (size_t)lp.K * lp.cout * lp.cin;
-        t.push_back(DGradEntry{base + "/bias", off, {lp.cout, 0, 0, 0}, 1});
+        t.push_back(WnGradEntry{base + "/bias", off, {lp.cout, 0, 0, 0}, 1});
         off += (size_t)lp.cout;
     }
     return t;
-}
-size_t dgrad_floats(const std::vector<DGradEntry>& t) {
-    return t.empty() ? 0 : t.back().off + (size_t)t.back().shape[0];
 }
 }  // namespace
 
@@ -496,20 +452,13 @@ extern "C" int wn_deconv_grad_info(const wn_handle* h, const char* scope, int i,
                                    int64_t* shape4, int* ndim) {
     int si;
     if (int rc = bwd_check(h, "wn_deconv_grad_info", scope, &si, false)) return rc;
-    const std::vector<DGradEntry> t = dgrad_table(h, si);
-    if (i < 0 || i >= (int)t.size() || !name || !offset || !shape4 || !ndim || name_cap <= t[i].name.size())
-        return wn_fail(h, WN_EINVAL, "wn_deconv_grad_info: bad argument (index %d of %zu)", i, t.size());
-    memcpy(name, t[i].name.c_str(), t[i].name.size() + 1);
-    *offset = (int64_t)t[i].off;
-    for (int k = 0; k < 4; ++k) shape4[k] = t[i].shape[k];
-    *ndim = t[i].ndim;
-    return WN_OK;
+    return wn_grad_info(h, "wn_deconv_grad_info", dgrad_table(h, si), i, name, name_cap, offset, shape4, ndim);
 }
 
 extern "C" size_t wn_deconv_grad_floats(const wn_handle* h, const char* scope) {
     int si;
     if (bwd_check(h, "wn_deconv_grad_floats", scope, &si, true)) return 0;
-    return dgrad_floats(dgrad_table(h, si));
+    return wn_grad_floats(dgrad_table(h, si));
 }
 
 extern "C" size_t wn_deconv_backward_workspace_bytes(const wn_handle* h, const char* scope, int B, int F) {
@@ -526,9 +475,9 @@ extern "C" int wn_deconv_backward(wn_handle* h, const char* scope, const float* 
     if (!mel || !d_enc || !grads || !ws || B < 1 || F < 1) return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
     if (B > 65535) return wn_fail(h, WN_EINVAL, "%s: B = %d above 65535", fn, B);
     const DeconvStackPack& sp = h->stacks[si];
-    const std::vector<DGradEntry> tab = dgrad_table(h, si);
-    if (grads_floats < dgrad_floats(tab))
-        return wn_fail(h, WN_EINVAL, "%s: grads holds %zu floats, the gradients need %zu", fn, grads_floats, dgrad_floats(tab));
+    const std::vector<WnGradEntry> tab = dgrad_table(h, si);
+    if (grads_floats < wn_grad_floats(tab))
+        return wn_fail(h, WN_EINVAL, "%s: grads holds %zu floats, the gradients need %zu", fn, grads_floats, wn_grad_floats(tab));
     const BwdLayout BL = bwd_layout(h, sp, B, F);
     if (ws_bytes < BL.total) return wn_fail(h, WN_EINVAL, "%s: workspace %zu < %zu bytes", fn, ws_bytes, BL.total);
     const int nl = (int)sp.layers.size();
@@ -568,10 +517,8 @@ extern "C" int wn_deconv_backward(wn_handle* h, const char* scope, const float* 
         const DeconvLayerPack& lp = sp.layers[j];
         const LayerDims d = layer_dims(lp, B, Lin[j]);
         float* sj = scal + 4 * j;
-        const long long ng = (long long)B * d.S * d.L * d.C;
-        const int nb = (int)std::min<long long>(DB_NPART, (ng + 255) / 256);
-        hipLaunchKernelGGL(db_absmax_kernel, dim3(nb), dim3(256), 0, st, g, ng, pamax);
-        hipLaunchKernelGGL(db_scale_kernel, dim3(1), dim3(256), 0, st, pamax, nb, sj, j + 1 < nl ? sj + 4 : (const float*)nullptr);
+        // scal[0] = 2^k applied to this layer's cotangent, scal[1] = what undoes every scale applied so far (the layer above's)
+        wn_pow2_scale(g, (long long)B * d.S * d.L * d.C, pamax, sj, j + 1 < nl ? sj + 4 : nullptr, st);
         // shifted images of the layer's input
         {
             const long long items = (long long)d.nsh * d.cinp * (d.N / 8);

@@ -19,6 +19,17 @@ int wn_fail(const wn_handle*, int code, const char* fmt, ...) {
     return code;
 }
 
+int wn_grad_info(const wn_handle* h, const char* fn, const std::vector<WnGradEntry>& t, int i, char* name, size_t name_cap,
+                 int64_t* offset, int64_t* shape4, int* ndim) {
+    if (i < 0 || i >= (int)t.size() || !name || !offset || !shape4 || !ndim || name_cap <= t[i].name.size())
+        return wn_fail(h, WN_EINVAL, "%s: bad argument (index %d of %zu)", fn, i, t.size());
+    memcpy(name, t[i].name.c_str(), t[i].name.size() + 1);
+    *offset = (int64_t)t[i].off;
+    for (int k = 0; k < 4; ++k) shape4[k] = t[i].shape[k];
+    *ndim = t[i].ndim;
+    return WN_OK;
+}
+
 static void expect(wn_handle* h, const std::string& name, std::vector<int64_t> shape) {
     HostTensor t;
     t.shape = std::move(shape);

@@ -117,7 +117,7 @@ struct ArPack {
     size_t ring_floats;        // per batch element
 };
 
-// Full-sequence teacher forward (wn_teacher.hip): split-fp16 A fragments in 64-row tiles
+// Full-sequence teacher forward and reverse pass (wn_teacher.hip, wn_teacher_bwd.hip, wn_teacher_wgrad.hip): split-fp16 A fragments in 64-row tiles
 struct TeacherGemmPack {
     size_t w_off = 0;      // [m-tile][K-step][4 row blocks][plane][lane][4] words
     size_t b_off = 0;      // [m-tile][64] bias, tile-local row order
@@ -218,6 +218,19 @@ struct WnWork {
             return wn_fail((h), WN_EIO, "%s failed: %s (%s:%d)", #expr,              \
                            hipGetErrorString(e__), __FILE__, __LINE__);              \
     } while (0)
+
+// ---- gradient tables (wn_teacher_wgrad.hip, wn_deconv_bwd.hip): the variables of one flat float32 gradient buffer ----
+struct WnGradEntry {
+    std::string name;      // the TF variable
+    size_t off;            // first float inside the buffer
+    int64_t shape[4];      // the TF shape, ndim entries
+    int ndim;
+};
+// floats of the buffer: the entries are contiguous and the last one is a bias [shape[0]]
+inline size_t wn_grad_floats(const std::vector<WnGradEntry>& t) { return t.empty() ? 0 : t.back().off + (size_t)t.back().shape[0]; }
+// entry i for the *_grad_info calls (message prefix fn); refuses a bad index, a null output or a short name buffer
+int wn_grad_info(const wn_handle* h, const char* fn, const std::vector<WnGradEntry>& t, int i, char* name, size_t name_cap,
+                 int64_t* offset, int64_t* shape4, int* ndim);
 
 // ---- sizes of the IAF packs (width 64, deconv_width 256) ----
 // layer: P 112 K-steps * 4 mb * 64 lanes | PR 8 * 4 * 64 | bgate 64 | bres 64

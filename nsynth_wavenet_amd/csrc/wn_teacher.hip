@@ -15,57 +15,14 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <mutex>
-#include <unordered_map>
 
-#include "wn_internal.h"
-#include "wn_codec.h"
+#include "wn_teacher.h"
+#include "wn_g4.h"
 #include "wn_mol.h"
 #include "wn_pack_h.h"
 #include "wn_mfma_h.h"
 
 namespace {
-
-constexpr int TG_NT = 4;                 // 16-column blocks per wave
-constexpr int TG_TN = 4 * 16 * TG_NT;    // columns per workgroup
-constexpr int TG_KC = 4;                 // K-steps of weights per LDS stage
-constexpr int TG_XP = 64;                // zero left pad of the scaled input row
-
-enum { TG_SRC_G4 = 0, TG_SRC_ACC_RELU = 1 };
-enum { TG_EPI_GATE = 0, TG_EPI_RS = 1, TG_EPI_ACC = 2, TG_EPI_OUT = 3, TG_EPI_GATE_TAPE = 4, TG_EPI_BGATE = 5, TG_EPI_MASK = 6 };
-
-struct TgSeg {
-    const unsigned* base;   // G4 words or accumulator-layout floats
-    long long bstride;      // words per batch element
-    int rowlen;             // G4: columns per group row; ACC: 16-row blocks per column block
-    int col0;               // G4: column of t = 0 (left pad, tap shift, centre crop)
-    int nks;                // 32-channel K-steps in this segment
-    int ng;                 // G4: group rows per plane
-    int kind;
-};
-
-struct TgArgs {
-    TgSeg seg[4];
-    int nseg, nks;
-    const unsigned* wp;     // A fragments [m-tile][K-step][4 row blocks][plane][lane][4]
-    const float* bias;      // [m-tile][64], tile-local row order
-    float inv_scale;
-    long long T;            // valid columns (only the time-major store is guarded)
-    unsigned* og4;          // GATE: m;  RS: l (updated in place)
-    long long og4_bstride;
-    int og4_rowlen, og4_col0, og4_ng;
-    float* oacc;            // RS: s (accumulated);  ACC: destination
-    long long oacc_bstride;
-    int oacc_nmb;
-    int res_mtiles;         // RS: m-tiles below this are residual rows, the rest skip rows
-    float* otm;             // OUT: [B][T][ow]
-    int ow;
-    // tape (accumulator layout [t/16][row block][lane][4] per batch element):  GATE_TAPE writes sigma at row block
-    // hb and tanh at tape_hoff + hb, BGATE reads them;  MASK reads the pre-ReLU rows of its own row blocks
-    float* tape;
-    long long tape_bstride;
-    int tape_nmb, tape_hoff;
-};
 
 // U = 64-row m-tiles per workgroup (1 or 2): two tiles halve the re-reads of the activation operand,
 // which bound the kernel (each operand word is fetched once per workgroup row of the grid).
@@ -395,10 +352,9 @@ __global__ __launch_bounds__(256) void tg_start_kernel(const float* __restrict__
     if (t >= 0) {
         const float* xp = xs + (size_t)b * (TG_XP + Tp) + TG_XP + t;
         const float x0 = xp[-3], x1 = xp[-2], x2 = xp[-1];
-        const int s = g >> 2, kg = g & 3;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int ch = 2 * (16 * s + 8 * (i >> 1) + 2 * kg + (i & 1));
+            const int ch = wn_g4_channel(g, i);
             float o[2];
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh)
@@ -409,37 +365,7 @@ __global__ __launch_bounds__(256) void tg_start_kernel(const float* __restrict__
             lw[i] = c2;
         }
     }
-    unsigned* base = l + (size_t)b * W * RS;
-    *reinterpret_cast<wn_u4*>(base + ((size_t)g * RS + c) * 4) = hw;
-    *reinterpret_cast<wn_u4*>(base + ((size_t)(NG + g) * RS + c) * 4) = lw;
-}
-
-struct TLayout {
-    long long T, Tp, TE, RS;
-    int c0;
-    size_t enc, l, m, s, h1, xs, scratch, total;
-};
-
-TLayout t_layout(const wn_handle* h, int B, int F, long long T) {
-    const wn_config& c = h->cfg;
-    TLayout L;
-    L.T = T;
-    L.Tp = (T + TG_TN - 1) / TG_TN * TG_TN;
-    L.TE = (long long)F * h->frame_shift;
-    L.c0 = (int)((L.TE - T) / 2);                           // wavenet.py:76-85
-    L.RS = IAF_LP + L.Tp;
-    size_t o = 0;
-    auto carve = [&](size_t floats) { size_t r = o; o += align_up(floats * sizeof(float), 256); return r; };
-    L.enc = carve((size_t)B * c.deconv_width * (L.TE + TG_TN) + 64);
-    L.l = carve((size_t)B * c.width * L.RS);
-    L.m = carve((size_t)B * (c.gate_width / 2) * L.Tp);
-    L.s = carve((size_t)B * c.skip_width * L.Tp);
-    L.h1 = carve((size_t)B * c.skip_width * L.Tp);
-    L.xs = carve((size_t)B * (TG_XP + L.Tp));
-    L.scratch = o;
-    o += wn_deconv_scratch_bytes(h, B, F);
-    L.total = o;
-    return L;
+    wn_g4_store(l + (size_t)b * W * RS, NG, RS, g, c, hw, lw);
 }
 
 template <int EPI>
@@ -454,6 +380,18 @@ void tg_launch(const TgArgs& a, int mtiles, int B, long long Tp, hipStream_t st)
 }
 
 }  // namespace
+
+void wn_tg_launch(int epi, const TgArgs& a, int mtiles, int B, long long Tp, hipStream_t st) {
+    switch (epi) {
+        case TG_EPI_GATE: return tg_launch<TG_EPI_GATE>(a, mtiles, B, Tp, st);
+        case TG_EPI_RS: return tg_launch<TG_EPI_RS>(a, mtiles, B, Tp, st);
+        case TG_EPI_ACC: return tg_launch<TG_EPI_ACC>(a, mtiles, B, Tp, st);
+        case TG_EPI_OUT: return tg_launch<TG_EPI_OUT>(a, mtiles, B, Tp, st);
+        case TG_EPI_GATE_TAPE: return tg_launch<TG_EPI_GATE_TAPE>(a, mtiles, B, Tp, st);
+        case TG_EPI_BGATE: return tg_launch<TG_EPI_BGATE>(a, mtiles, B, Tp, st);
+        case TG_EPI_MASK: return tg_launch<TG_EPI_MASK>(a, mtiles, B, Tp, st);
+    }
+}
 
 // ---- packing: A fragments of a row-major [M][K] matrix, 64-row tiles, rows picked by rowfn ----
 template <class RowFn>
@@ -572,11 +510,6 @@ namespace {
 // a - b = 2 inv_s / Q formed directly: the difference of two float32 sigmoids the reference's formula takes loses all but
 // two digits of it at Q = 65 536 (the float64 evaluation of the reference's formula is what the tests compare with).
 // The per-component arithmetic is wn_mol.h's, shared with the distillation cross entropy (wn_distill.hip).
-__device__ inline float tl_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
 __device__ inline float tl_wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -603,10 +536,10 @@ __global__ __launch_bounds__(256) void tg_log_prob_kernel(const float* __restric
             wn_mol_thresholds(Q, min_thres, max_thres);
             v = wn_mol_component_lp(xt, c, inv, iq, wn_mol_bin_factor(inv, iq), min_thres, max_thres);
         }
-        const float lmax = tl_wave_max(lg);
+        const float lmax = wn_wave_max(lg);
         const float lse = lmax + logf(tl_wave_sum(lane < M ? expf(lg - lmax) : 0.f));
         v = lane < M ? v + (lg - lse) : NEG;
-        const float vmax = tl_wave_max(v);
+        const float vmax = wn_wave_max(v);
         res = vmax + logf(tl_wave_sum(lane < M ? expf(v - vmax) : 0.f));
     } else if (loss == WN_LOSS_GAUSS) {
         const float ls = fmaxf(o[1], -7.0f), z = (xt - o[0]) * expf(-ls);
@@ -617,7 +550,7 @@ __global__ __launch_bounds__(256) void tg_log_prob_kernel(const float* __restric
         label = min(max(label, 0), Q - 1);
         float m = NEG;
         for (int k = lane; k < ow; k += 64) m = fmaxf(m, o[k]);
-        m = tl_wave_max(m);
+        m = wn_wave_max(m);
         float sum = 0.f;
         for (int k = lane; k < ow; k += 64) sum += expf(o[k] - m);
         res = o[label] - (m + logf(tl_wave_sum(sum)));
@@ -664,7 +597,7 @@ __device__ inline void tl_ce_grad_row(const float* __restrict__ o, float* __rest
         s = s * expf(m - mn) + a;
         m = mn;
     }
-    const float mx = tl_wave_max(m);
+    const float mx = wn_wave_max(m);
     const float rinv = 1.0f / tl_wave_sum(s * expf(m - mx));     // a lane without classes holds s = 0
     const bool once = ow <= 64 * W;                              // v still holds the lane's only classes
 #pragma unroll 4
@@ -702,10 +635,10 @@ __global__ __launch_bounds__(256) void tg_log_prob_grad_kernel(const float* __re
             v = wn_mol_component_lp(xt, c, inv, iq, bf, min_thres, max_thres);
             wn_mol_component_grad(xt, c, inv, iq, bf, min_thres, max_thres, dx, dinv);
         }
-        const float lmax = tl_wave_max(lg);
+        const float lmax = wn_wave_max(lg);
         const float lse = lmax + logf(tl_wave_sum(lane < M ? expf(lg - lmax) : 0.f));
         v = lane < M ? v + (lg - lse) : NEG;
-        const float vmax = tl_wave_max(v);
+        const float vmax = wn_wave_max(v);
         const float res = vmax + logf(tl_wave_sum(lane < M ? expf(v - vmax) : 0.f));
         const float r = lane < M ? expf(v - res) : 0.f;           // responsibility of the component
         dx_tot = tl_wave_sum(r * dx);
@@ -732,16 +665,13 @@ __global__ __launch_bounds__(256) void tg_log_prob_grad_kernel(const float* __re
 }
 }  // namespace
 
-size_t wn_teacher_ws_bytes(const wn_handle* h, int B, int F, long long T) { return t_layout(h, B, F, T).total; }
-
 extern "C" size_t wn_teacher_workspace_bytes(const wn_handle* h, int B, int F, int64_t T) {
     if (!h || !h->finalized || h->cfg.kind != WN_KIND_TEACHER || B < 1 || F < 1 || T < 1) return 0;
-    return wn_teacher_ws_bytes(h, B, F, T);
+    return t_layout(h, B, F, T).total;
 }
 
-// checks of the forward calls (message prefix fn)
-static int tg_forward_check(wn_handle* h, const char* fn, const float* wav, const float* mel, int B, int F, int64_t T,
-                            const float* out_params, const void* ws) {
+int tg_forward_check(wn_handle* h, const char* fn, const float* wav, const float* mel, int B, int F, int64_t T,
+                     const float* out_params, const void* ws) {
     if (!h) return wn_fail(nullptr, WN_EINVAL, "%s: null handle", fn);
     if (!h->finalized) return wn_fail(h, WN_ESTATE, "%s: call wn_finalize first", fn);
     const wn_config& c = h->cfg;
@@ -757,27 +687,26 @@ static int tg_forward_check(wn_handle* h, const char* fn, const float* wav, cons
     return WN_OK;
 }
 
-// the forward; with tape_s != nullptr the skip sum and out1 rows land in the tape and every gate stores its activations
-// to tape_g (layer i at i * B * gate * Tp floats) -- the same arithmetic, so out_params are the same bits either way.
-// With tape_l (training tape) the conditioning and the scaled input row are written to the tape instead of the
-// workspace and layer i reads its input l_i from slot i of tape_l: l_i is copied to the next slot (the workspace row for the
+// the forward; with tape.s the skip sum and out1 rows land in the tape and every gate stores its activations
+// to tape.g (layer i at i * B * gate * Tp floats) -- the same arithmetic, so out_params are the same bits either way.
+// With tape.l (training tape) the conditioning and the scaled input row are written to the tape instead of the
+// workspace and layer i reads its input l_i from slot i of tape.l: l_i is copied to the next slot (the workspace row for the
 // last layer) before the residual GEMM updates that copy in place -- the same kernels on the same values.
-static int tg_forward(wn_handle* h, const char* fn, const float* wav, const float* mel, int B, int F, int64_t T,
-                      float* out_params, void* ws, size_t ws_bytes, float* tape_s, float* tape_h1, float* tape_g,
-                      void* stream, unsigned* tape_l = nullptr, float* tape_enc = nullptr, float* tape_xs = nullptr) {
+int tg_forward(wn_handle* h, const char* fn, const float* wav, const float* mel, int B, int F, int64_t T, float* out_params,
+               void* ws, size_t ws_bytes, const TgTape& tape, void* stream) {
     const wn_config& c = h->cfg;
     const TLayout L = t_layout(h, B, F, T);
     if (ws_bytes < L.total)
         return wn_fail(h, WN_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, L.total);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     char* base = reinterpret_cast<char*>(ws);
-    float* enc = tape_enc ? tape_enc : reinterpret_cast<float*>(base + L.enc);
+    float* enc = tape.enc ? tape.enc : reinterpret_cast<float*>(base + L.enc);
     unsigned* lws = reinterpret_cast<unsigned*>(base + L.l);
-    unsigned* l = tape_l ? tape_l : lws;
+    unsigned* l = tape.l ? tape.l : lws;
     unsigned* m = reinterpret_cast<unsigned*>(base + L.m);
-    float* s = tape_s ? tape_s : reinterpret_cast<float*>(base + L.s);
-    float* h1 = tape_h1 ? tape_h1 : reinterpret_cast<float*>(base + L.h1);
-    float* xs = tape_xs ? tape_xs : reinterpret_cast<float*>(base + L.xs);
+    float* s = tape.s ? tape.s : reinterpret_cast<float*>(base + L.s);
+    float* h1 = tape.h1 ? tape.h1 : reinterpret_cast<float*>(base + L.h1);
+    float* xs = tape.xs ? tape.xs : reinterpret_cast<float*>(base + L.xs);
     const int W = c.width, S = c.skip_width, H = c.gate_width / 2, Cd = c.deconv_width;
     const TeacherPack& P = h->teacher;
 
@@ -791,82 +720,67 @@ static int tg_forward(wn_handle* h, const char* fn, const float* wav, const floa
         dim3 g2((unsigned)((L.RS + 255) / 256), W / 8, B);
         hipLaunchKernelGGL(tg_start_kernel, g2, dim3(256), 0, st, xs, h->d_blob + h->ar.start_off, l, W, L.Tp, L.RS);
     }
-    auto seg_g4 = [](const unsigned* p, long long bstride, long long rowlen, int col0, int nks, int ng) {
-        TgSeg sg;
-        sg.base = p; sg.bstride = bstride; sg.rowlen = (int)rowlen; sg.col0 = col0; sg.nks = nks; sg.ng = ng;
-        sg.kind = TG_SRC_G4;
-        return sg;
-    };
     auto seg_acc = [&](const float* p, int nks) {
         TgSeg sg;
         sg.base = reinterpret_cast<const unsigned*>(p); sg.bstride = (long long)S * L.Tp; sg.rowlen = S / 16;
         sg.col0 = 0; sg.nks = nks; sg.ng = 0; sg.kind = TG_SRC_ACC_RELU;
         return sg;
     };
-    auto base_args = [&](const TeacherGemmPack& g) {
-        TgArgs a{};
-        a.wp = reinterpret_cast<const unsigned*>(h->d_blob + g.w_off);
-        a.bias = h->d_blob + g.b_off;
-        a.inv_scale = g.inv_scale;
-        a.nks = g.nks;
-        a.T = T;
-        return a;
-    };
-    TgSeg seg_l = seg_g4(l, (long long)W * L.RS, L.RS, IAF_LP, W / 32, W / 8);
+    TgSeg seg_l = tg_seg_g4(l, (long long)W * L.RS, L.RS, IAF_LP, W);
     const size_t l_words = (size_t)B * W * L.RS;
-    const TgSeg seg_enc = seg_g4(reinterpret_cast<const unsigned*>(enc), (long long)Cd * L.TE, L.TE, L.c0, Cd / 32, Cd / 8);
-    const TgSeg seg_m = seg_g4(m, (long long)H * L.Tp, L.Tp, 0, H / 32, H / 8);
+    const TgSeg seg_enc = tg_seg_g4(reinterpret_cast<const unsigned*>(enc), (long long)Cd * L.TE, L.TE, L.c0, Cd);
+    const TgSeg seg_m = tg_seg_g4(m, (long long)H * L.Tp, L.Tp, 0, H);
     // s = skip_start(l)  (wavenet.py:231-233)
     {
-        TgArgs a = base_args(P.skip_start);
+        TgArgs a = tg_pack_args(h, P.skip_start, T);
         a.seg[0] = seg_l; a.nseg = 1;
         a.oacc = s; a.oacc_bstride = (long long)S * L.Tp; a.oacc_nmb = S / 16;
-        tg_launch<TG_EPI_ACC>(a, P.skip_start.mtiles, B, L.Tp, st);
+        wn_tg_launch(TG_EPI_ACC, a, P.skip_start.mtiles, B, L.Tp, st);
     }
     for (size_t li = 0; li < P.layers.size(); ++li) {
         const TeacherLayerPack& tl = P.layers[li];
-        if (tape_l) {
+        if (tape.l) {
             seg_l.base = l;
             unsigned* next = li + 1 < P.layers.size() ? l + l_words : lws;
             WN_HIP(h, hipMemcpyAsync(next, l, l_words * 4, hipMemcpyDeviceToDevice, st));
             l = next;                     // the gate below reads seg_l (slot li); the residual GEMM updates the copy
         }
         {   // d = dilated_conv(l) + mel_cond(enc); m = sigmoid(d[:H]) * tanh(d[H:])  (wavenet.py:243-269)
-            TgArgs a = base_args(tl.gate);
+            TgArgs a = tg_pack_args(h, tl.gate, T);
             for (int tap = 0; tap < 3; ++tap) {
                 a.seg[tap] = seg_l;
                 a.seg[tap].col0 = IAF_LP - (2 - tap) * tl.dilation;
             }
             a.seg[3] = seg_enc; a.nseg = 4;
             a.og4 = m; a.og4_bstride = (long long)H * L.Tp; a.og4_rowlen = (int)L.Tp; a.og4_col0 = 0; a.og4_ng = H / 8;
-            if (tape_g) {
-                a.tape = tape_g + li * (size_t)B * 2 * H * L.Tp;
+            if (tape.g) {
+                a.tape = tape.g + li * (size_t)B * 2 * H * L.Tp;
                 a.tape_bstride = 2ll * H * L.Tp; a.tape_nmb = 2 * H / 16; a.tape_hoff = H / 16;
-                tg_launch<TG_EPI_GATE_TAPE>(a, tl.gate.mtiles, B, L.Tp, st);
+                wn_tg_launch(TG_EPI_GATE_TAPE, a, tl.gate.mtiles, B, L.Tp, st);
             } else {
-                tg_launch<TG_EPI_GATE>(a, tl.gate.mtiles, B, L.Tp, st);
+                wn_tg_launch(TG_EPI_GATE, a, tl.gate.mtiles, B, L.Tp, st);
             }
         }
         {   // l += res(m); s += skip(m)  (wavenet.py:271-277)
-            TgArgs a = base_args(tl.rs);
+            TgArgs a = tg_pack_args(h, tl.rs, T);
             a.seg[0] = seg_m; a.nseg = 1;
             a.og4 = l; a.og4_bstride = (long long)W * L.RS; a.og4_rowlen = (int)L.RS; a.og4_col0 = IAF_LP; a.og4_ng = W / 8;
             a.oacc = s; a.oacc_bstride = (long long)S * L.Tp; a.oacc_nmb = S / 16;
             a.res_mtiles = W / 64;
-            tg_launch<TG_EPI_RS>(a, tl.rs.mtiles, B, L.Tp, st);
+            wn_tg_launch(TG_EPI_RS, a, tl.rs.mtiles, B, L.Tp, st);
         }
     }
     {   // out1(relu(s)) + mel_cond_out1(enc)  (wavenet.py:283-289)
-        TgArgs a = base_args(P.out1);
+        TgArgs a = tg_pack_args(h, P.out1, T);
         a.seg[0] = seg_acc(s, S / 32); a.seg[1] = seg_enc; a.nseg = 2;
         a.oacc = h1; a.oacc_bstride = (long long)S * L.Tp; a.oacc_nmb = S / 16;
-        tg_launch<TG_EPI_ACC>(a, P.out1.mtiles, B, L.Tp, st);
+        wn_tg_launch(TG_EPI_ACC, a, P.out1.mtiles, B, L.Tp, st);
     }
     {   // out2(relu(.))  (wavenet.py:290-292)
-        TgArgs a = base_args(P.out2);
+        TgArgs a = tg_pack_args(h, P.out2, T);
         a.seg[0] = seg_acc(h1, S / 32); a.nseg = 1;
         a.otm = out_params; a.ow = c.out_width;
-        tg_launch<TG_EPI_OUT>(a, P.out2.mtiles, B, L.Tp, st);
+        wn_tg_launch(TG_EPI_OUT, a, P.out2.mtiles, B, L.Tp, st);
     }
     WN_HIP(h, hipGetLastError());
     return WN_OK;
@@ -877,7 +791,7 @@ extern "C" int wn_teacher_forward(wn_handle* h, const float* wav, const float* m
     const char* fn = "wn_teacher_forward";
     if (int rc = tg_forward_check(h, fn, wav, mel, B, F, T, out_params, ws)) return rc;
     const WnWork work(h);
-    return tg_forward(h, fn, wav, mel, B, F, T, out_params, ws, ws_bytes, nullptr, nullptr, nullptr, stream);
+    return tg_forward(h, fn, wav, mel, B, F, T, out_params, ws, ws_bytes, TgTape{}, stream);
 }
 
 extern "C" int wn_teacher_log_prob(wn_handle* h, const float* out_params, const float* wav, int B, int64_t T, float* log_prob,
@@ -916,992 +830,5 @@ extern "C" int wn_teacher_log_prob_grad(wn_handle* h, const float* out_params, c
     hipLaunchKernelGGL(tg_log_prob_grad_kernel, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, st, out_params, wav,
                        d_log_prob, d_out_params, d_wav, n, c.out_width, c.loss_type, Q, c.use_mu_law, vec);
     WN_HIP(h, hipGetLastError());
-    return WN_OK;
-}
-
-// ---- input VJP of the teacher: d out_params [B,T,ow] -> d wav [B,T], weights frozen ----
-// The tape (wn_teacher_forward_tape) holds what the reverse pass reads: a header, the pre-ReLU skip sum s and out1 rows
-// (accumulator layout, as the forward keeps them), and sigma / tanh of every gate.  The reverse pass runs the forward's
-// GEMM kernel on the transposed packs: d out2 and d out1 through the ReLU masks (MASK), then per layer from the last one
-// dm = W_res^T dl + W_skip^T ds with the gate derivative in the epilogue (BGATE) and dl += sum_k W_dil[k]^T dd(t + (2-k) d)
-// in place (RS, anti-causal taps: dd rows carry a zero right pad of 2 * max dilation), then skip_start^T and the start
-// conv transposed.  The operands are split-fp16 like the forward's, so d out_params enter scaled by a power of two that
-// brings their largest magnitude to [1, 2) (found on the device) and d wav leaves unscaled: the VJP is linear.
-namespace {
-constexpr uint32_t TB_MAGIC = 0x31505457u;      // "WTP1"
-constexpr uint32_t TB_MAGIC_TRAIN = 0x32505457u;   // "WTP2": a training tape (wn_teacher_forward_train_tape)
-constexpr size_t TB_HEAD = 256;
-constexpr int TB_NMAX = 1024;                   // workgroups of the max-magnitude pass
-
-struct TapeRec {
-    uint64_t serial;
-    int B;
-    long long T;
-    int F;              // > 0: a training tape (wn_teacher_forward_train_tape) for F mel frames
-};
-std::mutex g_tape_mu;
-std::unordered_map<const void*, TapeRec> g_tapes;   // tape address -> the handle and shape that last wrote it
-
-struct TapeLayout {
-    long long Tp;
-    size_t s, h1, g, total;
-};
-TapeLayout tape_layout(const wn_handle* h, int B, long long T) {
-    const wn_config& c = h->cfg;
-    TapeLayout L;
-    L.Tp = (T + TG_TN - 1) / TG_TN * TG_TN;
-    const size_t cols = (size_t)B * L.Tp;
-    L.s = TB_HEAD;
-    L.h1 = L.s + cols * c.skip_width * sizeof(float);
-    L.g = L.h1 + cols * c.skip_width * sizeof(float);
-    L.total = L.g + h->teacher.layers.size() * cols * c.gate_width * sizeof(float);
-    return L;
-}
-
-struct BLayout {
-    long long Tp, RD;
-    int Kp;
-    size_t scal, dout, dh1, ds, dl, dd, total;
-};
-BLayout b_layout(const wn_handle* h, int B, long long T) {
-    const wn_config& c = h->cfg;
-    BLayout L;
-    L.Tp = (T + TG_TN - 1) / TG_TN * TG_TN;
-    L.RD = L.Tp + 2 * (1ll << (c.num_stages - 1));
-    L.Kp = h->teacher.out2_t.nks * 32;
-    size_t o = 0;
-    auto carve = [&](size_t words) { size_t r = o; o += align_up(words * 4, 256); return r; };
-    L.scal = carve(4 + TB_NMAX);
-    L.dout = carve((size_t)B * L.Kp * L.Tp);
-    L.dh1 = carve((size_t)B * c.skip_width * L.Tp);
-    L.ds = carve((size_t)B * c.skip_width * L.Tp);
-    L.dl = carve((size_t)B * c.width * L.Tp);
-    L.dd = carve((size_t)B * c.gate_width * L.RD);
-    L.total = o;
-    return L;
-}
-
-struct TbHead {
-    unsigned w[8];
-};
-__global__ void tb_header_kernel(TbHead v, unsigned* __restrict__ dst) {
-    if (threadIdx.x < 8) dst[threadIdx.x] = v.w[threadIdx.x];
-}
-
-__device__ inline float tb_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-// largest |x| per workgroup, then one workgroup: scal[0] = 2^k with max |x| 2^k in [1, 2), scal[1] = 2^-k
-__global__ __launch_bounds__(256) void tb_absmax_kernel(const float* __restrict__ x, long long n, float* __restrict__ part) {
-    __shared__ float sh[4];
-    float m = 0.f;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) m = fmaxf(m, fabsf(x[i]));
-    m = tb_wave_max(m);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-}
-__global__ __launch_bounds__(256) void tb_scale_kernel(const float* __restrict__ part, int np, float* __restrict__ scal) {
-    __shared__ float sh[4];
-    float m = 0.f;
-    for (int i = threadIdx.x; i < np; i += 256) m = fmaxf(m, part[i]);
-    m = tb_wave_max(m);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-        int k = 0;
-        if (m > 0.f && m < __builtin_inff()) k = min(max(-ilogbf(m), -100), 100);
-        scal[0] = ldexpf(1.f, k);
-        scal[1] = ldexpf(1.f, -k);
-    }
-}
-
-// d out_params [B,T,ow] (scaled by scal[0]) -> G4 rows of Kp channels (zero beyond ow and from column T on)
-__global__ __launch_bounds__(256) void tb_dout_kernel(const float* __restrict__ dout, const float* __restrict__ scal,
-                                                      unsigned* __restrict__ g4, long long T, long long Tp, int ow, int Kp) {
-    const int b = blockIdx.z, gr = blockIdx.y, NG = Kp / 8;
-    const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (c >= Tp) return;
-    const float sc = scal[0];
-    const int s4 = gr >> 2, kg = gr & 3;
-    wn_u4 hw, lw;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float o[2];
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-            const int ch = 32 * s4 + 16 * (i >> 1) + 4 * kg + 2 * (i & 1) + hh;
-            o[hh] = c < T && ch < ow ? dout[((size_t)b * T + c) * ow + ch] * sc : 0.f;
-        }
-        unsigned a, a2;
-        wn_split_pair(o[0], o[1], a, a2);
-        hw[i] = a;
-        lw[i] = a2;
-    }
-    unsigned* base = g4 + (size_t)b * Kp * Tp;
-    *reinterpret_cast<wn_u4*>(base + ((size_t)gr * Tp + c) * 4) = hw;
-    *reinterpret_cast<wn_u4*>(base + ((size_t)(NG + gr) * Tp + c) * 4) = lw;
-}
-
-// conv_start transposed (tg_start_kernel: l0(t) = b + w0 x(t-3) + w1 x(t-2) + w2 x(t-1)):
-// d wav(t) = scal[1] sum_c (w0[c] dl0[c](t+3) + w1[c] dl0[c](t+2) + w2[c] dl0[c](t+1)); 64 columns x 4 waves of channels
-__global__ __launch_bounds__(256) void tb_dx_kernel(const unsigned* __restrict__ dl, const float* __restrict__ wb,
-                                                    const float* __restrict__ scal, float* __restrict__ dwav, int W,
-                                                    long long T, long long Tp) {
-    __shared__ float red[4][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.y, NG = W / 8;
-    const long long t = (long long)blockIdx.x * 64 + lane;
-    float acc = 0.f;
-    if (t < T) {
-        const unsigned* base = dl + (size_t)b * W * Tp;
-        for (int gr = wave; gr < NG; gr += 4) {
-            const int s4 = gr >> 2, kg = gr & 3;
-            for (int k = 0; k < 3; ++k) {
-                const long long col = t + 3 - k;
-                if (col >= T) continue;
-                const wn_u4 hw = *reinterpret_cast<const wn_u4*>(base + ((size_t)gr * Tp + col) * 4);
-                const wn_u4 lw = *reinterpret_cast<const wn_u4*>(base + ((size_t)(NG + gr) * Tp + col) * 4);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float v0, v1;
-                    wn_join_pair(hw[i], lw[i], v0, v1);
-                    const int ch = 32 * s4 + 16 * (i >> 1) + 4 * kg + 2 * (i & 1);
-                    acc = fmaf(wb[k * W + ch], v0, acc);
-                    acc = fmaf(wb[k * W + ch + 1], v1, acc);
-                }
-            }
-        }
-    }
-    red[wave][lane] = acc;
-    __syncthreads();
-    if (wave == 0 && t < T) dwav[(size_t)b * T + t] = (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) * scal[1];
-}
-
-// what the two VJP-side calls refuse (the distillation losses' own refusals, wn_distill.hip)
-int tb_check(wn_handle* h, const char* fn) {
-    if (!h) return wn_fail(nullptr, WN_EINVAL, "%s: null handle", fn);
-    const wn_config& c = h->cfg;
-    if (c.kind != WN_KIND_TEACHER)
-        return wn_fail(h, WN_EINVAL, "%s: this is a ParallelWavenet student handle; the teacher's input VJP runs under the "
-                       "TEACHER's handle", fn);
-    if (c.loss_type == WN_LOSS_CE)
-        return wn_fail(h, WN_EINVAL, "%s: cross-entropy (ce) teacher: the distillation losses need a mol or gauss teacher "
-                       "(parallel_wavenet.py:133-135)", fn);
-    if (c.use_mu_law)
-        return wn_fail(h, WN_EINVAL, "%s: mu-law teacher: mu-law students and teachers are not supported by the "
-                       "distillation losses", fn);
-    if (!h->finalized) return wn_fail(h, WN_ESTATE, "%s: call wn_finalize first", fn);
-    if (!h->teacher.vjp_ok)
-        return wn_fail(h, WN_EINVAL, "%s: width %d, skip_width %d, gate_width / 2 = %d must be multiples of 64 and "
-                       "out_width <= 64 for the transposed GEMMs", fn, c.width, c.skip_width, c.gate_width / 2);
-    return WN_OK;
-}
-}  // namespace
-
-extern "C" size_t wn_teacher_tape_bytes(const wn_handle* h, int B, int64_t T) {
-    if (!h || !h->finalized || h->cfg.kind != WN_KIND_TEACHER || B < 1 || T < 1) return 0;
-    return tape_layout(h, B, T).total;
-}
-
-extern "C" size_t wn_teacher_backward_workspace_bytes(const wn_handle* h, int B, int64_t T) {
-    if (!h || !h->finalized || h->cfg.kind != WN_KIND_TEACHER || !h->teacher.vjp_ok || B < 1 || T < 1) return 0;
-    return b_layout(h, B, T).total;
-}
-
-extern "C" int wn_teacher_forward_tape(wn_handle* h, const float* wav, const float* mel, int B, int F, int64_t T,
-                                       float* out_params, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes,
-                                       void* stream) {
-    const char* fn = "wn_teacher_forward_tape";
-    if (int rc = tb_check(h, fn)) return rc;
-    if (int rc = tg_forward_check(h, fn, wav, mel, B, F, T, out_params, ws)) return rc;
-    if (!tape) return wn_fail(h, WN_EINVAL, "%s: bad argument (tape)", fn);
-    const TapeLayout TL = tape_layout(h, B, T);
-    if (tape_bytes < TL.total) return wn_fail(h, WN_ENOMEM, "%s: tape %zu < %zu bytes", fn, tape_bytes, TL.total);
-    const WnWork work(h);
-    char* tb = reinterpret_cast<char*>(tape);
-    TbHead hd;
-    const uint64_t ser = h->teacher.serial;
-    hd.w[0] = TB_MAGIC; hd.w[1] = (unsigned)ser; hd.w[2] = (unsigned)(ser >> 32); hd.w[3] = (unsigned)B;
-    hd.w[4] = (unsigned)T; hd.w[5] = (unsigned)((uint64_t)T >> 32); hd.w[6] = (unsigned)h->teacher.layers.size();
-    hd.w[7] = (unsigned)F;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(tb_header_kernel, dim3(1), dim3(64), 0, st, hd, reinterpret_cast<unsigned*>(tb));
-    const int rc = tg_forward(h, fn, wav, mel, B, F, T, out_params, ws, ws_bytes, reinterpret_cast<float*>(tb + TL.s),
-                              reinterpret_cast<float*>(tb + TL.h1), reinterpret_cast<float*>(tb + TL.g), stream);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_tape_mu);
-    g_tapes[tape] = TapeRec{ser, B, (long long)T, 0};
-    return WN_OK;
-}
-
-// registry check shared by the reverse-pass calls; *F receives the frame count of a training tape (0: a plain tape)
-static int tb_tape_check(wn_handle* h, const char* fn, const void* tape, size_t tape_bytes, int B, int64_t T, int* F) {
-    const TapeLayout TL = tape_layout(h, B, T);
-    if (tape_bytes < TL.total)
-        return wn_fail(h, WN_EINVAL, "%s: a tape of %zu bytes cannot hold B = %d, T = %lld (%zu bytes)", fn, tape_bytes, B,
-                       (long long)T, TL.total);
-    std::lock_guard<std::mutex> lk(g_tape_mu);
-    auto it = g_tapes.find(tape);
-    if (it == g_tapes.end() || it->second.serial != h->teacher.serial)
-        return wn_fail(h, WN_EINVAL, "%s: the tape was not written by wn_teacher_forward_tape of this handle", fn);
-    if (it->second.B != B || it->second.T != (long long)T)
-        return wn_fail(h, WN_EINVAL, "%s: the tape holds B = %d, T = %lld, not B = %d, T = %lld", fn, it->second.B,
-                       it->second.T, B, (long long)T);
-    *F = it->second.F;
-    return WN_OK;
-}
-
-namespace {
-struct TwCtx;                                   // weight-gradient side of the reverse pass (below)
-int tw_aux(wn_handle* h, const TwCtx& w, hipStream_t st);
-int tw_head(wn_handle* h, const TwCtx& w, hipStream_t st, int stage);
-int tw_layer(wn_handle* h, const TwCtx& w, size_t li, hipStream_t st);
-int tw_tail(wn_handle* h, const TwCtx& w, hipStream_t st);
-}  // namespace
-
-// The reverse pass.  wg == nullptr: the input VJP alone, launch for launch what wn_teacher_backward_input always ran.
-// With wg the weight-gradient products, the d enc GEMMs and their reductions are issued between those launches, where
-// the cotangents they read are complete; they write nothing the input VJP reads, so d_wav is the same bits.
-static int tb_reverse(wn_handle* h, const void* tape, const float* d_out_params, int B, int64_t T, float* d_wav, void* ws,
-                      void* stream, const TwCtx* wg) {
-    const TapeLayout TL = tape_layout(h, B, T);
-    const BLayout L = b_layout(h, B, T);
-    const wn_config& c = h->cfg;
-    const int W = c.width, S = c.skip_width, G = c.gate_width, H = G / 2;
-    const TeacherPack& P = h->teacher;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    char* base = reinterpret_cast<char*>(ws);
-    float* scal = reinterpret_cast<float*>(base + L.scal);
-    unsigned* dout = reinterpret_cast<unsigned*>(base + L.dout);
-    unsigned* dh1 = reinterpret_cast<unsigned*>(base + L.dh1);
-    unsigned* ds = reinterpret_cast<unsigned*>(base + L.ds);
-    unsigned* dl = reinterpret_cast<unsigned*>(base + L.dl);
-    unsigned* dd = reinterpret_cast<unsigned*>(base + L.dd);
-    const char* tb = reinterpret_cast<const char*>(tape);
-    float* tape_s = const_cast<float*>(reinterpret_cast<const float*>(tb + TL.s));
-    float* tape_h1 = const_cast<float*>(reinterpret_cast<const float*>(tb + TL.h1));
-    float* tape_g = const_cast<float*>(reinterpret_cast<const float*>(tb + TL.g));
-    const long long Tp = L.Tp;
-
-    // operand scale
-    const long long n = (long long)B * T * c.out_width;
-    const int nb = (int)std::min<long long>(TB_NMAX, (n + 255) / 256);
-    hipLaunchKernelGGL(tb_absmax_kernel, dim3(nb), dim3(256), 0, st, d_out_params, n, scal + 4);
-    hipLaunchKernelGGL(tb_scale_kernel, dim3(1), dim3(256), 0, st, scal + 4, nb, scal);
-    hipLaunchKernelGGL(tb_dout_kernel, dim3((unsigned)((Tp + 255) / 256), L.Kp / 8, B), dim3(256), 0, st, d_out_params, scal,
-                       dout, (long long)T, Tp, c.out_width, L.Kp);
-    WN_HIP(h, hipMemsetAsync(dl, 0, (size_t)B * W * Tp * 4, st));
-    WN_HIP(h, hipMemsetAsync(dd, 0, (size_t)B * G * L.RD * 4, st));
-
-    auto seg = [](const unsigned* p, long long bstride, long long rowlen, long long col0, int C) {
-        TgSeg sg;
-        sg.base = p; sg.bstride = bstride; sg.rowlen = (int)rowlen; sg.col0 = (int)col0; sg.nks = C / 32; sg.ng = C / 8;
-        sg.kind = TG_SRC_G4;
-        return sg;
-    };
-    auto args = [&](const TeacherGemmPack& g, unsigned* og4, long long obstride, long long orowlen, int C) {
-        TgArgs a{};
-        a.wp = reinterpret_cast<const unsigned*>(h->d_blob + g.w_off);
-        a.bias = h->d_blob + g.b_off;
-        a.inv_scale = g.inv_scale;
-        a.nks = g.nks;
-        a.T = T;
-        a.og4 = og4; a.og4_bstride = obstride; a.og4_rowlen = (int)orowlen; a.og4_col0 = 0; a.og4_ng = C / 8;
-        return a;
-    };
-    const TgSeg seg_ds = seg(ds, (long long)S * Tp, Tp, 0, S), seg_dl = seg(dl, (long long)W * Tp, Tp, 0, W);
-    {   // d relu(h1) = W_out2^T d out, masked by h1 > 0  (wavenet.py:290-292)
-        TgArgs a = args(P.out2_t, dh1, (long long)S * Tp, Tp, S);
-        a.seg[0] = seg(dout, (long long)L.Kp * Tp, Tp, 0, L.Kp); a.nseg = 1;
-        a.tape = tape_h1; a.tape_bstride = (long long)S * Tp; a.tape_nmb = S / 16;
-        tg_launch<TG_EPI_MASK>(a, P.out2_t.mtiles, B, Tp, st);
-    }
-    if (wg) {
-        if (int rc = tw_aux(h, *wg, st)) return rc;
-        if (int rc = tw_head(h, *wg, st, 0)) return rc;
-    }
-    {   // ds = W_out1^T d h1 (its skip columns), masked by s > 0  (wavenet.py:283-289)
-        TgArgs a = args(P.out1_t, ds, (long long)S * Tp, Tp, S);
-        a.seg[0] = seg(dh1, (long long)S * Tp, Tp, 0, S); a.nseg = 1;
-        a.tape = tape_s; a.tape_bstride = (long long)S * Tp; a.tape_nmb = S / 16;
-        tg_launch<TG_EPI_MASK>(a, P.out1_t.mtiles, B, Tp, st);
-    }
-    if (wg)
-        if (int rc = tw_head(h, *wg, st, 1)) return rc;
-    for (size_t li = P.layers.size(); li-- > 0;) {
-        const TeacherLayerPack& tl = P.layers[li];
-        {   // dm = W_res^T dl + W_skip^T ds -> dd through the gate derivative  (wavenet.py:264-277 transposed)
-            TgArgs a = args(tl.rs_t, dd, (long long)G * L.RD, L.RD, G);
-            a.seg[0] = seg_dl; a.seg[1] = seg_ds; a.nseg = 2;
-            a.tape = tape_g + li * (size_t)B * G * Tp; a.tape_bstride = (long long)G * Tp; a.tape_nmb = G / 16;
-            a.tape_hoff = H / 16;
-            tg_launch<TG_EPI_BGATE>(a, tl.rs_t.mtiles, B, Tp, st);
-        }
-        if (wg)     // dl = d l_{li+1} and dd_li are complete here, before the dilated step overwrites dl
-            if (int rc = tw_layer(h, *wg, li, st)) return rc;
-        {   // dl += sum_k W_dil[k]^T dd(t + (2 - k) dilation)  (wavenet.py:243-262 transposed)
-            TgArgs a = args(tl.gate_t, dl, (long long)W * Tp, Tp, W);
-            for (int k = 0; k < 3; ++k) a.seg[k] = seg(dd, (long long)G * L.RD, L.RD, (long long)(2 - k) * tl.dilation, G);
-            a.nseg = 3;
-            a.res_mtiles = W / 64;
-            tg_launch<TG_EPI_RS>(a, tl.gate_t.mtiles, B, Tp, st);
-        }
-    }
-    {   // dl0 += W_skip_start^T ds  (wavenet.py:231-233)
-        TgArgs a = args(P.skip_start_t, dl, (long long)W * Tp, Tp, W);
-        a.seg[0] = seg_ds; a.nseg = 1;
-        a.res_mtiles = W / 64;
-        tg_launch<TG_EPI_RS>(a, P.skip_start_t.mtiles, B, Tp, st);
-    }
-    if (wg)
-        if (int rc = tw_tail(h, *wg, st)) return rc;
-    if (d_wav)
-        hipLaunchKernelGGL(tb_dx_kernel, dim3((unsigned)((T + 63) / 64), B), dim3(256), 0, st, dl,
-                           h->d_blob + h->ar.start_off, scal, d_wav, W, (long long)T, Tp);
-    WN_HIP(h, hipGetLastError());
-    return WN_OK;
-}
-
-extern "C" int wn_teacher_backward_input(wn_handle* h, const void* tape, size_t tape_bytes, const float* d_out_params,
-                                         int B, int64_t T, float* d_wav, void* ws, size_t ws_bytes, void* stream) {
-    const char* fn = "wn_teacher_backward_input";
-    if (int rc = tb_check(h, fn)) return rc;
-    if (B < 1 || T < 1 || !tape || !d_out_params || !d_wav || !ws) return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
-    int F = 0;
-    if (int rc = tb_tape_check(h, fn, tape, tape_bytes, B, T, &F)) return rc;
-    const BLayout L = b_layout(h, B, T);
-    if (ws_bytes < L.total) return wn_fail(h, WN_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, L.total);
-    const WnWork work(h);
-    return tb_reverse(h, tape, d_out_params, B, T, d_wav, ws, stream, nullptr);
-}
-
-
-// ---- weight gradients of the teacher: d out_params -> d of every variable of the residual stack and head ----
-// The reverse pass above already holds every cotangent a weight gradient needs as G4 rows (d out, d h1, ds, and per layer dl
-// and dd); the training tape adds the activations they multiply (l_i, enc, the scaled audio; m_i, relu(s), relu(h1) are
-// re-formed from the gate / pre-ReLU tapes by tw_act_kernel).  Each gradient is dW[in][out] = sum_{b,t} X[in][b,t] dY[out][b,t]:
-// a GEMM whose reduction index is TIME, the column index of both operands.  tw_gemm_kernel puts time into the MFMA K slot by
-// transposing BOTH operands on their way into LDS: a thread loads eight consecutive columns of one G4 group (128 contiguous
-// bytes: 8 channels x 8 columns of fp16), transposes the 8 x 8 halves in registers and writes eight 16-byte rows
-// [channel][8 columns]; a lane's A (dY) or B (X) fragment of a 32-column K-step is then one ds_read_b128.  Split-fp16 like the
-// forward (dY.hi X.hi + dY.hi X.lo + dY.lo X.hi, fp32 accumulation).
-// Pad columns: the kernel walks valid columns only -- a column >= T is never loaded, its operand words are the constant 0 --
-// so the tape's undefined (possibly NaN) contents at [T, Tp) and the rows enc lacks past TE never meet a product.  Taps
-// t - (2 - k) d < 0 read the zero left pad of the l_i rows (IAF_LP columns, written by tg_start_kernel and copied with them).
-// Time is cut into chunks of a fixed number of 256-column tiles, chosen on the host from B and T alone so that about TW_SLABS
-// slabs exist (w_layout: one tile per chunk up to TW_SLABS / B tiles, so short clips fill the machine and long ones do not
-// drown in slab traffic); workgroup (tile, op, b x chunk) stores its fp32 partial to its own slab with
-// plain vector stores and tw_reduce_kernel sums the slabs in increasing (b, chunk) order, times scal[1]: one writer per
-// element, no atomics, bit-identical repeats.  Biases are the products with the all-ones row of `aux`, whose rows 0-2 are the
-// shifted audio (conv_start/W).
-namespace {
-constexpr int TW_SLABS = 64;        // slabs (batch elements x chunks) aimed at
-constexpr int TW_KT = 32;           // columns per LDS stage (one K-step)
-constexpr int TW_LD = TW_KT + 8;    // halves per LDS row: 80 bytes, 16 lanes of a ds_read_b128 hit 16 distinct bank quads
-constexpr int TW_MAXOP = 10;
-constexpr int TW_MAXRED = 12;
-constexpr int TW_AUXC = 32;         // channels of aux: x(t-3), x(t-2), x(t-1), 1, zeros
-
-struct TwOp {
-    const unsigned* dy;             // G4 rows of M channels (cotangent)
-    const unsigned* x;              // G4 rows of N channels (activation)
-    long long dy_bs, x_bs;          // words per batch element
-    long long out_off;              // floats inside a slab, [N][M]
-    int dy_rowlen, dy_col0, M;
-    int x_rowlen, x_col0, N;
-};
-struct TwArgs {
-    TwOp op[TW_MAXOP];
-    float* slab;
-    long long slab_stride;          // floats per slab
-    long long T;
-    int nchunk, chunk;              // chunks per batch element, columns per chunk
-};
-struct TwRed {
-    long long src_off, dst_off;     // floats inside a slab / inside grads
-    int rows, cols, src_ld, dst_ld;
-};
-struct TwRedArgs {
-    TwRed r[TW_MAXRED];
-    const float* slab;
-    long long slab_stride;
-    int nslab;
-    const float* scal;
-    float* grads;
-};
-
-// eight columns of one G4 group -> eight rows [channel][8 columns] of an LDS operand image.  r[j] = the four words of
-// column j: word i holds channels 16 (i >> 1) + 2 (i & 1) + {0, 1} (+ 4 kg + 32 s4) of the group (tb_dout_kernel's order)
-__device__ inline void tw_put(unsigned short (*img)[TW_LD], int g, int cb, const wn_u4 (&r)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            wn_u4 w;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                w[j] = p == 0 ? (r[2 * j][i] & 0xffffu) | (r[2 * j + 1][i] << 16)
-                              : (r[2 * j][i] >> 16) | (r[2 * j + 1][i] & 0xffff0000u);
-            const int c = 32 * (g >> 2) + 16 * (i >> 1) + 4 * (g & 3) + 2 * (i & 1) + p;
-            *reinterpret_cast<wn_u4*>(&img[c][8 * cb]) = w;
-        }
-}
-
-// One 128 (dY channels) x 128 (X channels) tile of one op over one chunk of one batch element, one 32-column K-step per LDS
-// stage.  Staging: thread -> (operand = tid >> 7, plane = (tid >> 6) & 1, group = (tid >> 2) & 15, column block = tid & 3);
-// the next stage's words are in flight while the MFMAs of this one run.  Waves 2 x 2, 4 x 4 MFMA tiles each.
-__global__ __launch_bounds__(256) void tw_gemm_kernel(const TwArgs a) {
-    __shared__ __attribute__((aligned(16))) unsigned short lds[2][2][128][TW_LD];     // [dY | X][hi | lo][channel][column]
-    const TwOp& o = a.op[blockIdx.y];
-    const int mtiles = (o.M + 127) / 128, ntiles = (o.N + 127) / 128;
-    if ((int)blockIdx.x >= mtiles * ntiles) return;
-    const int mt = blockIdx.x % mtiles, nt = blockIdx.x / mtiles;
-    const int b = blockIdx.z / a.nchunk, chunk = blockIdx.z % a.nchunk;
-    const long long tbeg = (long long)chunk * a.chunk, tend = a.T < tbeg + a.chunk ? a.T : tbeg + a.chunk;
-    const int nst = (int)((tend - tbeg + TW_KT - 1) / TW_KT);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 15, q = lane >> 4;
-    const int wm = wave & 1, wn = wave >> 1;
-    const int opnd = tid >> 7, plane = (tid >> 6) & 1, g = (tid >> 2) & 15, cb = tid & 3;
-
-    // this thread's row of its operand (null: a group beyond the operand's channels -> zeros)
-    const int C = opnd ? o.N : o.M, gg = (opnd ? nt : mt) * 16 + g;
-    const wn_u4* src = nullptr;
-    if (gg < C / 8)
-        src = reinterpret_cast<const wn_u4*>((opnd ? o.x : o.dy) + (size_t)b * (opnd ? o.x_bs : o.dy_bs)) +
-              (size_t)(plane * (C / 8) + gg) * (opnd ? o.x_rowlen : o.dy_rowlen) + (opnd ? o.x_col0 : o.dy_col0);
-    auto fetch = [&](int stg, wn_u4 (&r)[8]) {
-        const long long t = tbeg + (long long)stg * TW_KT + 8 * cb;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = src && t + j < tend ? src[t + j] : (wn_u4){0u, 0u, 0u, 0u};
-    };
-    // 16-row blocks of this wave that hold channels at all
-    const int na = min(4, max(0, (o.M - 128 * mt - 64 * wm + 15) / 16));
-    const int nb = min(4, max(0, (o.N - 128 * nt - 64 * wn + 15) / 16));
-
-    f4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[i][e] = (f4){0.f, 0.f, 0.f, 0.f};
-
-    wn_u4 rr[8];
-    fetch(0, rr);
-    for (int stg = 0; stg < nst; ++stg) {
-        tw_put(lds[opnd][plane], g, cb, rr);
-        __syncthreads();
-        if (stg + 1 < nst) fetch(stg + 1, rr);
-        wn_u4 ah[4], al[4], bh[4], bl[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            ah[i] = *reinterpret_cast<const wn_u4*>(&lds[0][0][64 * wm + 16 * i + n][8 * q]);
-            al[i] = *reinterpret_cast<const wn_u4*>(&lds[0][1][64 * wm + 16 * i + n][8 * q]);
-            bh[i] = *reinterpret_cast<const wn_u4*>(&lds[1][0][64 * wn + 16 * i + n][8 * q]);
-            bl[i] = *reinterpret_cast<const wn_u4*>(&lds[1][1][64 * wn + 16 * i + n][8 * q]);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (i < na)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (e < nb) acc[i][e] = mfma3(ah[i], al[i], bh[e], bl[e], acc[i][e]);
-        __syncthreads();
-    }
-
-    // slab element [x channel][dY channel]: lane (q, n) holds dY channels 4 q .. 4 q + 3 of block i, x channel n of block e
-    float* out = a.slab + (size_t)blockIdx.z * a.slab_stride + o.out_off;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int m0 = 128 * mt + 64 * wm + 16 * i + 4 * q, nn = 128 * nt + 64 * wn + 16 * e + n;
-            if (m0 < o.M && nn < o.N) *reinterpret_cast<f4*>(out + (size_t)nn * o.M + m0) = acc[i][e];
-        }
-}
-
-// grads[dst] = scal[1] * sum over the slabs, in slab order
-__global__ __launch_bounds__(256) void tw_reduce_kernel(const TwRedArgs a) {
-    const TwRed& r = a.r[blockIdx.y];
-    const long long cnt = (long long)r.rows * r.cols;
-    const float sc = a.scal[1];
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (long long)gridDim.x * 256) {
-        const int row = (int)(i / r.cols), col = (int)(i % r.cols);
-        const float* p = a.slab + r.src_off + (size_t)row * r.src_ld + col;
-        float acc = 0.f;
-        for (int s = 0; s < a.nslab; ++s) acc += p[(size_t)s * a.slab_stride];
-        a.grads[r.dst_off + (size_t)row * r.dst_ld + col] = acc * sc;
-    }
-}
-
-// accumulator-layout tape rows -> G4 activation rows of C channels, zero from column T on:
-// mode 0: relu(src) (the pre-ReLU s / out1 rows);  mode 1: sigma * tanh of a gate tape (m_i, the forward's own product)
-__global__ __launch_bounds__(256) void tw_act_kernel(const float* __restrict__ src, long long src_bs, int nmb, int hoff,
-                                                     unsigned* __restrict__ g4, long long T, long long Tp, int C, int mode) {
-    const int b = blockIdx.z, gr = blockIdx.y, NG = C / 8;
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= Tp) return;
-    const int s4 = gr >> 2, kg = gr & 3;
-    wn_u4 hw = (wn_u4){0u, 0u, 0u, 0u}, lw = hw;
-    if (t < T) {
-        const f4* p = reinterpret_cast<const f4*>(src + (size_t)b * src_bs) + ((size_t)(t >> 4) * nmb + 2 * s4) * 64 + 16 * kg + (t & 15);
-#pragma unroll
-        for (int mg = 0; mg < 2; ++mg) {
-            f4 v = p[(size_t)mg * 64];
-            if (mode == 0) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-            } else {
-                const f4 th = p[(size_t)(mg + hoff) * 64];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = v[r] * th[r];
-            }
-#pragma unroll
-            for (int rp = 0; rp < 2; ++rp) {
-                unsigned a0, a1;
-                wn_split_pair(v[2 * rp], v[2 * rp + 1], a0, a1);
-                hw[2 * mg + rp] = a0;
-                lw[2 * mg + rp] = a1;
-            }
-        }
-    }
-    unsigned* base = g4 + (size_t)b * C * Tp;
-    *reinterpret_cast<wn_u4*>(base + ((size_t)gr * Tp + t) * 4) = hw;
-    *reinterpret_cast<wn_u4*>(base + ((size_t)(NG + gr) * Tp + t) * 4) = lw;
-}
-
-// aux rows [B][32][Tp] in G4: channel k < 3 = xs(t - 3 + k) (the three taps of tg_start_kernel), channel 3 = 1, the rest 0;
-// all zero from column T on
-__global__ __launch_bounds__(256) void tw_aux_kernel(const float* __restrict__ xs, unsigned* __restrict__ g4, long long T,
-                                                     long long Tp) {
-    const int b = blockIdx.z, gr = blockIdx.y, NG = TW_AUXC / 8;
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= Tp) return;
-    wn_u4 hw = (wn_u4){0u, 0u, 0u, 0u}, lw = hw;
-    if (t < T && gr == 0) {
-        const float* xp = xs + (size_t)b * (TG_XP + Tp) + TG_XP + t;
-        unsigned a0, a1;
-        wn_split_pair(xp[-3], xp[-2], a0, a1);       // channels 0, 1 -> slot 0
-        hw[0] = a0; lw[0] = a1;
-        wn_split_pair(xp[-1], 1.0f, a0, a1);         // channels 2, 3 -> slot 1
-        hw[1] = a0; lw[1] = a1;
-    }
-    unsigned* base = g4 + (size_t)b * TW_AUXC * Tp;
-    *reinterpret_cast<wn_u4*>(base + ((size_t)gr * Tp + t) * 4) = hw;
-    *reinterpret_cast<wn_u4*>(base + ((size_t)(NG + gr) * Tp + t) * 4) = lw;
-}
-
-// d enc: G4 rows [B][Cd][RE] (scaled) -> float32 [B][TE][Cd]
-__global__ __launch_bounds__(256) void tw_denc_kernel(const unsigned* __restrict__ g4, const float* __restrict__ scal,
-                                                      float* __restrict__ out, long long TE, long long RE, int Cd) {
-    const int b = blockIdx.z, gr = blockIdx.y, NG = Cd / 8;
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= TE) return;
-    const unsigned* base = g4 + (size_t)b * Cd * RE;
-    const wn_u4 hw = *reinterpret_cast<const wn_u4*>(base + ((size_t)gr * RE + t) * 4);
-    const wn_u4 lw = *reinterpret_cast<const wn_u4*>(base + ((size_t)(NG + gr) * RE + t) * 4);
-    const float sc = scal[1];
-    const int s4 = gr >> 2, kg = gr & 3;
-    float* o = out + ((size_t)b * TE + t) * Cd;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float v0, v1;
-        wn_join_pair(hw[i], lw[i], v0, v1);
-        const int ch = 32 * s4 + 16 * (i >> 1) + 4 * kg + 2 * (i & 1);
-        o[ch] = v0 * sc;
-        o[ch + 1] = v1 * sc;
-    }
-}
-
-struct TrainLayout {
-    size_t l, enc, xs, total;       // after the plain tape's regions
-    long long RS, TE;
-};
-TrainLayout train_layout(const wn_handle* h, int B, int F, long long T) {
-    const wn_config& c = h->cfg;
-    const TapeLayout TL = tape_layout(h, B, T);
-    TrainLayout L;
-    L.RS = IAF_LP + TL.Tp;
-    L.TE = (long long)F * h->frame_shift;
-    size_t o = align_up(TL.total, 256);
-    auto carve = [&](size_t words) { size_t r = o; o += align_up(words * 4, 256); return r; };
-    L.l = carve(h->teacher.layers.size() * (size_t)B * c.width * L.RS);
-    L.enc = carve((size_t)B * c.deconv_width * (L.TE + TG_TN) + 64);      // the forward's over-read margin (t_layout)
-    L.xs = carve((size_t)B * (TG_XP + TL.Tp));
-    L.total = o;
-    return L;
-}
-
-struct WLayout {
-    long long Tp, TE, RE;
-    int c0, nchunk, chunk;
-    size_t aux, xa, xb, denc, slab, slab_floats, total;
-};
-WLayout w_layout(const wn_handle* h, int B, int F, long long T) {
-    const wn_config& c = h->cfg;
-    const int W = c.width, S = c.skip_width, G = c.gate_width, H = G / 2, Cd = c.deconv_width;
-    const BLayout BL = b_layout(h, B, T);
-    WLayout L;
-    L.Tp = BL.Tp;
-    L.TE = (long long)F * h->frame_shift;
-    L.c0 = (int)((L.TE - T) / 2);
-    L.RE = std::max<long long>(L.TE, L.c0 + L.Tp);
-    const long long ntiles = L.Tp / TG_TN, want = std::min<long long>(ntiles, std::max(1, TW_SLABS / B));
-    L.chunk = (int)((ntiles + want - 1) / want) * TG_TN;
-    L.nchunk = (int)((T + L.chunk - 1) / L.chunk);
-    size_t o = align_up(BL.total, 256);
-    auto carve = [&](size_t words) { size_t r = o; o += align_up(words * 4, 256); return r; };
-    L.aux = carve((size_t)B * TW_AUXC * L.Tp);
-    L.xa = carve((size_t)B * std::max(H, S) * L.Tp);
-    L.xb = carve((size_t)B * S * L.Tp);
-    L.denc = carve(h->teacher.denc_ok ? (size_t)B * Cd * L.RE : 0);
-    const size_t layer = (size_t)H * (W + S) + (size_t)TW_AUXC * (W + S + G) + (size_t)G * (3 * W + Cd);
-    const size_t head = (size_t)BL.Kp * (S + TW_AUXC) + (size_t)S * (S + Cd + TW_AUXC);
-    const size_t tail = (size_t)S * (W + TW_AUXC) + (size_t)TW_AUXC * W;
-    L.slab_floats = std::max(layer, std::max(head, tail));
-    L.slab = carve((size_t)B * L.nchunk * L.slab_floats);
-    L.total = o;
-    return L;
-}
-
-// the gradients in one flat float32 buffer: the variables of the residual stack and head in the order weights.py lists them
-struct GradEntry {
-    std::string name;
-    size_t off;
-    int64_t shape[4];
-    int ndim;
-};
-std::vector<GradEntry> grad_table(const wn_handle* h) {
-    const wn_config& c = h->cfg;
-    const int W = c.width, S = c.skip_width, G = c.gate_width, H = G / 2, Cd = c.deconv_width, OW = c.out_width;
-    std::vector<GradEntry> t;
-    size_t off = 0;
-    auto conv = [&](const std::string& scope, int K, int cin, int cout) {
-        t.push_back({scope + "/W", off, {1, K, cin, cout}, 4});
-        off += (size_t)K * cin * cout;
-        t.push_back({scope + "/biases", off, {cout, 0, 0, 0}, 1});
-        off += cout;
-    };
-    conv("conv_start", 3, 1, W);
-    conv("skip_start", 1, W, S);
-    for (size_t i = 0; i < h->teacher.layers.size(); ++i) {
-        const std::string n = std::to_string(i + 1);
-        conv("dilated_conv_" + n, 3, W, G);
-        conv("mel_cond_" + n, 1, Cd, G);
-        conv("res_" + n, 1, H, W);
-        conv("skip_" + n, 1, H, S);
-    }
-    conv("out1", 1, S, S);
-    conv("mel_cond_out1", 1, Cd, S);
-    conv("out2", 1, S, OW);
-    return t;
-}
-size_t grad_floats(const std::vector<GradEntry>& t) { return t.back().off + (size_t)t.back().shape[0]; }
-constexpr size_t GRAD_NONE = ~(size_t)0;
-size_t grad_off(const std::vector<GradEntry>& t, const std::string& name) {
-    for (const GradEntry& e : t)
-        if (e.name == name) return e.off;
-    return GRAD_NONE;       // an unknown name: TwBatch::red records it and run() refuses to launch
-}
-
-struct TwCtx {
-    int B;
-    long long T;
-    WLayout L;
-    TrainLayout TR;
-    std::vector<GradEntry> tab;
-    // workspace (reverse pass)
-    float* scal;
-    unsigned *dout, *dh1, *ds, *dl, *dd;
-    long long RD;
-    int Kp;
-    // workspace (weight side)
-    unsigned *aux, *xa, *xb, *denc;
-    float* slab;
-    // tape
-    const float *tape_s, *tape_h1, *tape_g, *xs;
-    const unsigned *tl, *enc;
-    float* grads;
-    bool want_denc;
-};
-
-// one batch of products and the reduction of their slabs
-struct TwBatch {
-    TwArgs a{};
-    TwRedArgs r{};
-    int nop = 0, nred = 0;
-    long long used = 0;
-    int max_tiles = 0;
-    // dY (M channels, rows of rowlen) x X (N channels): returns the slab offset of the [N][M] product
-    bool bad = false;               // a table overflow or an unknown gradient name: nothing was written, run() refuses
-    long long add(const unsigned* dy, int M, long long dy_rowlen, const unsigned* x, int N, long long x_rowlen, long long x_col0) {
-        if (nop >= TW_MAXOP) { bad = true; return 0; }
-        TwOp& o = a.op[nop++];
-        o.dy = dy; o.dy_bs = (long long)M * dy_rowlen; o.dy_rowlen = (int)dy_rowlen; o.dy_col0 = 0; o.M = M;
-        o.x = x; o.x_bs = (long long)N * x_rowlen; o.x_rowlen = (int)x_rowlen; o.x_col0 = (int)x_col0; o.N = N;
-        o.out_off = used;
-        used += (long long)M * N;
-        max_tiles = std::max(max_tiles, ((M + 127) / 128) * ((N + 127) / 128));
-        return o.out_off;
-    }
-    void red(long long src_off, int rows, int cols, int src_ld, size_t dst_off, int dst_ld) {
-        if (nred >= TW_MAXRED || dst_off == GRAD_NONE) { bad = true; return; }
-        TwRed& q = r.r[nred++];
-        q.src_off = src_off; q.dst_off = (long long)dst_off; q.rows = rows; q.cols = cols; q.src_ld = src_ld; q.dst_ld = dst_ld;
-    }
-    int run(wn_handle* h, const TwCtx& w, hipStream_t st) {
-        if (bad || used > (long long)w.L.slab_floats)
-            return wn_fail(h, WN_EIO, "wn_teacher_backward_weights: internal product table overflow or unknown gradient name");
-        a.slab = w.slab; a.slab_stride = (long long)w.L.slab_floats; a.T = w.T; a.nchunk = w.L.nchunk; a.chunk = w.L.chunk;
-        hipLaunchKernelGGL(tw_gemm_kernel, dim3(max_tiles, nop, w.B * w.L.nchunk), dim3(256), 0, st, a);
-        r.slab = w.slab; r.slab_stride = a.slab_stride; r.nslab = w.B * w.L.nchunk; r.scal = w.scal; r.grads = w.grads;
-        int most = 0;
-        for (int i = 0; i < nred; ++i) most = std::max(most, r.r[i].rows * r.r[i].cols);
-        hipLaunchKernelGGL(tw_reduce_kernel, dim3(std::min(1024, (most + 255) / 256), nred), dim3(256), 0, st, r);
-        WN_HIP(h, hipGetLastError());
-        return WN_OK;
-    }
-};
-
-// in-place accumulation of W^T dY into the d enc rows (tg_gemm_kernel, RS epilogue with residual rows only)
-void tw_denc_gemm(wn_handle* h, const TwCtx& w, const TeacherGemmPack& g, const unsigned* dy, int C, long long rowlen,
-                  hipStream_t st) {
-    const int Cd = h->cfg.deconv_width;
-    TgArgs a{};
-    a.wp = reinterpret_cast<const unsigned*>(h->d_blob + g.w_off);
-    a.bias = h->d_blob + g.b_off;
-    a.inv_scale = g.inv_scale;
-    a.nks = g.nks;
-    a.T = w.T;
-    a.og4 = w.denc; a.og4_bstride = (long long)Cd * w.L.RE; a.og4_rowlen = (int)w.L.RE; a.og4_col0 = w.L.c0; a.og4_ng = Cd / 8;
-    a.seg[0].base = dy; a.seg[0].bstride = (long long)C * rowlen; a.seg[0].rowlen = (int)rowlen; a.seg[0].col0 = 0;
-    a.seg[0].nks = C / 32; a.seg[0].ng = C / 8; a.seg[0].kind = TG_SRC_G4;
-    a.nseg = 1;
-    a.res_mtiles = g.mtiles;
-    tg_launch<TG_EPI_RS>(a, g.mtiles, w.B, w.L.Tp, st);
-}
-
-int tw_aux(wn_handle* h, const TwCtx& w, hipStream_t st) {
-    const long long Tp = w.L.Tp;
-    hipLaunchKernelGGL(tw_aux_kernel, dim3((unsigned)(Tp / 256), TW_AUXC / 8, w.B), dim3(256), 0, st, w.xs, w.aux, w.T, Tp);
-    if (w.want_denc) WN_HIP(h, hipMemsetAsync(w.denc, 0, (size_t)w.B * h->cfg.deconv_width * w.L.RE * 4, st));
-    return WN_OK;
-}
-
-// stage 0 (d h1 is complete): relu(h1) rows;  stage 1 (ds is complete): the head's products
-int tw_head(wn_handle* h, const TwCtx& w, hipStream_t st, int stage) {
-    const wn_config& c = h->cfg;
-    const int S = c.skip_width, Cd = c.deconv_width, OW = c.out_width, Kp = w.Kp;
-    const long long Tp = w.L.Tp;
-    const dim3 ga((unsigned)(Tp / 256), S / 8, w.B);
-    if (stage == 0) {
-        hipLaunchKernelGGL(tw_act_kernel, ga, dim3(256), 0, st, w.tape_h1, (long long)S * Tp, S / 16, 0, w.xa, w.T, Tp, S, 0);
-        return WN_OK;
-    }
-    hipLaunchKernelGGL(tw_act_kernel, ga, dim3(256), 0, st, w.tape_s, (long long)S * Tp, S / 16, 0, w.xb, w.T, Tp, S, 0);
-    TwBatch k;
-    const long long o2w = k.add(w.dout, Kp, Tp, w.xa, S, Tp, 0);
-    const long long o2b = k.add(w.dout, Kp, Tp, w.aux, TW_AUXC, Tp, 0);
-    const long long o1w = k.add(w.dh1, S, Tp, w.xb, S, Tp, 0);
-    const long long c1w = k.add(w.dh1, S, Tp, w.enc, Cd, w.L.TE, w.L.c0);
-    const long long o1b = k.add(w.dh1, S, Tp, w.aux, TW_AUXC, Tp, 0);
-    k.red(o2w, S, OW, Kp, grad_off(w.tab, "out2/W"), OW);
-    k.red(o2b + 3 * Kp, 1, OW, Kp, grad_off(w.tab, "out2/biases"), OW);
-    k.red(o1w, S, S, S, grad_off(w.tab, "out1/W"), S);
-    k.red(c1w, Cd, S, S, grad_off(w.tab, "mel_cond_out1/W"), S);
-    k.red(o1b + 3 * S, 1, S, S, grad_off(w.tab, "out1/biases"), S);
-    k.red(o1b + 3 * S, 1, S, S, grad_off(w.tab, "mel_cond_out1/biases"), S);
-    if (int rc = k.run(h, w, st)) return rc;
-    if (w.want_denc) tw_denc_gemm(h, w, h->teacher.cond_out1_t, w.dh1, S, Tp, st);
-    return WN_OK;
-}
-
-int tw_layer(wn_handle* h, const TwCtx& w, size_t li, hipStream_t st) {
-    const wn_config& c = h->cfg;
-    const int W = c.width, S = c.skip_width, G = c.gate_width, H = G / 2, Cd = c.deconv_width;
-    const long long Tp = w.L.Tp, RS = w.TR.RS;
-    const TeacherLayerPack& tl = h->teacher.layers[li];
-    const std::string n = std::to_string(li + 1);
-    // m_i = sigma * tanh of the gate tape
-    hipLaunchKernelGGL(tw_act_kernel, dim3((unsigned)(Tp / 256), H / 8, w.B), dim3(256), 0, st,
-                       w.tape_g + li * (size_t)w.B * G * Tp, (long long)G * Tp, G / 16, H / 16, w.xa, w.T, Tp, H, 1);
-    const unsigned* l = w.tl + li * (size_t)w.B * W * RS;
-    TwBatch k;
-    const long long rw = k.add(w.dl, W, Tp, w.xa, H, Tp, 0);
-    const long long sw = k.add(w.ds, S, Tp, w.xa, H, Tp, 0);
-    const long long rb = k.add(w.dl, W, Tp, w.aux, TW_AUXC, Tp, 0);
-    const long long sb = k.add(w.ds, S, Tp, w.aux, TW_AUXC, Tp, 0);
-    long long dw[3];
-    for (int tap = 0; tap < 3; ++tap) dw[tap] = k.add(w.dd, G, w.RD, l, W, RS, IAF_LP - (long long)(2 - tap) * tl.dilation);
-    const long long cw = k.add(w.dd, G, w.RD, w.enc, Cd, w.L.TE, w.L.c0);
-    const long long db = k.add(w.dd, G, w.RD, w.aux, TW_AUXC, Tp, 0);
-    k.red(rw, H, W, W, grad_off(w.tab, "res_" + n + "/W"), W);
-    k.red(sw, H, S, S, grad_off(w.tab, "skip_" + n + "/W"), S);
-    k.red(rb + 3 * W, 1, W, W, grad_off(w.tab, "res_" + n + "/biases"), W);
-    k.red(sb + 3 * S, 1, S, S, grad_off(w.tab, "skip_" + n + "/biases"), S);
-    for (int tap = 0; tap < 3; ++tap)
-        k.red(dw[tap], W, G, G, grad_off(w.tab, "dilated_conv_" + n + "/W") + (size_t)tap * W * G, G);
-    k.red(cw, Cd, G, G, grad_off(w.tab, "mel_cond_" + n + "/W"), G);
-    k.red(db + 3 * G, 1, G, G, grad_off(w.tab, "dilated_conv_" + n + "/biases"), G);
-    k.red(db + 3 * G, 1, G, G, grad_off(w.tab, "mel_cond_" + n + "/biases"), G);
-    if (int rc = k.run(h, w, st)) return rc;
-    if (w.want_denc) tw_denc_gemm(h, w, tl.cond_t, w.dd, G, w.RD, st);
-    return WN_OK;
-}
-
-// dl = d l_0: skip_start and conv_start
-int tw_tail(wn_handle* h, const TwCtx& w, hipStream_t st) {
-    const wn_config& c = h->cfg;
-    const int W = c.width, S = c.skip_width;
-    const long long Tp = w.L.Tp, RS = w.TR.RS;
-    TwBatch k;
-    const long long sw = k.add(w.ds, S, Tp, w.tl, W, RS, IAF_LP);
-    const long long sb = k.add(w.ds, S, Tp, w.aux, TW_AUXC, Tp, 0);
-    const long long cs = k.add(w.dl, W, Tp, w.aux, TW_AUXC, Tp, 0);
-    k.red(sw, W, S, S, grad_off(w.tab, "skip_start/W"), S);
-    k.red(sb + 3 * S, 1, S, S, grad_off(w.tab, "skip_start/biases"), S);
-    k.red(cs, 3, W, W, grad_off(w.tab, "conv_start/W"), W);
-    k.red(cs + 3 * W, 1, W, W, grad_off(w.tab, "conv_start/biases"), W);
-    return k.run(h, w, st);
-}
-
-// what the weight-gradient calls refuse beyond tb_check
-int tw_check(wn_handle* h, const char* fn) {
-    if (int rc = tb_check(h, fn)) return rc;
-    if (h->cfg.use_weight_norm)
-        return wn_fail(h, WN_EINVAL, "%s: weight-norm teacher: the gradients of W_V / W_g are not implemented", fn);
-    return WN_OK;
-}
-}  // namespace
-
-extern "C" int wn_teacher_grad_count(const wn_handle* h) {
-    if (!h || !h->finalized || h->cfg.kind != WN_KIND_TEACHER) return 0;
-    return (int)grad_table(h).size();
-}
-
-extern "C" int wn_teacher_grad_info(const wn_handle* h, int i, char* name, size_t name_cap, int64_t* offset, int64_t* shape4,
-                                    int* ndim) {
-    if (!h || !h->finalized || h->cfg.kind != WN_KIND_TEACHER)
-        return wn_fail(h, WN_EINVAL, "wn_teacher_grad_info: needs a finalized teacher handle");
-    const std::vector<GradEntry> t = grad_table(h);
-    if (i < 0 || i >= (int)t.size() || !name || !offset || !shape4 || !ndim || name_cap <= t[i].name.size())
-        return wn_fail(h, WN_EINVAL, "wn_teacher_grad_info: bad argument (index %d of %zu)", i, t.size());
-    memcpy(name, t[i].name.c_str(), t[i].name.size() + 1);
-    *offset = (int64_t)t[i].off;
-    for (int k = 0; k < 4; ++k) shape4[k] = t[i].shape[k];
-    *ndim = t[i].ndim;
-    return WN_OK;
-}
-
-extern "C" size_t wn_teacher_grad_floats(const wn_handle* h) {
-    if (!h || !h->finalized || h->cfg.kind != WN_KIND_TEACHER) return 0;
-    return grad_floats(grad_table(h));
-}
-
-// the work calls' refusals (tw_check) without a message: the size queries return 0 for what they would refuse
-static bool tw_supported(const wn_handle* h) {
-    return h && h->finalized && h->cfg.kind == WN_KIND_TEACHER && h->cfg.loss_type != WN_LOSS_CE && !h->cfg.use_mu_law &&
-           !h->cfg.use_weight_norm && h->teacher.vjp_ok;
-}
-
-extern "C" size_t wn_teacher_train_tape_bytes(const wn_handle* h, int B, int F, int64_t T) {
-    if (!tw_supported(h) || B < 1 || F < 1 || T < 1) return 0;
-    return train_layout(h, B, F, T).total;
-}
-
-extern "C" size_t wn_teacher_backward_weights_workspace_bytes(const wn_handle* h, int B, int F, int64_t T) {
-    if (!tw_supported(h) || B < 1 || F < 1 || T < 1) return 0;
-    return w_layout(h, B, F, T).total;
-}
-
-extern "C" int wn_teacher_forward_train_tape(wn_handle* h, const float* wav, const float* mel, int B, int F, int64_t T,
-                                             float* out_params, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes,
-                                             void* stream) {
-    const char* fn = "wn_teacher_forward_train_tape";
-    if (int rc = tw_check(h, fn)) return rc;
-    if (int rc = tg_forward_check(h, fn, wav, mel, B, F, T, out_params, ws)) return rc;
-    if (!tape) return wn_fail(h, WN_EINVAL, "%s: bad argument (tape)", fn);
-    const TapeLayout TL = tape_layout(h, B, T);
-    const TrainLayout TR = train_layout(h, B, F, T);
-    if (tape_bytes < TR.total) return wn_fail(h, WN_ENOMEM, "%s: tape %zu < %zu bytes", fn, tape_bytes, TR.total);
-    const WnWork work(h);
-    char* tb = reinterpret_cast<char*>(tape);
-    TbHead hd;
-    const uint64_t ser = h->teacher.serial;
-    hd.w[0] = TB_MAGIC_TRAIN; hd.w[1] = (unsigned)ser; hd.w[2] = (unsigned)(ser >> 32); hd.w[3] = (unsigned)B;
-    hd.w[4] = (unsigned)T; hd.w[5] = (unsigned)((uint64_t)T >> 32); hd.w[6] = (unsigned)h->teacher.layers.size();
-    hd.w[7] = (unsigned)F;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(tb_header_kernel, dim3(1), dim3(64), 0, st, hd, reinterpret_cast<unsigned*>(tb));
-    const int rc = tg_forward(h, fn, wav, mel, B, F, T, out_params, ws, ws_bytes, reinterpret_cast<float*>(tb + TL.s),
-                              reinterpret_cast<float*>(tb + TL.h1), reinterpret_cast<float*>(tb + TL.g), stream,
-                              reinterpret_cast<unsigned*>(tb + TR.l), reinterpret_cast<float*>(tb + TR.enc),
-                              reinterpret_cast<float*>(tb + TR.xs));
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_tape_mu);
-    g_tapes[tape] = TapeRec{ser, B, (long long)T, F};
-    return WN_OK;
-}
-
-extern "C" int wn_teacher_backward_weights(wn_handle* h, const void* tape, size_t tape_bytes, const float* d_out_params, int B,
-                                           int F, int64_t T, float* grads, size_t grads_floats, float* d_encoding, float* d_wav,
-                                           void* ws, size_t ws_bytes, void* stream) {
-    const char* fn = "wn_teacher_backward_weights";
-    if (int rc = tw_check(h, fn)) return rc;
-    if (B < 1 || F < 1 || T < 1 || !tape || !d_out_params || !grads || !ws) return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
-    int tape_F = 0;
-    if (int rc = tb_tape_check(h, fn, tape, tape_bytes, B, T, &tape_F)) return rc;
-    if (tape_F == 0)
-        return wn_fail(h, WN_EINVAL, "%s: a plain tape of wn_teacher_forward_tape holds no layer inputs and no conditioning; "
-                       "the weight gradients need a tape of wn_teacher_forward_train_tape", fn);
-    if (tape_F != F) return wn_fail(h, WN_EINVAL, "%s: the tape holds F = %d mel frames, not %d", fn, tape_F, F);
-    TwCtx w;
-    w.TR = train_layout(h, B, F, T);
-    if (tape_bytes < w.TR.total)
-        return wn_fail(h, WN_EINVAL, "%s: a tape of %zu bytes cannot hold the training tape of B = %d, F = %d, T = %lld "
-                       "(%zu bytes)", fn, tape_bytes, B, F, (long long)T, w.TR.total);
-    w.tab = grad_table(h);
-    if (grads_floats < grad_floats(w.tab))
-        return wn_fail(h, WN_ENOMEM, "%s: grads holds %zu floats, the gradients need %zu", fn, grads_floats, grad_floats(w.tab));
-    if (d_encoding && !h->teacher.denc_ok)
-        return wn_fail(h, WN_EINVAL, "%s: d_encoding needs deconv_width %d to be a multiple of 64", fn, h->cfg.deconv_width);
-    w.L = w_layout(h, B, F, T);
-    if ((long long)B * w.L.nchunk > 65535) return wn_fail(h, WN_EINVAL, "%s: B = %d needs more than 65535 slabs", fn, B);
-    if (ws_bytes < w.L.total) return wn_fail(h, WN_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, w.L.total);
-    const WnWork work(h);
-    const TapeLayout TL = tape_layout(h, B, T);
-    const BLayout BL = b_layout(h, B, T);
-    char* base = reinterpret_cast<char*>(ws);
-    const char* tb = reinterpret_cast<const char*>(tape);
-    w.B = B; w.T = T;
-    w.scal = reinterpret_cast<float*>(base + BL.scal);
-    w.dout = reinterpret_cast<unsigned*>(base + BL.dout);
-    w.dh1 = reinterpret_cast<unsigned*>(base + BL.dh1);
-    w.ds = reinterpret_cast<unsigned*>(base + BL.ds);
-    w.dl = reinterpret_cast<unsigned*>(base + BL.dl);
-    w.dd = reinterpret_cast<unsigned*>(base + BL.dd);
-    w.RD = BL.RD; w.Kp = BL.Kp;
-    w.aux = reinterpret_cast<unsigned*>(base + w.L.aux);
-    w.xa = reinterpret_cast<unsigned*>(base + w.L.xa);
-    w.xb = reinterpret_cast<unsigned*>(base + w.L.xb);
-    w.denc = reinterpret_cast<unsigned*>(base + w.L.denc);
-    w.slab = reinterpret_cast<float*>(base + w.L.slab);
-    w.tape_s = reinterpret_cast<const float*>(tb + TL.s);
-    w.tape_h1 = reinterpret_cast<const float*>(tb + TL.h1);
-    w.tape_g = reinterpret_cast<const float*>(tb + TL.g);
-    w.tl = reinterpret_cast<const unsigned*>(tb + w.TR.l);
-    w.enc = reinterpret_cast<const unsigned*>(tb + w.TR.enc);
-    w.xs = reinterpret_cast<const float*>(tb + w.TR.xs);
-    w.grads = grads;
-    w.want_denc = d_encoding != nullptr;
-    if (int rc = tb_reverse(h, tape, d_out_params, B, T, d_wav, ws, stream, &w)) return rc;
-    if (d_encoding) {
-        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-        const int Cd = h->cfg.deconv_width;
-        hipLaunchKernelGGL(tw_denc_kernel, dim3((unsigned)((w.L.TE + 255) / 256), Cd / 8, B), dim3(256), 0, st, w.denc, w.scal,
-                           d_encoding, w.L.TE, w.L.RE, Cd);
-        WN_HIP(h, hipGetLastError());
-    }
     return WN_OK;
 }

@@ -1,7 +1,7 @@
 """torch.autograd Functions of the distillation losses.
 
 Each forward calls the HIP kernels the no-grad loss path calls (so the values are the same bits) and each backward the
-gradient kernels of csrc/wn_teacher.hip / wn_distill.hip.  The loss Functions return the raw float64 sums of their kernels;
+gradient kernels of csrc/wn_teacher_bwd.hip / wn_distill.hip.  The loss Functions return the raw float64 sums of their kernels;
 the scalar arithmetic of the losses stays in torch, so a backward receives d loss / d sums as a device tensor and hands it
 to the kernels without a host read.  The teacher is frozen: TeacherForward differentiates with respect to the audio only.
 """

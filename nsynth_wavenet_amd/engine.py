@@ -38,6 +38,7 @@ class Engine(object):
         self._ar_stream = None
         self._ar_groups = None              # per-group streams / queue states of ar_generate(streams=G)
         self._last_ws = None
+        self._train_frames = {}           # tape address -> mel frames of the training tapes written through this handle
         self.range_fallbacks = 0          # calls re-run on the fp32 form because they left the fp16 range
         self._finalized = False
         self.precision = precision or cfg.default_precision()
@@ -372,19 +373,30 @@ class Engine(object):
                                                            _ptr(ws), ws.numel(), self._stream()))
         return dwav
 
+    # ---- gradient tables of the weight-gradient calls: one flat float32 buffer, one entry per TF variable ----
+    def _grad_table(self, count, info, *prefix_args):
+        """[(tf variable name, float offset, TF shape)] from a wn_*_grad_count / wn_*_grad_info pair (prefix_args: what the
+        pair takes between the handle and the index)."""
+        out = []
+        name = ctypes.create_string_buffer(160)
+        off, nd, shape = ctypes.c_int64(0), ctypes.c_int(0), (ctypes.c_int64 * 4)()
+        for i in range(int(count(self._h, *prefix_args))):
+            self._check(info(self._h, *prefix_args, i, name, 160, ctypes.byref(off), shape, ctypes.byref(nd)))
+            out.append((name.value.decode(), int(off.value), tuple(int(shape[k]) for k in range(nd.value))))
+        return out
+
+    @staticmethod
+    def _grad_views(flat, table):
+        """{tf name: view of the flat buffer in the TF shape}"""
+        return {name: flat[off:off + int(np.prod(shape))].view(shape) for name, off, shape in table}
+
     # ---- weight gradients of the teacher (DESIGN.md 14) ----
     def teacher_train_tape_bytes(self, B, F, T):
         return int(self.lib.wn_teacher_train_tape_bytes(self._h, int(B), int(F), int(T)))
 
     def teacher_grad_table(self):
         """[(tf variable name, float offset, TF shape)] of the flat gradient buffer, in the library's fixed order."""
-        out = []
-        name = ctypes.create_string_buffer(128)
-        off, nd, shape = ctypes.c_int64(0), ctypes.c_int(0), (ctypes.c_int64 * 4)()
-        for i in range(int(self.lib.wn_teacher_grad_count(self._h))):
-            self._check(self.lib.wn_teacher_grad_info(self._h, i, name, 128, ctypes.byref(off), shape, ctypes.byref(nd)))
-            out.append((name.value.decode(), int(off.value), tuple(int(shape[k]) for k in range(nd.value))))
-        return out
+        return self._grad_table(self.lib.wn_teacher_grad_count, self.lib.wn_teacher_grad_info)
 
     def teacher_forward_train_tape(self, wav, mel):
         """teacher_forward (bit-identical out_params) that also returns the TRAINING tape teacher_backward_weights reads: the
@@ -405,10 +417,9 @@ class Engine(object):
             self._check(self.lib.wn_teacher_forward_train_tape(self._h, _ptr(wav), _ptr(mel), B, F, T, _ptr(out), _ptr(tape),
                                                                tape.numel(), _ptr(ws), ws.numel(), self._stream()))
         # the library identifies a tape by its address (a copy is refused), so the frame count is kept by address too
-        frames = self.__dict__.setdefault('_train_frames', {})
-        if len(frames) >= 256:
-            frames.clear()
-        frames[tape.data_ptr()] = F
+        if len(self._train_frames) >= 256:
+            self._train_frames.clear()
+        self._train_frames[tape.data_ptr()] = F
         return out, tape
 
     def teacher_backward_weights(self, tape, d_out_params, n_frames=None, want_encoding=False, want_wav=False):
@@ -418,7 +429,7 @@ class Engine(object):
         g = self._dev(d_out_params)
         if g.dim() != 3 or (self.kind == 'teacher' and int(g.shape[2]) != cfg.teacher_out_width(self.hp)):
             raise ValueError('teacher_backward_weights: d_out_params must be [B,T,{}]'.format(cfg.teacher_out_width(self.hp)))
-        F = int(n_frames if n_frames is not None else self.__dict__.get('_train_frames', {}).get(tape.data_ptr(), 0))
+        F = int(n_frames if n_frames is not None else self._train_frames.get(tape.data_ptr(), 0))
         if F < 1:
             raise ValueError('teacher_backward_weights: pass n_frames for a tape this engine object did not write')
         B, T = int(g.shape[0]), int(g.shape[1])
@@ -432,10 +443,7 @@ class Engine(object):
                              dtype=torch.uint8, device=self.device)
             self._check(self.lib.wn_teacher_backward_weights(self._h, _ptr(tape), tape.numel(), _ptr(g), B, F, T, _ptr(flat), n,
                                                              _ptr(denc), _ptr(dwav), _ptr(ws), ws.numel(), self._stream()))
-            grads = {}
-            for name, off, shape in self.teacher_grad_table():
-                cnt = int(np.prod(shape))
-                grads[name] = flat[off:off + cnt].view(shape)
+            grads = self._grad_views(flat, self.teacher_grad_table())
         return {'grads': grads, 'flat_grads': flat[:n], 'd_encoding': denc, 'd_wav': dwav}
 
     # ---- reverse pass of the upsampler ----
@@ -443,14 +451,7 @@ class Engine(object):
         """[(tf variable name, float offset, TF shape)] of deconv_backward's flat gradient buffer: per layer
         '<scope/>trans_conv_j/kernel' [1,K,Cout,Cin], then '<scope/>trans_conv_j/bias' [Cout].  Empty for a stack the call
         refuses."""
-        sc = scope.encode()
-        out = []
-        name = ctypes.create_string_buffer(160)
-        off, nd, shape = ctypes.c_int64(0), ctypes.c_int(0), (ctypes.c_int64 * 4)()
-        for i in range(int(self.lib.wn_deconv_grad_count(self._h, sc))):
-            self._check(self.lib.wn_deconv_grad_info(self._h, sc, i, name, 160, ctypes.byref(off), shape, ctypes.byref(nd)))
-            out.append((name.value.decode(), int(off.value), tuple(int(shape[k]) for k in range(nd.value))))
-        return out
+        return self._grad_table(self.lib.wn_deconv_grad_count, self.lib.wn_deconv_grad_info, scope.encode())
 
     def deconv_backward(self, mel, d_encoding, scope=''):
         """VJP of deconv(mel, scope) with respect to the stack's variables: mel [B,F,n_mel] and a cotangent d_encoding
@@ -472,9 +473,7 @@ class Engine(object):
                              device=self.device)
             self._check(self.lib.wn_deconv_backward(self._h, sc, _ptr(mel), _ptr(g), B, F, _ptr(flat), n, _ptr(ws), ws.numel(),
                                                     self._stream()))
-            grads = {}
-            for name, off, shape in self.deconv_grad_table(scope):
-                grads[name] = flat[off:off + int(np.prod(shape))].view(shape)
+            grads = self._grad_views(flat, self.deconv_grad_table(scope))
         return {'grads': grads, 'flat_grads': flat[:n]}
 
     def _fac(self, fac):

@@ -1,5 +1,5 @@
 """GPU tests of the distillation-loss gradients: ParallelWavenet.calculate_loss and its terms differentiated
-with respect to the student's x, mean_tot and scale_tot -- the teacher's tape forward and input VJP (csrc/wn_teacher.hip)
+with respect to the student's x, mean_tot and scale_tot -- the teacher's tape forward and input VJP (csrc/wn_teacher_bwd.hip)
 and the loss gradients (csrc/wn_distill.hip) -- against the float64 torch restatement of the reference's graph
 (tests/distill_oracle64.py, pinned to tests/golden/ref_distill.npz by tests/test_distill_grad_oracle.py)."""
 import json

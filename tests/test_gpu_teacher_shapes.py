@@ -1,5 +1,5 @@
 """GPU tests of the full-sequence teacher off its 256-column tile ("Pad columns"): the forward, the tape and the
-input VJP wn_teacher_backward_input (csrc/wn_teacher.hip) at lengths T that are no multiple of TG_TN = 256, where every
+input VJP wn_teacher_backward_input (csrc/wn_teacher_bwd.hip) at lengths T that are no multiple of TG_TN = 256, where every
 workspace row carries pad columns [T, Tp) that the GEMM kernel computes without a guard and the anti-causal taps of the reverse
 pass read.  Everything is held to the float64 oracle of tests/distill_oracle64.py on the small teacher of
 tests/golden/ref_distill.npz (width 128, skip 64, gate 128, 7 layers, largest dilation 4, frame shift 200), at the bars the
@@ -204,7 +204,7 @@ def _edge_cotangent(c, kind):
 @pytest.mark.parametrize('shape', EDGE_SHAPES, ids=_sid)
 def test_cotangents_at_the_edges(cases, eng, shape, kind):
     """Cotangents that are non-zero only at t = T - 1, only at t = 0 (out_params(0) sees no audio -- the input is shifted right
-    -- so the gradient is exactly zero), only in batch row 0, and nowhere (the m == 0 branch of tb_scale_kernel)."""
+    -- so the gradient is exactly zero), only in batch row 0, and nowhere (the m == 0 branch of wn_scale_kernel)."""
     c = cases(shape)
     g = _edge_cotangent(c, kind)
     d_wav = eng.teacher_backward_input(c.tape, g)

@@ -1,5 +1,5 @@
 """GPU tests of the teacher's weight gradients: wn_teacher_forward_train_tape and wn_teacher_backward_weights
-(csrc/wn_teacher.hip) behind Engine.teacher_forward_train_tape / teacher_backward_weights and Wavenet.loss_and_weight_grads.
+(csrc/wn_teacher_wgrad.hip) behind Engine.teacher_forward_train_tape / teacher_backward_weights and Wavenet.loss_and_weight_grads.
 Everything is held to the float64 oracle of tests/distill_oracle64.py with requires_grad on its weight tensors (pinned by
 tests/test_teacher_wgrad_oracle.py), on the small teacher of tests/golden/ref_distill.npz (width 128, skip 64, 7 layers,
 largest dilation 4, frame shift 200) at shapes and per-row seeded inputs of tests/test_gpu_teacher_shapes.py, whose seeds
