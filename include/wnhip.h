@@ -472,6 +472,53 @@ WN_API size_t wn_deconv_backward_workspace_bytes(const wn_handle* h, const char*
 WN_API int wn_deconv_backward(wn_handle* h, const char* scope, const float* mel, const float* d_enc, int B, int F, float* grads,
                               size_t grads_floats, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Teacher training step on the device ----
+ *
+ * wn_teacher_set_weights rewrites the packed weights of a FINALIZED teacher handle in place from fp32 masters that live on
+ * the device.  `params` is a flat buffer in the layout of the gradient table (offsets and TF shapes of wn_teacher_grad_info,
+ * wn_teacher_grad_floats floats); `up_params` is the upsampler's, in the layout of wn_deconv_grad_info with scope "", or NULL:
+ * the upsampler's packs then stay as they are.  After the call every byte of the handle's device blob that depends on those
+ * variables equals what wn_finalize of a fresh handle would have uploaded for the same values: the row-major matrices, summed
+ * and composite biases and A-fragment copies of the autoregressive step, every split-fp16 GEMM pack of the full-sequence
+ * forward and its transposes, the upsampler's fp32 fragments, bias, split-fp16 pack, phase-group pack and the transposed
+ * planes of its reverse pass.  No device pointer of the handle changes and nothing is allocated.
+ *
+ * No weight and no packed word crosses to the host.  The scale of every split pack needs the largest magnitude of its
+ * source: those maxima are reduced on the device into `ws` and READ BACK (a few hundred floats), so the call SYNCHRONISES
+ * `stream` once, midway; the kernels behind that point are enqueued and the call returns without waiting for them, so
+ * `params` and `up_params` must stay unchanged until `stream` has passed the call (later work on `stream` is ordered).
+ *
+ * The call takes the handle exclusively, like the switches ("Concurrency"): WN_ESTATE while a work call of another thread is
+ * inside the library.  Work enqueued earlier on OTHER streams that reads the handle's weights must have finished: that is
+ * the caller's job (work on `stream` itself is ordered).  The handle's tape serial changes: a tape or training tape written
+ * before the call is refused afterwards by wn_teacher_backward_input and wn_teacher_backward_weights.
+ * If the call fails with WN_EIO after it has begun to launch, the handle's weights are undefined (partly old, partly new)
+ * until a later call succeeds; the tape serial has changed by then, so no older tape is accepted.
+ * WN_EINVAL: a student handle; a handle the weight-gradient calls refuse (mu-law, ce, weight norm); use_resize_conv with a
+ * non-NULL up_params; float counts that are not the tables'; a workspace below wn_teacher_set_weights_workspace_bytes (0 for
+ * a handle the call refuses).  WN_ESTATE: a handle that is not finalized. */
+WN_API size_t wn_teacher_set_weights_workspace_bytes(const wn_handle* h);
+WN_API int wn_teacher_set_weights(wn_handle* h, const float* params, size_t params_floats, const float* up_params,
+                                  size_t up_floats, void* ws, size_t ws_bytes, void* stream);
+
+/* Sum of squares of n device floats in double: a fixed-order two-stage reduction without atomics (a repeated call gives the
+ * same bits).  acc[0] (one device double) is written, or added to when `accumulate` is non-zero, so that the buffers of the
+ * residual stack and of the upsampler chain into one global norm.  Needs no handle; errors through wn_last_error(NULL).
+ * Asynchronous on `stream`. */
+WN_API size_t wn_grad_sumsq_workspace_bytes(size_t n);
+WN_API int wn_grad_sumsq(const float* g, size_t n, double* acc, int accumulate, void* ws, size_t ws_bytes, void* stream);
+
+/* One step of TensorFlow's Adam on n device floats, with the shadow of tf.train.ExponentialMovingAverage:
+ *   m <- beta1 m + (1 - beta1) g',  v <- beta2 v + (1 - beta2) g'^2,  p <- p - lr_t m / (sqrt(v) + eps),
+ *   ema <- ema - (1 - ema_decay_t) (ema - p)   on the updated p (ema may be NULL).
+ * lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t) is formed by the caller.  With sumsq non-NULL (one device double, the squared
+ * global norm of wn_grad_sumsq), g' = g clip_norm / max(sqrt(sumsq[0]), clip_norm) -- tf.clip_by_global_norm, read on the
+ * device -- otherwise g' = g.  Each element is formed in double from the fp32 state and every stored value is rounded once.
+ * 16-byte accesses with a scalar tail (all scalar when a pointer is off the 16-byte grid); any n >= 1.  Needs no handle;
+ * asynchronous on `stream`. */
+WN_API int wn_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr_t, float beta1,
+                            float beta2, float eps, float ema_decay_t, const double* sumsq, float clip_norm, void* stream);
+
 /* Gradient of L = fac[0] sums[0] + fac[1] sums[1] of wn_distill_mol_xent (same draws: `noise`, or Philox under `seed`):
  * d_out_params [B,T,3 mol_mix], d_mean_tot and d_scale_tot [B,T] (through x = rl scale_tot + mean_tot, and 1 / scale_tot of
  * the log scale_tot sum).  Overwrites its outputs; no workspace. */

@@ -1109,20 +1109,26 @@ int wn_pack_ar(wn_handle* h, std::vector<float>& blob) {
     return WN_OK;
 }
 
-int wn_ar_post_upload(wn_handle* h) {
+// composite matrices wcomp_j and the [wd_j | wcomp_j] fragments of every layer from the row-major matrices in the blob, enqueued
+// on `st`: after the upload (wn_finalize) and after an in-place re-pack (wn_teacher_set_weights)
+void wn_ar_compose(wn_handle* h, hipStream_t st) {
     const wn_config& c = h->cfg;
     const int W = c.width, G = c.gate_width, H = G / 2, K = 3 * W + c.deconv_width;
     for (size_t j = 1; j < h->ar.layers.size(); ++j) {
         const ArLayerPack& lp = h->ar.layers[j];
         const ArLayerPack& pv = h->ar.layers[j - 1];
-        hipLaunchKernelGGL(ar_compose_kernel, dim3((H + 255) / 256, G), dim3(256), 0, 0, h->d_blob + lp.wd_off,
+        hipLaunchKernelGGL(ar_compose_kernel, dim3((H + 255) / 256, G), dim3(256), 0, st, h->d_blob + lp.wd_off,
                            h->d_blob + pv.wrs_off, h->d_blob + lp.wcomp_off, G, W, H, K);
         if (lp.wdc_b_off) {
             const size_t total = (size_t)G * (K + H);
-            hipLaunchKernelGGL(ar_frag_dc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0,
+            hipLaunchKernelGGL(ar_frag_dc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
                                h->d_blob + lp.wd_off, h->d_blob + lp.wcomp_off, h->d_blob + lp.wdc_b_off, G, K, H);
         }
     }
+}
+
+int wn_ar_post_upload(wn_handle* h) {
+    wn_ar_compose(h, 0);
     WN_HIP(h, hipDeviceSynchronize());
     WN_HIP(h, hipGetLastError());
     return WN_OK;

@@ -442,6 +442,8 @@ int wn_pack_deconv_bwd(wn_handle* h, std::vector<float>& blob) {
     return WN_OK;
 }
 
+std::vector<WnGradEntry> wn_deconv_grad_table(const wn_handle* h, int si) { return dgrad_table(h, si); }
+
 extern "C" int wn_deconv_grad_count(const wn_handle* h, const char* scope) {
     int si;
     if (bwd_check(h, "wn_deconv_grad_count", scope, &si, true)) return 0;

@@ -229,6 +229,8 @@ struct WnGradEntry {
 // floats of the buffer: the entries are contiguous and the last one is a bias [shape[0]]
 inline size_t wn_grad_floats(const std::vector<WnGradEntry>& t) { return t.empty() ? 0 : t.back().off + (size_t)t.back().shape[0]; }
 // entry i for the *_grad_info calls (message prefix fn); refuses a bad index, a null output or a short name buffer
+std::vector<WnGradEntry> wn_teacher_grad_table(const wn_handle* h);        // wn_teacher_wgrad.hip: residual stack and head
+std::vector<WnGradEntry> wn_deconv_grad_table(const wn_handle* h, int si);   // wn_deconv_bwd.hip: stack si
 int wn_grad_info(const wn_handle* h, const char* fn, const std::vector<WnGradEntry>& t, int i, char* name, size_t name_cap,
                  int64_t* offset, int64_t* shape4, int* ndim);
 
@@ -343,5 +345,6 @@ size_t wn_iaf_workspace_bytes(const wn_handle* h, int B, int F, int form = WN_FO
 size_t wn_ar_workspace_bytes(const wn_handle* h, int B, int F);
 void wn_ar_release(wn_handle* h);
 int wn_ar_post_upload(wn_handle* h);   // device-side part of the AR packing (composite matrices)
+void wn_ar_compose(wn_handle* h, hipStream_t st);   // ... its launches alone, on a stream (wn_train.hip re-packs in place)
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

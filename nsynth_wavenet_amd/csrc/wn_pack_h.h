@@ -1,14 +1,16 @@
-// Host-side packing helpers for the split-fp16 paths (wn_iaf_h.hip, wn_deconv.hip).
+// Packing helpers for the split-fp16 paths (wn_iaf_h.hip, wn_deconv.hip): host loops at wn_finalize; the roundings are
+// integer code shared with the device-side re-pack (wn_train.hip), which must produce the same bits.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 
-// ---- host-side fp32 -> fp16 (round to nearest even), independent of host _Float16 support ----
-inline uint16_t f2h(float f) {
+// ---- fp32 -> fp16 (round to nearest even) in integer code, independent of host _Float16 support ----
+__host__ __device__ inline uint16_t f2h(float f) {
     uint32_t x;
-    memcpy(&x, &f, 4);
+    __builtin_memcpy(&x, &f, 4);
     const uint32_t sign = (x >> 16) & 0x8000u;
     x &= 0x7fffffffu;
     if (x >= 0x47800000u) return (uint16_t)(sign | (x > 0x7f800000u ? 0x7e00u : 0x7c00u));   // inf / nan
@@ -28,7 +30,7 @@ inline uint16_t f2h(float f) {
     if (rem > 0x1000u || (rem == 0x1000u && (m & 1))) ++m;
     return (uint16_t)(sign | m);
 }
-inline float h2f(uint16_t h) {
+__host__ __device__ inline float h2f(uint16_t h) {
     const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
     uint32_t e = (h >> 10) & 0x1f, m = h & 0x3ffu, x;
     if (e == 0) {
@@ -41,8 +43,13 @@ inline float h2f(uint16_t h) {
     } else if (e == 31) x = sign | 0x7f800000u | (m << 13);
     else x = sign | ((e + 112) << 23) | (m << 13);
     float f;
-    memcpy(&f, &x, 4);
+    __builtin_memcpy(&f, &x, 4);
     return f;
+}
+// half of plane 0 (hi) or 1 (lo = what hi leaves of v) of the split
+__host__ __device__ inline uint16_t split_half(float v, int plane) {
+    const uint16_t hi = f2h(v);
+    return plane == 0 ? hi : f2h(v - h2f(hi));
 }
 
 // power-of-two prescale so that the lo halves of small weights stay normal fp16 numbers
@@ -64,11 +71,7 @@ void pack_afrag(unsigned* dst, F wk) {
             for (int i = 0; i < 4; ++i) {
                 const int i16 = lane & 15, kg = lane >> 4;
                 uint16_t hh[2];
-                for (int p = 0; p < 2; ++p) {
-                    const float v = wk(2 * i + p, kg, i16);
-                    const uint16_t hi = f2h(v);
-                    hh[p] = plane == 0 ? hi : f2h(v - h2f(hi));
-                }
+                for (int p = 0; p < 2; ++p) hh[p] = split_half(wk(2 * i + p, kg, i16), plane);
                 dst[(plane * 64 + lane) * 4 + i] = (uint32_t)hh[0] | ((uint32_t)hh[1] << 16);
             }
 }

@@ -487,6 +487,8 @@ static int tw_check(wn_handle* h, const char* fn) {
     return WN_OK;
 }
 
+std::vector<WnGradEntry> wn_teacher_grad_table(const wn_handle* h) { return grad_table(h); }
+
 extern "C" int wn_teacher_grad_count(const wn_handle* h) {
     if (!h || !h->finalized || h->cfg.kind != WN_KIND_TEACHER) return 0;
     return (int)grad_table(h).size();

@@ -1,0 +1,592 @@
+// Teacher training step on the device: the optimiser kernels (global gradient norm, Adam with the EMA
+// shadow) and wn_teacher_set_weights, which rewrites a finalized handle's packed weights in place from device-resident
+// fp32 masters.
+//
+// The re-pack repeats wn_finalize's host packs (wn_pack_ar, wn_pack_teacher, wn_pack_deconv, wn_pack_deconv_bwd) with the
+// same index maps, one thread per packed word: first the plain fp32 matrices and biases of the AR pack, which are also the
+// sources of the teacher's GEMM packs, then -- once the absolute maxima of the split packs have come back and pick_scale has
+// chosen their scales -- every split-fp16 pack.  The roundings are wn_pack_h.h's integer code on both sides, the composite
+// bias accumulates in double in the host's order, the composite matrices come from wn_finalize's own kernels (wn_ar_compose), so every word equals what a fresh handle would have uploaded.
+#include <atomic>
+
+#include "wn_internal.h"
+#include "wn_pack_h.h"
+
+namespace {
+
+constexpr int TR_NT = 256;
+inline unsigned tr_blocks(size_t n) { return (unsigned)((n + TR_NT - 1) / TR_NT); }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// optimiser
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int SS_MAXBLK = 1024;
+inline int ss_blocks(size_t n) { return (int)std::min<size_t>(SS_MAXBLK, (n + 8 * TR_NT - 1) / (8 * TR_NT)); }
+
+// fixed tree over the block's 256 partial sums
+__device__ inline double ss_block_sum(double v, double* red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = TR_NT / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// stage 1: block b sums g[i]^2 over i = b * 256 + tid + k * gridDim.x * 256, in that order
+__global__ __launch_bounds__(TR_NT) void tr_sumsq1_kernel(const float* __restrict__ g, size_t n, double* __restrict__ part) {
+    __shared__ double red[TR_NT];
+    double acc = 0.0;
+    for (size_t i = (size_t)blockIdx.x * TR_NT + threadIdx.x; i < n; i += (size_t)gridDim.x * TR_NT) {
+        const double v = (double)g[i];
+        acc += v * v;
+    }
+    const double s = ss_block_sum(acc, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+// stage 2: one block over the partial sums
+__global__ __launch_bounds__(TR_NT) void tr_sumsq2_kernel(const double* __restrict__ part, int nb, double* __restrict__ acc,
+                                                          int accumulate) {
+    __shared__ double red[TR_NT];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < nb; i += TR_NT) a += part[i];
+    const double s = ss_block_sum(a, red);
+    if (threadIdx.x == 0) acc[0] = accumulate ? acc[0] + s : s;
+}
+
+struct AdamArgs {
+    float* p;
+    const float* g;
+    float *m, *v, *ema;
+    size_t n;
+    float lr_t, beta1, beta2, eps, ema_decay_t, clip_norm;
+    const double* sumsq;
+};
+// One element: the update is formed in double from the fp32 state and every stored value is rounded once; p and the shadow
+// use the STORED m, v and p, as TensorFlow's kernels do.
+__device__ inline void adam_one(const AdamArgs& a, double gs, float& p, float g, float& m, float& v, float* ema) {
+    const double gh = (double)g * gs;
+    const double b1 = (double)a.beta1, b2 = (double)a.beta2;
+    m = (float)(b1 * (double)m + (1.0 - b1) * gh);
+    v = (float)(b2 * (double)v + (1.0 - b2) * gh * gh);
+    p = (float)((double)p - (double)a.lr_t * (double)m / (sqrt((double)v) + (double)a.eps));
+    if (ema) *ema = (float)((double)*ema - (1.0 - (double)a.ema_decay_t) * ((double)*ema - (double)p));
+}
+// VEC: 16-byte accesses over the first n / 4 quads and a scalar tail; otherwise (a pointer off the 16-byte grid) scalar
+template <bool VEC>
+__global__ __launch_bounds__(TR_NT) void tr_adam_kernel(AdamArgs a) {
+    // tf.clip_by_global_norm: g * clip / max(||g||, clip)
+    double gs = 1.0;
+    if (a.sumsq) gs = (double)a.clip_norm / fmax(sqrt(a.sumsq[0]), (double)a.clip_norm);
+    const size_t i = (size_t)blockIdx.x * TR_NT + threadIdx.x;
+    const size_t nq = VEC ? a.n / 4 : 0;
+    if (VEC && i < nq) {
+        f4 p = reinterpret_cast<f4*>(a.p)[i], m = reinterpret_cast<f4*>(a.m)[i], v = reinterpret_cast<f4*>(a.v)[i];
+        const f4 g = reinterpret_cast<const f4*>(a.g)[i];
+        f4 e = a.ema ? reinterpret_cast<f4*>(a.ema)[i] : f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float pk = p[k], mk = m[k], vk = v[k], ek = e[k];
+            adam_one(a, gs, pk, g[k], mk, vk, a.ema ? &ek : nullptr);
+            p[k] = pk; m[k] = mk; v[k] = vk; e[k] = ek;
+        }
+        reinterpret_cast<f4*>(a.p)[i] = p;
+        reinterpret_cast<f4*>(a.m)[i] = m;
+        reinterpret_cast<f4*>(a.v)[i] = v;
+        if (a.ema) reinterpret_cast<f4*>(a.ema)[i] = e;
+    }
+    // tail: the first threads of the grid take the elements behind the last quad
+    const size_t t = 4 * nq + i;
+    if (i < a.n - 4 * nq && (!VEC || i < 4)) adam_one(a, gs, a.p[t], a.g[t], a.m[t], a.v[t], a.ema ? a.ema + t : nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// re-pack: plain fp32 parts
+// ---------------------------------------------------------------------------------------------------------------------
+// HWIO [1,1,cin,cout] -> dst[o * ld + col0 + ci] (pack_T of wn_pack_ar); cin = 1, ld = 1 is a plain copy of cout floats
+struct ScatterArgs {
+    const float* src;
+    float* dst;
+    int cin, cout, ld, col0;
+};
+__global__ __launch_bounds__(TR_NT) void tr_scatter_kernel(ScatterArgs a) {
+    const size_t i = (size_t)blockIdx.x * TR_NT + threadIdx.x;
+    if (i >= (size_t)a.cin * a.cout) return;
+    const int o = (int)(i / a.cin), ci = (int)(i % a.cin);
+    a.dst[(size_t)o * a.ld + a.col0 + ci] = a.src[(size_t)ci * a.cout + o];
+}
+// dst = x + y: the summed biases
+__global__ __launch_bounds__(TR_NT) void tr_add_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                       float* __restrict__ dst, int n) {
+    const int i = blockIdx.x * TR_NT + threadIdx.x;
+    if (i < n) dst[i] = __fadd_rn(x[i], y[i]);
+}
+// composite bias bm = bd + Wd[tap t] . bres_{j-1}, in double in the host's order (a float x float product is exact in double)
+__global__ __launch_bounds__(TR_NT) void tr_bm_kernel(const float* __restrict__ wd, const float* __restrict__ bd,
+                                                      const float* __restrict__ brs_prev, float* __restrict__ bm, int G, int W,
+                                                      int K) {
+    const int o = blockIdx.x * TR_NT + threadIdx.x;
+    if (o >= G) return;
+    double acc = bd[o];
+    for (int cc = 0; cc < W; ++cc) acc += (double)wd[(size_t)o * K + 2 * W + cc] * (double)brs_prev[cc];
+    bm[o] = (float)acc;
+}
+// A-fragment order [row block][k-group of 16][lane][4] of a row-major [rows][KA] matrix; rows beyond `rows` are zero (frag of
+// wn_pack_ar)
+__global__ __launch_bounds__(TR_NT) void tr_frag_kernel(const float* __restrict__ a, float* __restrict__ dst, int rows, int KA) {
+    const int nks4 = KA / 16, mbs = (rows + 15) / 16;
+    const size_t i = (size_t)blockIdx.x * TR_NT + threadIdx.x;
+    if (i >= (size_t)mbs * nks4 * 256) return;
+    const int jj = i & 3, lane = (i >> 2) & 63;
+    const size_t blk = i >> 8;
+    const int k4 = (int)(blk % nks4), mb = (int)(blk / nks4);
+    const int row = 16 * mb + (lane & 15), k = 16 * k4 + 4 * jj + (lane >> 4);
+    dst[i] = row >= rows ? 0.f : a[(size_t)row * KA + k];
+}
+// fp32 A fragments of one transposed-conv layer: [S][tap, block][mb][lane][4] of W [K][cout][cin] (wn_pack_deconv)
+__global__ __launch_bounds__(TR_NT) void tr_deconv_frag_kernel(const float* __restrict__ W, float* __restrict__ P, int S, int taps,
+                                                               int cin, int cout) {
+    const int nmb = cout / 16, cblk = cin / 16, nks4 = taps * cblk;
+    const size_t i = (size_t)blockIdx.x * TR_NT + threadIdx.x;
+    if (i >= (size_t)S * nks4 * nmb * 256) return;
+    const int jj = i & 3, lane = (i >> 2) & 63;
+    size_t rest = i >> 8;
+    const int mb = (int)(rest % nmb);
+    rest /= nmb;
+    const int ks4 = (int)(rest % nks4), r = (int)(rest / nks4);
+    const int tap = ks4 / cblk, c4 = ks4 % cblk;
+    const int co = 16 * mb + (lane & 15), ci = 16 * c4 + 4 * jj + (lane >> 4), k = S * tap + r;
+    P[i] = W[((size_t)k * cout + co) * cin + ci];
+}
+
+// largest |x| of n floats, as the bit pattern of a non-negative float (exact in any order); NaNs are passed over like
+// std::max does in pick_scale.  *out starts at zero.
+__global__ __launch_bounds__(TR_NT) void tr_absmax_kernel(const float* __restrict__ x, size_t n, unsigned* __restrict__ out) {
+    float mx = 0.f;
+    for (size_t i = (size_t)blockIdx.x * TR_NT + threadIdx.x; i < n; i += (size_t)gridDim.x * TR_NT) {
+        const float v = fabsf(x[i]);
+        if (v > mx) mx = v;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if ((threadIdx.x & 63) == 0 && mx > 0.f) atomicMax(out, __float_as_uint(mx));
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// re-pack: split-fp16 packs.  One thread per packed word of pack_afrag's layout [fragment][plane][lane][4].
+// ---------------------------------------------------------------------------------------------------------------------
+enum { ROW_IDENT = 0, ROW_GATE = 1 };              // rowfn of wn_pack_teacher
+enum { SRC_DIRECT = 0, SRC_T = 1, SRC_GATE_T = 2 };   // the matrix as stored, a transposed column range, gate_t's tap-major form
+__device__ inline int tr_row(int kind, int M, int H, int i) {
+    if (kind == ROW_IDENT) return i < M ? i : -1;
+    const int j = i / 64, lr = i % 64;
+    return lr < 32 ? 32 * j + lr : H + 32 * j + lr - 32;
+}
+struct TileArgs {
+    const float* src;      // row-major matrix inside the blob
+    unsigned* dst;
+    float sc;
+    int ld, nks, mtiles;
+    int rowkind, M, H;     // ROW_*: rows of the pack (ident) / half gate width (gate)
+    int srckind;           // SRC_*
+    int R, c0;             // SRC_T: rows of the source, first column taken
+    int G, W;              // SRC_GATE_T
+};
+__device__ inline float tile_elem(const TileArgs& a, int row, int col) {
+    if (a.srckind == SRC_DIRECT) return a.src[(size_t)row * a.ld + col];
+    if (a.srckind == SRC_T) return col < a.R ? a.src[(size_t)col * a.ld + a.c0 + row] : 0.f;
+    const int k = col / a.G, g = col % a.G;
+    return a.src[(size_t)g * a.ld + k * a.W + row];
+}
+__global__ __launch_bounds__(TR_NT) void tr_tile_kernel(TileArgs a) {
+    const size_t i = (size_t)blockIdx.x * TR_NT + threadIdx.x;
+    if (i >= (size_t)a.mtiles * a.nks * 4 * 512) return;
+    const int ii = i & 3, lane = (i >> 2) & 63, plane = (i >> 8) & 1;
+    const size_t f = i >> 9;
+    const int mb = f & 3, ks = (int)((f >> 2) % a.nks), mt = (int)((f >> 2) / a.nks);
+    const int i16 = lane & 15, kg = lane >> 4;
+    const int row = tr_row(a.rowkind, a.M, a.H, mt * 64 + 16 * mb + i16);
+    uint16_t hh[2];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const int e = 2 * ii + p;
+        const float v = row < 0 ? 0.f : __fmul_rn(a.sc, tile_elem(a, row, 32 * ks + 16 * (e >> 2) + 4 * kg + (e & 3)));
+        hh[p] = split_half(v, plane);
+    }
+    a.dst[i] = (uint32_t)hh[0] | ((uint32_t)hh[1] << 16);
+}
+// tile-ordered bias of a TeacherGemmPack
+__global__ __launch_bounds__(TR_NT) void tr_tile_bias_kernel(const float* __restrict__ bsrc, float* __restrict__ dst, int n,
+                                                             int rowkind, int M, int H) {
+    const int i = blockIdx.x * TR_NT + threadIdx.x;
+    if (i >= n) return;
+    const int row = tr_row(rowkind, M, H, i);
+    dst[i] = row < 0 ? 0.f : bsrc[row];
+}
+
+// split-fp16 A fragments of one transposed-conv layer, W [K][cout][cin]: the phase pack [S][ks][mb] (nph = 0) or the row
+// groups of ONE phase group [sub][input block][tap][mb8] (nph = 4 | 2 phases from p0) of wn_pack_deconv
+struct DeconvHArgs {
+    const float* W;
+    unsigned* dst;
+    float sc;
+    int S, taps, cin, cout, pL;
+    int nph, p0, nsub;
+};
+__global__ __launch_bounds__(TR_NT) void tr_deconv_h_kernel(DeconvHArgs a) {
+    const size_t i = (size_t)blockIdx.x * TR_NT + threadIdx.x;
+    const int ii = i & 3, lane = (i >> 2) & 63, plane = (i >> 8) & 1;
+    const int i16 = lane & 15, kg = lane >> 4;
+    size_t f = i >> 9;
+    uint16_t hh[2];
+    if (a.nph == 0) {
+        const int nb16 = a.cin / 16, nks = a.taps * nb16 / 2, nmb = a.cout / 16;
+        if (f >= (size_t)a.S * nks * nmb) return;
+        const int mb = (int)(f % nmb);
+        f /= nmb;
+        const int ks = (int)(f % nks), r = (int)(f / nks);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int e = 2 * ii + p, g = 2 * ks + (e >> 2), tap = g / nb16, blk = g - tap * nb16;
+            const int ci = 16 * blk + 4 * kg + (e & 3);
+            hh[p] = split_half(__fmul_rn(a.sc, a.W[((size_t)(a.S * tap + r) * a.cout + 16 * mb + i16) * a.cin + ci]), plane);
+        }
+    } else {
+        const int nb32 = a.cin / 32;
+        if (f >= (size_t)a.nsub * nb32 * 4 * 8) return;
+        const int mb8 = f & 7, m = (f >> 3) & 3;
+        f >>= 5;
+        const int cb = (int)(f % nb32), sub = (int)(f / nb32);
+        const int ph = a.nph == 4 ? mb8 >> 1 : mb8 >> 2;
+        const int cb16 = a.nph == 4 ? 2 * sub + (mb8 & 1) : 4 * sub + (mb8 & 3);
+        const int r = (a.p0 + ph + a.pL) % a.S;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int e = 2 * ii + p;
+            const int ci = 32 * cb + 16 * (e >> 2) + 4 * kg + (e & 3);
+            hh[p] = split_half(__fmul_rn(a.sc, a.W[((size_t)(a.S * m + r) * a.cout + 16 * cb16 + i16) * a.cin + ci]), plane);
+        }
+    }
+    a.dst[i] = (uint32_t)hh[0] | ((uint32_t)hh[1] << 16);
+}
+// W^T as two planes of halves [k][ci][co] (wn_pack_deconv_bwd); one thread per pair of neighbouring co
+__global__ __launch_bounds__(TR_NT) void tr_deconv_t_kernel(const float* __restrict__ W, unsigned* __restrict__ dst, float sc, int K,
+                                                            int cin, int cout) {
+    const size_t n2 = (size_t)K * cin * cout / 2;
+    const size_t i = (size_t)blockIdx.x * TR_NT + threadIdx.x;
+    if (i >= n2) return;
+    const size_t at = 2 * i;
+    const int co = (int)(at % cout), ci = (int)((at / cout) % cin), k = (int)(at / cout / cin);
+    const float v0 = __fmul_rn(sc, W[((size_t)k * cout + co) * cin + ci]);
+    const float v1 = __fmul_rn(sc, W[((size_t)k * cout + co + 1) * cin + ci]);
+    dst[i] = (uint32_t)split_half(v0, 0) | ((uint32_t)split_half(v1, 0) << 16);
+    dst[n2 + i] = (uint32_t)split_half(v0, 1) | ((uint32_t)split_half(v1, 1) << 16);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side of the re-pack
+// ---------------------------------------------------------------------------------------------------------------------
+// The variables of the flat parameter buffer, resolved once per call from the gradient table's fixed order (grad_table of
+// wn_teacher_wgrad.hip): conv_start, skip_start, per layer dilated_conv / mel_cond / res / skip, then out1, mel_cond_out1, out2,
+// each as W then biases.
+struct ConvP {
+    const float *W, *b;
+};
+struct TeacherParams {
+    ConvP start, skip_start, out1, cond_out1, out2;
+    std::vector<ConvP> dil, cond, res, skip;
+};
+bool resolve_params(const std::vector<WnGradEntry>& tab, const float* params, size_t nl, TeacherParams& q) {
+    if (tab.size() != 2 * (5 + 4 * nl) || tab.front().name != "conv_start/W" || tab.back().name != "out2/biases") return false;
+    size_t k = 0;
+    auto next = [&]() { ConvP c{params + tab[k].off, params + tab[k + 1].off}; k += 2; return c; };
+    q.start = next();
+    q.skip_start = next();
+    for (size_t i = 0; i < nl; ++i) {
+        q.dil.push_back(next());
+        q.cond.push_back(next());
+        q.res.push_back(next());
+        q.skip.push_back(next());
+    }
+    q.out1 = next();
+    q.cond_out1 = next();
+    q.out2 = next();
+    return true;
+}
+
+// what the weight-gradient calls support (tw_supported of wn_teacher_wgrad.hip): only such a handle has a parameter layout
+bool train_supported(const wn_handle* h) {
+    const wn_config& c = h->cfg;
+    return c.kind == WN_KIND_TEACHER && c.loss_type != WN_LOSS_CE && !c.use_mu_law && !c.use_weight_norm && h->teacher.vjp_ok &&
+           wn_teacher_grad_floats(h) > 0;
+}
+
+// the absolute maxima the call reduces: three per layer and four for the head, then one per upsampler layer
+struct ScaleSlots {
+    int n_layers, n_up;
+    int wss() const { return 0; }
+    int wo1a() const { return 1; }      // out1 columns
+    int wo1b() const { return 2; }      // mel_cond_out1 columns
+    int wo2() const { return 3; }
+    int dil(int i) const { return 4 + 4 * i; }
+    int cond(int i) const { return 5 + 4 * i; }
+    int res(int i) const { return 6 + 4 * i; }
+    int skip(int i) const { return 7 + 4 * i; }
+    int up(int j) const { return 4 + 4 * n_layers + j; }
+    int total() const { return 4 + 4 * n_layers + n_up; }
+};
+ScaleSlots scale_slots(const wn_handle* h) {
+    return ScaleSlots{(int)h->ar.layers.size(), h->stacks.empty() ? 0 : (int)h->stacks[0].layers.size()};
+}
+
+std::atomic<uint64_t> g_repack_serial{1ull << 62};   // tape serials of re-packed handles: apart from wn_finalize's counter
+
+}  // namespace
+
+extern "C" size_t wn_grad_sumsq_workspace_bytes(size_t n) { return align_up((size_t)ss_blocks(std::max<size_t>(n, 1)) * sizeof(double), 256); }
+
+extern "C" int wn_grad_sumsq(const float* g, size_t n, double* acc, int accumulate, void* ws, size_t ws_bytes, void* stream) {
+    if (!g || !acc || !ws || n < 1) return wn_fail(nullptr, WN_EINVAL, "wn_grad_sumsq: bad argument");
+    if (ws_bytes < wn_grad_sumsq_workspace_bytes(n))
+        return wn_fail(nullptr, WN_EINVAL, "wn_grad_sumsq: workspace %zu < %zu bytes", ws_bytes, wn_grad_sumsq_workspace_bytes(n));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int nb = ss_blocks(n);
+    double* part = reinterpret_cast<double*>(ws);
+    hipLaunchKernelGGL(tr_sumsq1_kernel, dim3(nb), dim3(TR_NT), 0, st, g, n, part);
+    hipLaunchKernelGGL(tr_sumsq2_kernel, dim3(1), dim3(TR_NT), 0, st, part, nb, acc, accumulate);
+    WN_HIP(nullptr, hipGetLastError());
+    return WN_OK;
+}
+
+extern "C" int wn_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr_t, float beta1,
+                                float beta2, float eps, float ema_decay_t, const double* sumsq, float clip_norm, void* stream) {
+    if (!p || !g || !m || !v || n < 1) return wn_fail(nullptr, WN_EINVAL, "wn_adam_ema_step: bad argument");
+    if (sumsq && !(clip_norm > 0.f)) return wn_fail(nullptr, WN_EINVAL, "wn_adam_ema_step: clip_norm must be positive");
+    const AdamArgs a{p, g, m, v, ema, n, lr_t, beta1, beta2, eps, ema_decay_t, clip_norm, sumsq};
+    const uintptr_t bits = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (bits & 15) hipLaunchKernelGGL(tr_adam_kernel<false>, dim3(tr_blocks(n)), dim3(TR_NT), 0, st, a);
+    else hipLaunchKernelGGL(tr_adam_kernel<true>, dim3(tr_blocks(std::max<size_t>(n / 4, 4))), dim3(TR_NT), 0, st, a);
+    WN_HIP(nullptr, hipGetLastError());
+    return WN_OK;
+}
+
+extern "C" size_t wn_teacher_set_weights_workspace_bytes(const wn_handle* h) {
+    if (!h || !h->finalized || !train_supported(h)) return 0;
+    return align_up((size_t)scale_slots(h).total() * sizeof(float), 256);
+}
+
+extern "C" int wn_teacher_set_weights(wn_handle* h, const float* params, size_t params_floats, const float* up_params,
+                                      size_t up_floats, void* ws, size_t ws_bytes, void* stream) {
+    const char* fn = "wn_teacher_set_weights";
+    if (!h) return wn_fail(nullptr, WN_EINVAL, "%s: null handle", fn);
+    const wn_config& c = h->cfg;
+    if (c.kind != WN_KIND_TEACHER) return wn_fail(h, WN_EINVAL, "%s: this is a ParallelWavenet student handle; only a teacher is re-packed", fn);
+    if (!h->finalized) return wn_fail(h, WN_ESTATE, "%s: call wn_finalize first", fn);
+    if (!train_supported(h))
+        return wn_fail(h, WN_EINVAL, "%s: the handle has no parameter layout (mu-law, ce and weight-norm teachers have no weight "
+                       "gradients)", fn);
+    if (!params || !ws) return wn_fail(h, WN_EINVAL, "%s: null argument", fn);
+    const std::vector<WnGradEntry> PT = wn_teacher_grad_table(h);
+    if (params_floats != wn_grad_floats(PT))
+        return wn_fail(h, WN_EINVAL, "%s: params holds %zu floats, the layout of wn_teacher_grad_info has %zu", fn, params_floats,
+                       wn_grad_floats(PT));
+    std::vector<WnGradEntry> UT;
+    if (up_params) {
+        if (c.use_resize_conv)
+            return wn_fail(h, WN_EINVAL, "%s: use_resize_conv: the resize-conv upsampler has no parameter layout; pass no up_params", fn);
+        if (wn_deconv_grad_floats(h, "") == 0)
+            return wn_fail(h, WN_EINVAL, "%s: the upsampler has no parameter layout (wn_deconv_grad_floats is 0)", fn);
+        UT = wn_deconv_grad_table(h, 0);
+        if (up_floats != wn_grad_floats(UT) || UT.size() != 2 * h->stacks[0].layers.size())
+            return wn_fail(h, WN_EINVAL, "%s: up_params holds %zu floats, the layout of wn_deconv_grad_info has %zu", fn, up_floats,
+                           wn_grad_floats(UT));
+    }
+    const size_t need = wn_teacher_set_weights_workspace_bytes(h);
+    if (ws_bytes < need) return wn_fail(h, WN_EINVAL, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
+    WN_SWITCH(h, "wn_teacher_set_weights");
+
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int W = c.width, S = c.skip_width, G = c.gate_width, H = G / 2, Cd = c.deconv_width, OW = c.out_width, K = 3 * W + Cd;
+    float* blob = h->d_blob;
+    ArPack& A = h->ar;
+    TeacherPack& T = h->teacher;
+    const ScaleSlots SL = scale_slots(h);
+    unsigned* amax = reinterpret_cast<unsigned*>(ws);
+    auto scatter = [&](const float* src, size_t dst_off, int cin, int cout, int ld, int col0) {
+        hipLaunchKernelGGL(tr_scatter_kernel, dim3(tr_blocks((size_t)cin * cout)), dim3(TR_NT), 0, st,
+                           ScatterArgs{src, blob + dst_off, cin, cout, ld, col0});
+    };
+    auto copy = [&](const float* src, size_t dst_off, int n) { scatter(src, dst_off, 1, n, 1, 0); };
+    auto add = [&](const float* x, const float* y, size_t dst_off, int n) {
+        hipLaunchKernelGGL(tr_add_kernel, dim3(tr_blocks(n)), dim3(TR_NT), 0, st, x, y, blob + dst_off, n);
+    };
+    auto absmax = [&](const float* x, size_t n, int slot) {
+        const unsigned nb = (unsigned)std::min<size_t>(256, (n + 4 * TR_NT - 1) / (4 * TR_NT));
+        hipLaunchKernelGGL(tr_absmax_kernel, dim3(nb), dim3(TR_NT), 0, st, x, n, amax + slot);
+    };
+    auto frag = [&](size_t src_off, size_t dst_off, int rows, int Kc) {
+        const size_t total = (size_t)((rows + 15) / 16) * (Kc / 16) * 256;
+        hipLaunchKernelGGL(tr_frag_kernel, dim3(tr_blocks(total)), dim3(TR_NT), 0, st, blob + src_off, blob + dst_off, rows,
+                           Kc);
+    };
+    const size_t nl = A.layers.size();
+    TeacherParams Q;
+    if (!resolve_params(PT, params, nl, Q)) return wn_fail(h, WN_EINVAL, "%s: the parameter layout is not the model's", fn);
+    // From here on the handle changes: tapes written under the old weights are refused, also after a failure below
+    T.serial = g_repack_serial++;
+
+    // ---- 1. absolute maxima of the sources of every split pack
+    WN_HIP(h, hipMemsetAsync(amax, 0, (size_t)SL.total() * sizeof(unsigned), st));
+    absmax(Q.skip_start.W, (size_t)W * S, SL.wss());
+    absmax(Q.out1.W, (size_t)S * S, SL.wo1a());
+    absmax(Q.cond_out1.W, (size_t)Cd * S, SL.wo1b());
+    absmax(Q.out2.W, (size_t)S * OW, SL.wo2());
+    for (size_t i = 0; i < nl; ++i) {
+        absmax(Q.dil[i].W, (size_t)3 * W * G, SL.dil((int)i));
+        absmax(Q.cond[i].W, (size_t)Cd * G, SL.cond((int)i));
+        absmax(Q.res[i].W, (size_t)H * W, SL.res((int)i));
+        absmax(Q.skip[i].W, (size_t)H * S, SL.skip((int)i));
+    }
+    DeconvStackPack* sp = up_params ? &h->stacks[0] : nullptr;
+    std::vector<const float*> upW, upB;
+    if (sp)
+        for (size_t j = 0; j < sp->layers.size(); ++j) {
+            upW.push_back(up_params + UT[2 * j].off);          // kernel, then bias (dgrad_table of wn_deconv_bwd.hip)
+            upB.push_back(up_params + UT[2 * j + 1].off);
+            const DeconvLayerPack& lp = sp->layers[j];
+            absmax(upW[j], (size_t)lp.K * lp.cout * lp.cin, SL.up((int)j));
+        }
+
+    // ---- 2. the plain fp32 matrices and biases (wn_pack_ar), the composites, the fp32 fragments
+    copy(Q.start.W, A.start_off, 3 * W);
+    copy(Q.start.b, A.start_off + 3 * (size_t)W, W);
+    scatter(Q.skip_start.W, A.wss_off, W, S, W, 0);
+    copy(Q.skip_start.b, A.bss_off, S);
+    for (size_t i = 0; i < nl; ++i) {
+        ArLayerPack& lp = A.layers[i];
+        const float* wd = Q.dil[i].W;
+        for (int tap = 0; tap < 3; ++tap) scatter(wd + (size_t)tap * W * G, lp.wd_off, W, G, K, tap * W);
+        scatter(Q.cond[i].W, lp.wd_off, Cd, G, K, 3 * W);
+        add(Q.dil[i].b, Q.cond[i].b, lp.bd_off, G);
+        copy(Q.cond[i].b, lp.bc_off, G);
+        scatter(Q.res[i].W, lp.wrs_off, H, W, H, 0);
+        scatter(Q.skip[i].W, lp.wrs_off + (size_t)W * H, H, S, H, 0);
+        copy(Q.res[i].b, lp.brs_off, W);
+        copy(Q.skip[i].b, lp.brs_off + W, S);
+        if (i > 0) {
+            const ArLayerPack& pv = A.layers[i - 1];
+            hipLaunchKernelGGL(tr_bm_kernel, dim3(tr_blocks(G)), dim3(TR_NT), 0, st, blob + lp.wd_off, blob + lp.bd_off,
+                               blob + pv.brs_off, blob + lp.bm_off, G, W, K);
+        }
+    }
+    wn_ar_compose(h, st);        // composite matrices and the [wd | wcomp] fragments: wn_finalize's own launches, on this stream
+    scatter(Q.out1.W, A.wo1_off, S, S, S + Cd, 0);
+    scatter(Q.cond_out1.W, A.wo1_off, Cd, S, S + Cd, S);
+    add(Q.out1.b, Q.cond_out1.b, A.bo1_off, S);
+    copy(Q.cond_out1.b, A.bco1_off, S);
+    scatter(Q.out2.W, A.wo2_off, S, OW, S, 0);
+    copy(Q.out2.b, A.bo2_off, OW);
+    if (A.wss_b_off) {           // the batched step's A-fragment copies exist
+        frag(A.wss_off, A.wss_b_off, S, W);
+        for (size_t i = 0; i < nl; ++i) {
+            ArLayerPack& lp = A.layers[i];
+            if (i == 0) frag(lp.wd_off, lp.wd_b_off, G, K);
+            frag(lp.wrs_off, lp.wrs_b_off, W + S, H);
+            copy(blob + lp.brs_off, lp.brs_gate_off, W + S);
+            copy(blob + lp.bd_off, lp.brs_gate_off + W + S, G);
+        }
+        frag(A.wo1_off, A.wo1_b_off, S, S + Cd);
+        frag(A.wo2_off, A.wo2_b_off, OW, S);
+    }
+    if (sp)
+        for (size_t j = 0; j < sp->layers.size(); ++j) {
+            const DeconvLayerPack& lp = sp->layers[j];
+            const size_t total = (size_t)lp.S * lp.taps * (lp.cin / 16) * (lp.cout / 16) * 256;
+            hipLaunchKernelGGL(tr_deconv_frag_kernel, dim3(tr_blocks(total)), dim3(TR_NT), 0, st, upW[j], blob + lp.w_off, lp.S,
+                               lp.taps, lp.cin, lp.cout);
+            copy(upB[j], lp.b_off, lp.cout);
+        }
+
+    // ---- 3. the maxima come back (the call's one read-back: it synchronises the stream); pick_scale on the host
+    std::vector<float> mx(SL.total());
+    WN_HIP(h, hipMemcpyAsync(mx.data(), amax, mx.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+    WN_HIP(h, hipStreamSynchronize(st));
+    auto scale_of = [&](std::initializer_list<int> slots) {
+        float m = 0.f;
+        for (int s : slots) m = std::max(m, mx[s]);
+        return pick_scale(&m, 1);
+    };
+
+    // ---- 4. the split-fp16 packs (wn_pack_teacher, wn_pack_deconv, wn_pack_deconv_bwd)
+    auto tile = [&](TeacherGemmPack& g, float sc, size_t src_off, int ld, int rowkind, int M, int srckind, int R, int c0) {
+        g.inv_scale = 1.0f / sc;
+        TileArgs a{blob + src_off, reinterpret_cast<unsigned*>(blob + g.w_off), sc, ld, g.nks, g.mtiles, rowkind, M, H, srckind, R, c0, G, W};
+        hipLaunchKernelGGL(tr_tile_kernel, dim3(tr_blocks((size_t)g.mtiles * g.nks * 4 * 512)), dim3(TR_NT), 0, st, a);
+    };
+    auto tile_bias = [&](const TeacherGemmPack& g, size_t b_off, int rowkind, int M) {
+        hipLaunchKernelGGL(tr_tile_bias_kernel, dim3(tr_blocks((size_t)g.mtiles * 64)), dim3(TR_NT), 0, st, blob + b_off,
+                           blob + g.b_off, g.mtiles * 64, rowkind, M, H);
+    };
+    const float s_wss = scale_of({SL.wss()}), s_wo1 = scale_of({SL.wo1a(), SL.wo1b()}), s_wo2 = scale_of({SL.wo2()});
+    tile(T.skip_start, s_wss, A.wss_off, W, ROW_IDENT, S, SRC_DIRECT, 0, 0);
+    tile_bias(T.skip_start, A.bss_off, ROW_IDENT, S);
+    tile(T.out1, s_wo1, A.wo1_off, S + Cd, ROW_IDENT, S, SRC_DIRECT, 0, 0);
+    tile_bias(T.out1, A.bo1_off, ROW_IDENT, S);
+    tile(T.out2, s_wo2, A.wo2_off, S, ROW_IDENT, OW, SRC_DIRECT, 0, 0);
+    tile_bias(T.out2, A.bo2_off, ROW_IDENT, OW);
+    for (size_t i = 0; i < nl; ++i) {
+        const ArLayerPack& lp = A.layers[i];
+        TeacherLayerPack& tl = T.layers[i];
+        const int li = (int)i;
+        tile(tl.gate, scale_of({SL.dil(li), SL.cond(li)}), lp.wd_off, K, ROW_GATE, G, SRC_DIRECT, 0, 0);
+        tile_bias(tl.gate, lp.bd_off, ROW_GATE, G);
+        tile(tl.rs, scale_of({SL.res(li), SL.skip(li)}), lp.wrs_off, H, ROW_IDENT, W + S, SRC_DIRECT, 0, 0);
+        tile_bias(tl.rs, lp.brs_off, ROW_IDENT, W + S);
+    }
+    if (T.vjp_ok) {              // the transposed packs: zero bias, as packed
+        tile(T.skip_start_t, s_wss, A.wss_off, W, ROW_IDENT, W, SRC_T, S, 0);
+        tile(T.out1_t, scale_of({SL.wo1a()}), A.wo1_off, S + Cd, ROW_IDENT, S, SRC_T, S, 0);
+        tile(T.out2_t, s_wo2, A.wo2_off, S, ROW_IDENT, S, SRC_T, OW, 0);
+        for (size_t i = 0; i < nl; ++i) {
+            const ArLayerPack& lp = A.layers[i];
+            TeacherLayerPack& tl = T.layers[i];
+            const int li = (int)i;
+            tile(tl.rs_t, scale_of({SL.res(li), SL.skip(li)}), lp.wrs_off, H, ROW_IDENT, H, SRC_T, W + S, 0);
+            tile(tl.gate_t, scale_of({SL.dil(li)}), lp.wd_off, K, ROW_IDENT, W, SRC_GATE_T, 0, 0);
+            if (T.denc_ok) tile(tl.cond_t, scale_of({SL.cond(li)}), lp.wd_off, K, ROW_IDENT, Cd, SRC_T, G, 3 * W);
+        }
+        if (T.denc_ok) tile(T.cond_out1_t, scale_of({SL.wo1b()}), A.wo1_off, S + Cd, ROW_IDENT, Cd, SRC_T, S, S);
+    }
+    if (sp)
+        for (size_t j = 0; j < sp->layers.size(); ++j) {
+            DeconvLayerPack& lp = sp->layers[j];
+            const float sc = scale_of({SL.up((int)j)});
+            if (lp.w_off_h) {
+                lp.inv_scale_h = 1.0f / sc;
+                const size_t words = (size_t)lp.S * (lp.taps * (lp.cin / 16) / 2) * (lp.cout / 16) * 512;
+                hipLaunchKernelGGL(tr_deconv_h_kernel, dim3(tr_blocks(words)), dim3(TR_NT), 0, st,
+                                   DeconvHArgs{upW[j], reinterpret_cast<unsigned*>(blob + lp.w_off_h), sc, lp.S, lp.taps, lp.cin, lp.cout,
+                                               lp.pL, 0, 0, 0});
+            }
+            if (lp.w_off_pg) {
+                const int nb32 = lp.cin / 32;
+                for (int g = 0; g < lp.pg_n; ++g) {
+                    const int nsub = lp.pg_nph[g] == 4 ? lp.cout / 32 : lp.cout / 64;
+                    const size_t words = (size_t)nsub * nb32 * 4 * 8 * 512;
+                    unsigned* dst = reinterpret_cast<unsigned*>(blob + lp.w_off_pg) + (size_t)lp.pg_rg0[g] * nb32 * 4 * 8 * 512;
+                    hipLaunchKernelGGL(tr_deconv_h_kernel, dim3(tr_blocks(words)), dim3(TR_NT), 0, st,
+                                       DeconvHArgs{upW[j], dst, sc, lp.S, lp.taps, lp.cin, lp.cout, lp.pL, lp.pg_nph[g], lp.pg_p0[g], nsub});
+                }
+            }
+            if (lp.wt_off) {
+                lp.wt_inv_scale = 1.0f / sc;
+                const size_t n2 = (size_t)lp.K * lp.cin * lp.cout / 2;
+                hipLaunchKernelGGL(tr_deconv_t_kernel, dim3(tr_blocks(n2)), dim3(TR_NT), 0, st, upW[j],
+                                   reinterpret_cast<unsigned*>(blob + lp.wt_off), sc, lp.K, lp.cin, lp.cout);
+            }
+        }
+    WN_HIP(h, hipGetLastError());
+    return WN_OK;
+}

@@ -476,6 +476,44 @@ class Engine(object):
             grads = self._grad_views(flat, self.deconv_grad_table(scope))
         return {'grads': grads, 'flat_grads': flat[:n]}
 
+    # ---- training step on the device (the trainer is train.TeacherTrainer) ----
+    def teacher_set_weights(self, params, up_params=None):
+        """Re-pack this finalized teacher's weights in place from flat float32 device buffers: `params` in the layout of
+        teacher_grad_table(), `up_params` in that of deconv_grad_table('') or None (the upsampler keeps its weights).  The
+        handle then holds what load_weights of the same values would have built.  Synchronises the current stream once (the
+        scales' maxima are read back); tapes written before the call are refused afterwards.  A switch: RuntimeError
+        (WN_ESTATE) while another thread's work call is inside the library."""
+        _flat_f32('teacher_set_weights', 'params', params)
+        if up_params is not None:
+            _flat_f32('teacher_set_weights', 'up_params', up_params)
+        with torch.cuda.device(self.device):
+            nb = int(self.lib.wn_teacher_set_weights_workspace_bytes(self._h))
+            ws = torch.empty(max(nb, 256), dtype=torch.uint8, device=self.device)
+            self._check(self.lib.wn_teacher_set_weights(self._h, _ptr(params), params.numel(), _ptr(up_params),
+                                                        up_params.numel() if up_params is not None else 0, _ptr(ws),
+                                                        nb if nb else ws.numel(), self._stream()))
+        self._train_frames.clear()
+        return self
+
+    def teacher_grad_floats(self):
+        """floats of the flat buffer teacher_grad_table() lays out"""
+        return int(self.lib.wn_teacher_grad_floats(self._h))
+
+    def deconv_grad_floats(self, scope=''):
+        """floats of the flat buffer deconv_grad_table(scope) lays out (0 for a stack deconv_backward refuses)"""
+        return int(self.lib.wn_deconv_grad_floats(self._h, scope.encode()))
+
+    def grad_sumsq(self, g, acc=None, accumulate=False):
+        """Sum of squares of the flat float32 device tensor g as one float64 device value (fixed order, no atomics): written
+        into `acc` ([1] float64) or added to it with accumulate.  Returns acc."""
+        return grad_sumsq(g, acc, accumulate)
+
+    def adam_ema_step(self, p, g, m, v, ema, lr_t, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay_t=0.0, sumsq=None,
+                      clip_norm=1.0):
+        """One Adam step in place on flat float32 device tensors, with the EMA shadow (or None) and, with `sumsq` (the [1]
+        float64 of grad_sumsq), tf.clip_by_global_norm(., clip_norm) applied to g on the device."""
+        return adam_ema_step(p, g, m, v, ema, lr_t, beta1, beta2, eps, ema_decay_t, sumsq, clip_norm)
+
     def _fac(self, fac):
         fac = fac.to(device=self.device, dtype=torch.float64).contiguous()
         if fac.numel() != 2:
@@ -794,3 +832,53 @@ def power_loss_grad(pred, orig, fac):
                                           d.stride(0), _ptr(ws), ws.numel(),
                                           ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     return d
+
+
+def _flat_f32(what, name, t, n=None):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous()):
+        raise ValueError('{}: {} must be a flat contiguous float32 device tensor'.format(what, name))
+    if n is not None and t.numel() != n:
+        raise ValueError('{}: {} holds {} values, not {}'.format(what, name, t.numel(), n))
+    return t
+
+
+def grad_sumsq(g, acc=None, accumulate=False):
+    """wn_grad_sumsq: the sum of squares of a flat float32 device tensor in float64, as a [1] float64 device tensor (`acc`,
+    or a new one); accumulate adds to acc instead of overwriting it."""
+    lib = _lib.load()
+    g = _flat_f32('grad_sumsq', 'g', g)
+    if g.numel() < 1:
+        raise ValueError('grad_sumsq: g is empty')
+    dev = g.device
+    if acc is None:
+        if accumulate:
+            raise ValueError('grad_sumsq: accumulate needs acc')
+        acc = torch.empty(1, dtype=torch.float64, device=dev)
+    elif not (acc.is_cuda and acc.dtype == torch.float64 and acc.numel() == 1):
+        raise ValueError('grad_sumsq: acc must be one float64 value on the device')
+    with torch.cuda.device(dev):
+        nb = int(lib.wn_grad_sumsq_workspace_bytes(g.numel()))
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        _lib.check(lib.wn_grad_sumsq(_ptr(g), g.numel(), _ptr(acc), 1 if accumulate else 0, _ptr(ws), nb,
+                                     ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return acc
+
+
+def adam_ema_step(p, g, m, v, ema, lr_t, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay_t=0.0, sumsq=None, clip_norm=1.0):
+    """wn_adam_ema_step in place on flat float32 device tensors of equal length (ema may be None; sumsq: None or the [1]
+    float64 squared global norm, which turns the clip on)."""
+    lib = _lib.load()
+    p = _flat_f32('adam_ema_step', 'p', p)
+    n = p.numel()
+    if n < 1:
+        raise ValueError('adam_ema_step: p is empty')
+    for name, t in (('g', g), ('m', m), ('v', v)) + ((('ema', ema),) if ema is not None else ()):
+        _flat_f32('adam_ema_step', name, t, n)
+    if sumsq is not None and not (sumsq.is_cuda and sumsq.dtype == torch.float64 and sumsq.numel() == 1):
+        raise ValueError('adam_ema_step: sumsq must be one float64 value on the device')
+    dev = p.device
+    with torch.cuda.device(dev):
+        _lib.check(lib.wn_adam_ema_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), n, float(lr_t), float(beta1),
+                                        float(beta2), float(eps), float(ema_decay_t), _ptr(sumsq), float(clip_norm),
+                                        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return p
