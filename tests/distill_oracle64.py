@@ -103,15 +103,20 @@ def _softplus(v):
     return Fn.softplus(v, beta=1, threshold=50)
 
 
-def mol_log_probs(par, x):
-    """loss_func.py:22-63: par [...,3M], x [...] -> log p [...]"""
+def mol_log_probs(par, x, stable=False):
+    """loss_func.py:22-63: par [...,3M], x [...] -> log p [...].  stable: the bin mass as the product
+    sigma(a) sigma(-b) (1 - e^-(a-b)) with a - b = 2 inv_s / Q taken directly -- the same function as the reference's
+    difference of two sigmoids, which in float64 loses about 1e-16 / mass of relative accuracy where both are near 1."""
     M = par.shape[-1] // 3
     lg, mean, ls = par[..., :M], par[..., M:2 * M], torch.clamp(par[..., 2 * M:], min=-7.0)
     inv = torch.exp(-ls)
     x = x[..., None]
     c = x - mean
     plus, mn = inv * (c + 1.0 / Q), inv * (c - 1.0 / Q)
-    delta = torch.sigmoid(plus) - torch.sigmoid(mn)
+    if stable:
+        delta = torch.sigmoid(plus) * torch.sigmoid(-mn) * (-torch.expm1(-(2.0 / Q) * inv))
+    else:
+        delta = torch.sigmoid(plus) - torch.sigmoid(mn)
     max_thres, min_thres = (Q - 1 - 0.5) / (Q / 2.) - 1.0, 0.5 / (Q / 2.) - 1.0
     xe = x.expand_as(plus)
     lp = torch.where(xe < min_thres, plus - _softplus(plus),
@@ -119,12 +124,12 @@ def mol_log_probs(par, x):
     return torch.logsumexp(lp + torch.log_softmax(lg, dim=-1), dim=-1)
 
 
-def kl_logistic(te, mean, scale, rl, log_scale=None):
+def kl_logistic(te, mean, scale, rl, log_scale=None, stable=False):
     """kl_loss_logistic (parallel_wavenet.py:361-402) on the draws rl [B,S,T]; H_Ps from log_scale when given (the
-    reference's input), else from log(scale) (the mirror's)"""
+    reference's input), else from log(scale) (the mirror's); stable as in mol_log_probs"""
     S = rl.shape[1]
     x = rl * scale[:, None, :] + mean[:, None, :]
-    lp = mol_log_probs(te[:, None].expand(-1, S, -1, -1), x)
+    lp = mol_log_probs(te[:, None].expand(-1, S, -1, -1), x, stable)
     hb = -lp.mean(dim=1)
     H_Ps = (torch.log(scale) if log_scale is None else log_scale).mean() + 2
     H_Ps_Pt = hb.mean()
@@ -166,11 +171,11 @@ def power_loss(pred, orig):
     return 0.5 * d.mean() + 0.5 * d[:, :, :PRIORITY_FREQ].mean()
 
 
-def calculate_loss(hp, te, te_rand, ff, rl_kl=None, rl_cl=None, log_scale=None):
+def calculate_loss(hp, te, te_rand, ff, rl_kl=None, rl_cl=None, log_scale=None, stable=False):
     """parallel_wavenet.py:492-512: te / te_rand are the teacher's out_params on x under mel / mel_rand"""
     plf = hp['power_loss_factor']
     if hp.get('loss_type', 'logistic') == 'logistic':
-        d = kl_logistic(te, ff['mean_tot'], ff['scale_tot'], rl_kl, log_scale)
+        d = kl_logistic(te, ff['mean_tot'], ff['scale_tot'], rl_kl, log_scale, stable)
         d.pop('H_bl')
         clf = hp.get('contrastive_loss_factor', 0.0)
     else:
@@ -181,7 +186,7 @@ def calculate_loss(hp, te, te_rand, ff, rl_kl=None, rl_cl=None, log_scale=None):
         d['power_loss'] = power_loss(ff['x'], ff['wav'])
         loss = loss + plf * d['power_loss']
     if clf > 0:
-        d['contrastive_loss'] = -kl_logistic(te_rand, ff['mean_tot'], ff['scale_tot'], rl_cl, log_scale)['kl_loss']
+        d['contrastive_loss'] = -kl_logistic(te_rand, ff['mean_tot'], ff['scale_tot'], rl_cl, log_scale, stable)['kl_loss']
         loss = loss + clf * d['contrastive_loss']
     d['loss'] = loss
     return d
