@@ -24,6 +24,8 @@
 //     chosen to match the accumulator layout), and the tap-t loads ARE its C-in.
 // Weights are packed on the host in A-fragment order and staged once per
 // workgroup in LDS (120.5 KB); workgroups are persistent over 64-sample tiles.
+#include <cstdlib>
+
 #include "wn_internal.h"
 #include "wn_codec.h"
 
@@ -69,21 +71,12 @@ __device__ inline void iaf_noise_body(float* __restrict__ x0, float* __restrict_
     *reinterpret_cast<f4*>(x + (size_t)b * XR + IAF_XP + i4 * 4) = (f4){v[0], v[1], v[2], v[3]};
 }
 
-__global__ void iaf_noise_kernel(float* __restrict__ x0, float* __restrict__ x, int64_t T, int XR,
-                                 uint64_t seed, int gauss) {
-    iaf_noise_body(x0, x, T, XR, seed, gauss, blockIdx.x, blockIdx.y);
-}
-
 __device__ inline void iaf_copy_noise_body(const float* __restrict__ noise, float* __restrict__ x, int64_t T, int XR,
                                            int bx, int b) {
     const int64_t i4 = (int64_t)bx * blockDim.x + threadIdx.x;
     if (i4 * 4 >= T) return;
     *reinterpret_cast<f4*>(x + (size_t)b * XR + IAF_XP + i4 * 4) =
         *reinterpret_cast<const f4*>(noise + (size_t)b * T + i4 * 4);
-}
-
-__global__ void iaf_copy_noise_kernel(const float* __restrict__ noise, float* __restrict__ x, int64_t T, int XR) {
-    iaf_copy_noise_body(noise, x, T, XR, blockIdx.x, blockIdx.y);
 }
 
 // zero the left pads of `rows` rows (row stride rs floats, pad floats each)
@@ -107,12 +100,6 @@ __device__ inline void zero_pads_body(float* __restrict__ lA, float* __restrict_
             x[(size_t)row * xrs + c] = 0.f;
         }
     }
-}
-
-__global__ void zero_pads_kernel(float* __restrict__ lA, float* __restrict__ lB, int64_t rs, int pad, int rows,
-                                 float* __restrict__ x, int64_t xrs, int xpad, int xrows, unsigned* __restrict__ status,
-                                 int dl_rj) {
-    zero_pads_body(lA, lB, rs, pad, rows, x, xrs, xpad, xrows, status, dl_rj, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y);
 }
 
 // The call's prologue as ONE launch (round 5): the zero pads and the flow input (noise drawn here, or the caller's copied)
@@ -728,7 +715,7 @@ __global__ void iaf_final_kernel(const float* __restrict__ x0, const float* __re
     // that is not the reference's result.  Never hand it out as audio -- every float output becomes NaN, the index 0;
     // wn_iaf_range_status() reports WN_ERANGE and the caller re-runs the call with wn_iaf_generate_prec(.., 1 = fp32).
     const bool bad = *status != 0u;
-    // status[1] accumulates over the calls made on this workspace (zero_pads_kernel clears status[0] only): a caller
+    // status[1] accumulates over the calls made on this workspace (the prologue, zero_pads_body, clears status[0] only): a caller
     // that keeps a run of calls asynchronous asks ONCE at the end (wn_iaf_range_status_since_reset)
     if (bad && i == 0) atomicOr(status + 1, *status);
     float s = fminf(St[i], EXP_7);                          // :327
@@ -937,61 +924,315 @@ int wn_pack_iaf(wn_handle* h, std::vector<float>& blob) {
     return WN_OK;
 }
 
-// A student whose widths the MFMA kernels are not specialised for: the same call on the generic fp32 kernels of
-// wn_iaf_x.hip (fp32 upsampler GEMM, one launch per start conv / layer / head, fp32 rows, no fp16 anywhere).
-static int iaf_generate_generic(wn_handle* h, const IafLayout& L, const float* mel, int B, int F, const float* noise,
-                                uint64_t seed, float* wav, int32_t* idx, float* x_raw, float* mean_tot, float* scale_tot,
-                                float* rand_out, char* base, hipStream_t st) {
-    const wn_config& c = h->cfg;
-    float* enc = reinterpret_cast<float*>(base + L.enc);
-    float* lA = reinterpret_cast<float*>(base + L.lA);
-    float* lB = reinterpret_cast<float*>(base + L.lB);
-    float* x = reinterpret_cast<float*>(base + L.x);
-    float* x0g = reinterpret_cast<float*>(base + L.x0);
-    float* Mt = reinterpret_cast<float*>(base + L.M);
-    float* St = reinterpret_cast<float*>(base + L.S);
-    unsigned* status = reinterpret_cast<unsigned*>(base + L.status);
-    void* scratch = base + L.scratch;
-    {
-        const int rows = B * c.width;
-        dim3 g((IAF_LP + 255) / 256, std::min(rows, 32768), 3);
-        hipLaunchKernelGGL(zero_pads_kernel, g, dim3(256), 0, st, lA, lB, L.RS, IAF_LP, rows, x, (int64_t)L.XR, IAF_XP, 2 * B,
-                           status, 0);
-    }
-    const float* x0 = noise;
-    {
-        dim3 g((unsigned)((L.T / 4 + 255) / 256), B);
-        if (noise) {
-            hipLaunchKernelGGL(iaf_copy_noise_kernel, g, dim3(256), 0, st, noise, x, L.T, L.XR);
-        } else {
-            hipLaunchKernelGGL(iaf_noise_kernel, g, dim3(256), 0, st, x0g, x, L.T, L.XR, seed,
-                               c.loss_type == WN_LOSS_GAUSS ? 1 : 0);
-            x0 = x0g;
+// ---------------------------------------------------------------------------
+// One generate call.  wn_iaf_generate_form fills an IafCall once -- workspace pointers, sizes, the switches in force --
+// and walks a fixed skeleton: prologue launch, then per flow [upsampler + conditioning GEMM where due, the flow runner of
+// the call's launch form], final kernel.  The form is chosen once per call (iaf_runner); no runner tests precision,
+// conditioning placement or group use inside its layer loop.
+namespace {
+
+constexpr size_t MAX_PART_EVENTS = 4096;   // a power loop of thousands of calls stops recording, not allocating
+
+struct IafCall {
+    wn_handle* h;
+    IafLayout L;
+    int B, F;
+    const float* mel;
+    hipStream_t st;
+    float *enc, *lA, *lB, *Mt, *St, *Cc;
+    float *xbuf0, *x;                  // the two copies of the flow input start at xbuf0; x is the one in force (run_groups)
+    unsigned* status;
+    void* scratch;
+    int prec;                          // WN_PREC_* of this call
+    bool f16x3, hoist, use_groups;
+    int tiles_per_row, ntiles, grid;   // 64-sample tiles of the fp32 kernels
+    size_t rb_floats;                  // C floats of one row block
+    // switches, each read ONCE at the call's entry
+    bool prof_on, parts_on;
+    int pmask;                         // parts the call runs: a restriction exists only inside a parts session (wn_profile_parts_only)
+    bool no_pair, no_headfuse;         // WN_NO_PAIR / WN_NO_HEADFUSE (cross-form tests): no two-layer launches / no head in a last layer
+    // measurement state
+    int part_now = -2;
+    bool prof_open = false;
+
+    int record(std::vector<hipEvent_t>& list, int tag) {
+        hipEvent_t ev;
+        WN_HIP(h, hipEventCreate(&ev));
+        {
+            std::lock_guard<std::mutex> g(h->list_mu);
+            list.push_back(ev);
+            if (&list == &h->part_events) h->part_tags.push_back(tag);
         }
+        WN_HIP(h, hipEventRecord(ev, st));
+        return WN_OK;
     }
-    if (c.share_deconv)
-        if (int rc = wn_run_deconv(h, 0, mel, B, F, enc, L.TE, scratch, st, false, nullptr, WN_PREC_F32)) return rc;
-    for (int k = 0; k < c.n_flows; ++k) {
-        const IafFlowX& fx = h->flows_x[k];
-        if (!c.share_deconv)
-            if (int rc = wn_run_deconv(h, fx.deconv_stack, mel, B, F, enc, L.TE, scratch, st, false, nullptr, WN_PREC_F32)) return rc;
-        wn_iaf_x_start(h, fx, x, lA, L.T, L.XR, L.RS, B, st);
-        float* lin = lA;
-        float* lout = lB;
-        for (const IafLayerX& lx : fx.layers) {
-            wn_iaf_x_layer(h, lx, lin, lout, enc, L.RS, L.TE, L.c0, B, L.T, st);
-            std::swap(lin, lout);
+    // measurement aid (wn_profile_parts_begin): an event where a part of the call begins.  Parts: 0 prologue / epilogue
+    // (pads, noise, final), 1 upsampler, 2 conditioning GEMM, 3 residual stack (start convs, layers, heads)
+    int part(int tag) {
+        if (!parts_on || tag == part_now) return WN_OK;
+        part_now = tag;
+        {
+            std::lock_guard<std::mutex> g(h->list_mu);
+            if (h->part_events.size() >= MAX_PART_EVENTS) return WN_OK;
         }
-        wn_iaf_x_head(h, fx, lin, enc, x, Mt, St, L.RS, L.TE, L.c0, L.XR, L.T, k == 0 ? 1 : 0, B, st);
+        return record(h->part_events, tag);
     }
-    const int64_t nn = (int64_t)B * L.T;
-    const int Q = c.use_mu_law ? 256 : 65536;
-    hipLaunchKernelGGL(iaf_final_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, x0, Mt, St, nn, Q, c.use_mu_law,
-                       wav, idx, x_raw, mean_tot, scale_tot, status);
-    if (rand_out && rand_out != x0) WN_HIP(h, hipMemcpyAsync(rand_out, x0, nn * sizeof(float), hipMemcpyDeviceToDevice, st));
-    WN_HIP(h, hipGetLastError());
+    // bench.py measurement aid: event pairs around every maximal run of single-layer launches (the dominant kernel);
+    // two-layer launches and heads stay outside the brackets
+    int prof_mark(bool open, int launches) {
+        if (!prof_on) return WN_OK;
+        if (open != prof_open) {
+            if (int rc = record(h->prof_events, 0)) return rc;
+            prof_open = open;
+        }
+        if (open) {
+            std::lock_guard<std::mutex> g(h->list_mu);
+            h->prof_launches += launches;
+        }
+        return WN_OK;
+    }
+    const unsigned* blob_u(size_t off) const { return reinterpret_cast<const unsigned*>(h->d_blob + off); }
+};
+
+// prologue: zero left pads + the flow input (drawn on the device, or the caller's noise), one launch
+void iaf_prologue(const IafCall& c, const float* noise, float* x0g, uint64_t seed) {
+    const IafLayout& L = c.L;
+    PrologueArgs A{};
+    // G4 layout (f16x3) and the Q4 rows of the hoisted fp32 form: 16 interleaved group rows per batch element, each
+    // 4*(LP+T) words; fused fp32 form and the generic student: planar rows, one per channel
+    const bool rows16 = c.f16x3 || c.hoist;
+    A.rows = rows16 ? c.B * 16 : c.B * c.h->cfg.width;
+    A.rs = rows16 ? 4 * L.RS : L.RS;
+    A.pad = rows16 ? 4 * IAF_LP : IAF_LP;
+    A.lA = c.lA; A.lB = c.lB; A.x = c.x; A.x0g = x0g; A.noise = noise; A.status = c.status;
+    A.xrs = (int64_t)L.XR; A.xpad = IAF_XP; A.xrows = 2 * c.B;
+    A.dl_rj = c.use_groups ? 64 + (int)(L.T / 32) : 0;
+    A.pgx = (A.pad + 255) / 256;
+    A.pgy = std::min(std::max(A.rows, 2 * c.B), 32768);
+    A.npad = A.pgx * A.pgy * 3;
+    A.T = L.T; A.XR = L.XR; A.seed = seed; A.gauss = c.h->cfg.loss_type == WN_LOSS_GAUSS ? 1 : 0;
+    A.ngx = (int)((L.T / 4 + 255) / 256);
+    hipLaunchKernelGGL(iaf_prologue_kernel, dim3((unsigned)(A.npad + A.ngx * c.B)), dim3(256), 0, c.st, A);
+}
+
+// Upsampler of deconv stack si, then (hoisted forms) the conditioning GEMM of its R row blocks, which start at row block
+// rb0 of the student's tables; order / n_nat: wn_iaf_c_cond.  Once per call for a shared stack, once per flow otherwise.
+int iaf_upsample_cond(IafCall& c, int si, int rb0, int R, const unsigned* order, int n_nat) {
+    wn_handle* h = c.h;
+    const IafLayout& L = c.L;
+    if (int rc = c.part(1)) return rc;
+    if (c.pmask & 2)
+        if (int rc = wn_run_deconv(h, si, c.mel, c.B, c.F, c.enc, L.TE, c.scratch, c.st, c.f16x3, c.status, c.prec)) return rc;
+    if (!c.hoist) return WN_OK;
+    if (int rc = c.part(2)) return rc;
+    if (!(c.pmask & 4)) return WN_OK;
+    if (c.f16x3)
+        wn_iaf_c_cond(c.enc, h->d_blob, c.blob_u(h->cond_tab_off) + rb0, order, n_nat, c.Cc, L.c_bstride, L.TE, L.c0, R, c.B,
+                      L.T, h->num_cu, c.st);
+    else
+        wn_iaf_f_cond(h, c.enc, c.blob_u(h->cond_tab_f_off) + 2 * rb0, R, c.Cc, L.c_bstride, L.TE, L.c0, c.B, L.T, c.st);
     return WN_OK;
 }
+
+// ---- flow runners: flow k from the start conv to the head, one per launch form.  Cf: the flow's row blocks inside C ----
+
+// Layer groups (wn_iaf_g.hip): natural / decimated layer groups in LDS: lA natural, lB DL; the first group computes the
+// start conv from x, the last one runs the flow head
+int run_groups(IafCall& c, int k, const float* Cf) {
+    wn_handle* h = c.h;
+    const IafLayout& L = c.L;
+    const IafFlowPack& fp = h->flows[k];
+    float* gin = c.lA;
+    float* gout = c.lB;
+    if (c.prof_on) if (int rc = c.record(h->prof_events, 0)) return rc;
+    for (size_t gi = 0; gi < fp.groups.size(); ++gi) {
+        const WnGroup& g = fp.groups[gi];
+        const bool lastg = gi + 1 == fp.groups.size();
+        // a flow that is ONE group reads x (start conv, with its halo) and writes x (head) in the same launch:
+        // the new x goes to the other copy, which becomes the flow input from then on
+        float* xnew = (gi == 0 && lastg) ? (c.x == c.xbuf0 ? c.xbuf0 + (size_t)c.B * L.XR : c.xbuf0) : c.x;
+        wn_iaf_g_run(h, g, fp.layers.data(), Cf + (size_t)g.begin * c.rb_floats, c.rb_floats, L.c_bstride, gin, gout, L.RS,
+                     lastg ? 0 : fp.groups[gi + 1].kind, c.B, L.T, gi == 0 ? c.x : nullptr, L.XR, h->d_blob + fp.start_off,
+                     lastg, h->d_blob + fp.head_off_h, c.x, xnew, c.Mt, c.St, k == 0 ? 1 : 0, c.status, c.st);
+        c.x = xnew;
+        std::swap(gin, gout);
+    }
+    if (c.prof_on) {
+        if (int rc = c.record(h->prof_events, 0)) return rc;
+        std::lock_guard<std::mutex> g(h->list_mu);
+        h->prof_launches += (int64_t)fp.groups.size();
+    }
+    return WN_OK;
+}
+
+// Split-fp16, hoisted conditioning, per-layer launches (wn_iaf_c.hip): layer pairs with small dilations run as one launch,
+// and when the flow starts with such a pair the start conv runs inside it; the last layer, unless a pair took it, carries
+// the head.  Pairs never overlap (the second layer of one has dilation 2 or 8, the first 1 or 4), so pair_at is exact.
+int run_f16x3_hoisted(IafCall& c, int k, const float* Cf) {
+    const wn_handle* h = c.h;
+    const IafLayout& L = c.L;
+    const IafFlowPack& fp = h->flows[k];
+    const size_t n = fp.layers.size();
+    const int first = k == 0 ? 1 : 0;
+    auto pair_at = [&](size_t i) {
+        return !c.no_pair && i + 1 < n && wn_iaf_c_pair_ok(fp.layers[i].dilation, fp.layers[i + 1].dilation);
+    };
+    const bool pair_start = pair_at(0) && fp.layers[0].dilation == 1;
+    const bool head_in_last = n > 0 && !c.no_headfuse && !(n >= 2 && pair_at(n - 2));
+    const size_t n_plain = head_in_last ? n - 1 : n;      // layers launched without the head
+    if (!pair_start) wn_iaf_h_start(c.x, h->d_blob + fp.start_off, c.lA, L.T, L.XR, L.RS, c.B, c.st, c.status);
+    float* lin = c.lA;
+    float* lout = c.lB;
+    for (size_t i = 0; i < n_plain;) {
+        const IafLayerPack& lp = fp.layers[i];
+        const float* Ci = Cf + i * c.rb_floats;
+        if (pair_at(i)) {
+            const IafLayerPack& lq = fp.layers[i + 1];
+            if (int rc = c.prof_mark(false, 0)) return rc;
+            wn_iaf_c_pair(lin, lout, Ci, Ci + c.rb_floats, L.c_bstride, h->d_blob + lp.off_h, h->d_blob + lq.off_h, L.RS,
+                          lp.dilation, lq.dilation, c.B, L.T, h->num_cu, c.st, (i == 0 && pair_start) ? c.x : nullptr, L.XR,
+                          h->d_blob + fp.start_off, c.status);
+            i += 2;
+        } else {
+            if (int rc = c.prof_mark(true, 1)) return rc;
+            wn_iaf_c_layer(lin, lout, Ci, L.c_bstride, h->d_blob + lp.off_h, L.RS, lp.dilation, c.B, L.T, h->num_cu, c.st,
+                           c.status);
+            ++i;
+        }
+        std::swap(lin, lout);
+    }
+    if (int rc = c.prof_mark(false, 0)) return rc;
+    const float* Ch = Cf + n * c.rb_floats;
+    if (head_in_last)
+        wn_iaf_c_layer_head(lin, Ch - c.rb_floats, Ch, L.c_bstride, h->d_blob + fp.layers[n - 1].off_h,
+                            h->d_blob + fp.head_off_h, c.x, c.Mt, c.St, L.RS, L.XR, fp.layers[n - 1].dilation, first, c.B, L.T,
+                            h->num_cu, c.st, c.status);
+    else
+        wn_iaf_c_head(lin, Ch, L.c_bstride, h->d_blob + fp.head_off_h, c.x, c.Mt, c.St, L.RS, L.XR, L.T, first, c.B,
+                      h->num_cu, c.st);
+    return WN_OK;
+}
+
+// Split-fp16, conditioning fused into every layer (wn_iaf_h.hip): the start conv runs inside the first layer kernel of the
+// flow when its dilation is 1
+int run_f16x3_fused(IafCall& c, int k, const float*) {
+    const wn_handle* h = c.h;
+    const IafLayout& L = c.L;
+    const IafFlowPack& fp = h->flows[k];
+    const bool fuse_start = !fp.layers.empty() && fp.layers[0].dilation == 1;
+    if (!fuse_start) wn_iaf_h_start(c.x, h->d_blob + fp.start_off, c.lA, L.T, L.XR, L.RS, c.B, c.st, c.status);
+    float* lin = c.lA;
+    float* lout = c.lB;
+    for (size_t i = 0; i < fp.layers.size(); ++i) {
+        const IafLayerPack& lp = fp.layers[i];
+        if (int rc = c.prof_mark(true, 1)) return rc;
+        wn_iaf_h_layer(lin, lout, c.enc, h->d_blob + lp.off_h, L.RS, L.TE, L.c0, lp.dilation, c.B, L.T, h->num_cu, c.st,
+                       c.status, (i == 0 && fuse_start) ? c.x : nullptr, L.XR, h->d_blob + fp.start_off);
+        std::swap(lin, lout);
+    }
+    if (int rc = c.prof_mark(false, 0)) return rc;
+    wn_iaf_h_head(lin, c.enc, h->d_blob + fp.head_off_h, c.x, c.Mt, c.St, L.RS, L.TE, L.c0, L.XR, L.T, k == 0 ? 1 : 0, c.B,
+                  h->num_cu, c.st);
+    return WN_OK;
+}
+
+// the launches of the fp32 layer and head kernels (HOIST: accumulators start from the C rows instead of streaming enc)
+template <bool HOIST, bool LAST = false, bool START = false>
+void launch_layer_f32(const IafCall& c, const IafLayerPack& lp, const float* lin, float* lout, const float* C,
+                      const HeadF& hd = HeadF{}, const StartF& sf = StartF{}) {
+    constexpr size_t lds = (HOIST ? IAF_LAYER_F_FLOATS + (LAST ? IAF_HEAD_F_FLOATS : 0) : IAF_LAYER_FLOATS) * sizeof(float);
+    hipLaunchKernelGGL((iaf_layer_kernel<HOIST, LAST, START>), dim3(c.grid), dim3(iaf_layer_threads(HOIST)), lds, c.st, lin,
+                       lout, c.enc + c.L.c0, c.h->d_blob + lp.off, c.L.RS, c.L.TE, lp.dilation, c.tiles_per_row, c.ntiles, C,
+                       c.L.c_bstride, hd, sf);
+}
+template <bool HOIST>
+void launch_head_f32(const IafCall& c, const IafFlowPack& fp, const float* lin, const float* C, int first) {
+    hipLaunchKernelGGL(iaf_head_kernel<HOIST>, dim3(c.grid), dim3(256), (HOIST ? IAF_HEAD_F_FLOATS : IAF_HEAD_FLOATS) * sizeof(float),
+                       c.st, lin, c.enc + c.L.c0, c.h->d_blob + fp.head_off, c.x, c.Mt, c.St, c.L.RS, c.L.TE, c.L.XR, c.L.T,
+                       first, c.tiles_per_row, c.ntiles, C, c.L.c_bstride);
+}
+
+// fp32, hoisted conditioning: the last layer of the flow carries the head in its epilogue (iaf_layer_kernel<true, true>);
+// with at least two layers and a first dilation of 1 the start conv runs in front of the first one (<true, false, true>)
+int run_f32_hoisted(IafCall& c, int k, const float* Cf) {
+    const wn_handle* h = c.h;
+    const IafLayout& L = c.L;
+    const IafFlowPack& fp = h->flows[k];
+    const size_t n = fp.layers.size();
+    const int first = k == 0 ? 1 : 0;
+    const bool start_in_layer = n >= 2 && fp.layers[0].dilation == 1;
+    if (!start_in_layer)
+        hipLaunchKernelGGL(iaf_start_q4_kernel, dim3((unsigned)((L.T + 255) / 256), c.B), dim3(256), 0, c.st, c.x,
+                           h->d_blob + fp.start_off, c.lA, L.T, L.XR, L.RS);
+    float* lin = c.lA;
+    float* lout = c.lB;
+    for (size_t i = 0; i + 1 < n; ++i) {
+        if (int rc = c.prof_mark(true, 1)) return rc;
+        if (i == 0 && start_in_layer)
+            launch_layer_f32<true, false, true>(c, fp.layers[i], lin, lout, Cf + i * c.rb_floats, HeadF{},
+                                                StartF{c.x, h->d_blob + fp.start_off, L.XR});
+        else
+            launch_layer_f32<true>(c, fp.layers[i], lin, lout, Cf + i * c.rb_floats);
+        std::swap(lin, lout);
+    }
+    const float* Ch = Cf + n * c.rb_floats;
+    if (n == 0) {
+        launch_head_f32<true>(c, fp, lin, Ch, first);
+        return WN_OK;
+    }
+    // the last layer counts as a single-layer launch and runs outside the brackets, like every launch with a head in it
+    if (int rc = c.prof_mark(true, 1)) return rc;
+    if (int rc = c.prof_mark(false, 0)) return rc;
+    launch_layer_f32<true, true>(c, fp.layers[n - 1], lin, lout, Ch - c.rb_floats,
+                                 HeadF{h->d_blob + fp.head_off, Ch, c.x, c.Mt, c.St, L.XR, L.T, first});
+    return WN_OK;
+}
+
+// fp32, conditioning fused into every layer: start conv, layers and head are one launch each
+int run_f32_fused(IafCall& c, int k, const float*) {
+    const wn_handle* h = c.h;
+    const IafLayout& L = c.L;
+    const IafFlowPack& fp = h->flows[k];
+    hipLaunchKernelGGL(iaf_start_kernel, dim3((unsigned)((L.T / 4 + 255) / 256), c.B), dim3(256), 0, c.st, c.x,
+                       h->d_blob + fp.start_off, c.lA, L.T, L.XR, L.RS);
+    float* lin = c.lA;
+    float* lout = c.lB;
+    for (const IafLayerPack& lp : fp.layers) {
+        if (int rc = c.prof_mark(true, 1)) return rc;
+        launch_layer_f32<false>(c, lp, lin, lout, nullptr);
+        std::swap(lin, lout);
+    }
+    if (int rc = c.prof_mark(false, 0)) return rc;
+    launch_head_f32<false>(c, fp, lin, nullptr, k == 0 ? 1 : 0);
+    return WN_OK;
+}
+
+// A student whose widths the MFMA kernels are not specialised for: the generic fp32 kernels of wn_iaf_x.hip (fp32 upsampler
+// GEMM, one launch per start conv / layer / head, fp32 rows of the model's own widths, no fp16 anywhere)
+int run_generic(IafCall& c, int k, const float*) {
+    const wn_handle* h = c.h;
+    const IafLayout& L = c.L;
+    const IafFlowX& fx = h->flows_x[k];
+    wn_iaf_x_start(h, fx, c.x, c.lA, L.T, L.XR, L.RS, c.B, c.st);
+    float* lin = c.lA;
+    float* lout = c.lB;
+    for (const IafLayerX& lx : fx.layers) {
+        wn_iaf_x_layer(h, lx, lin, lout, c.enc, L.RS, L.TE, L.c0, c.B, L.T, c.st);
+        std::swap(lin, lout);
+    }
+    wn_iaf_x_head(h, fx, lin, c.enc, c.x, c.Mt, c.St, L.RS, L.TE, L.c0, L.XR, L.T, k == 0 ? 1 : 0, c.B, c.st);
+    return WN_OK;
+}
+
+using IafRunner = int (*)(IafCall&, int, const float*);
+IafRunner iaf_runner(const IafCall& c) {
+    if (c.h->generic_student) return run_generic;
+    if (c.use_groups) return run_groups;
+    if (c.f16x3) return c.hoist ? run_f16x3_hoisted : run_f16x3_fused;
+    return c.hoist ? run_f32_hoisted : run_f32_fused;
+}
+
+}  // namespace
 
 extern "C" int wn_iaf_generate(wn_handle* h, const float* mel, int B, int F, const float* noise,
                                uint64_t seed, float* wav, int32_t* idx, float* x_raw, float* mean_tot,
@@ -1011,11 +1252,17 @@ extern "C" int wn_iaf_generate_form(wn_handle* h, int form, const float* mel, in
         return wn_fail(h, WN_EINVAL, "wn_iaf_generate: handle is not a ParallelWavenet student");
     if (B < 1 || F < 1) return wn_fail(h, WN_EINVAL, "wn_iaf_generate: B and F must be >= 1");
     // inside the library from here on: the switches (wn_iaf_set_groups, wn_profile_*) are refused until the call returns,
-    // and each of them is read ONCE, here
+    // and each of them -- the two environment switches included -- is read ONCE, here
     const WnWork work(h);
-    const bool prof_on = h->prof_on, parts_on = h->parts_on;
-    const int pmask = parts_on ? h->parts_mask : 0xf;   // a restriction exists only inside a parts session (wn_profile_parts_only)
-    const IafLayout L = iaf_layout(h, B, F, form);
+    IafCall c{};
+    c.h = h;
+    c.prof_on = h->prof_on;
+    c.parts_on = h->parts_on;
+    c.pmask = c.parts_on ? h->parts_mask : 0xf;
+    c.no_pair = getenv("WN_NO_PAIR") != nullptr;
+    c.no_headfuse = getenv("WN_NO_HEADFUSE") != nullptr;
+    c.L = iaf_layout(h, B, F, form);
+    const IafLayout& L = c.L;
     if (L.T == 0) return WN_OK;   // fewer frames than one max-dilation block: empty output
     if (!mel || !wav || !ws) return wn_fail(h, WN_EINVAL, "wn_iaf_generate: null mel/wav/workspace");
     if (ws_bytes < L.total)
@@ -1024,267 +1271,58 @@ extern "C" int wn_iaf_generate_form(wn_handle* h, int form, const float* mel, in
     if (L.TE > 2000000)   // 32-bit buffer offsets inside one batch element (960 * TE bytes)
         return wn_fail(h, WN_EINVAL, "wn_iaf_generate: %lld samples per utterance exceeds the 2,000,000 "
                        "(125 s) limit of the 32-bit row offsets; split the utterance", (long long)L.TE);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const wn_config& cfg = h->cfg;
     char* base = reinterpret_cast<char*>(ws);
-    float* enc = reinterpret_cast<float*>(base + L.enc);
-    float* lA = reinterpret_cast<float*>(base + L.lA);
-    float* lB = reinterpret_cast<float*>(base + L.lB);
-    float* x = reinterpret_cast<float*>(base + L.x);
-    float* const xbuf0 = x;
-    float* x0g = reinterpret_cast<float*>(base + L.x0);
-    float* Mt = reinterpret_cast<float*>(base + L.M);
-    float* St = reinterpret_cast<float*>(base + L.S);
-    float* Cc = reinterpret_cast<float*>(base + L.C);
-    unsigned* status = reinterpret_cast<unsigned*>(base + L.status);
-    void* scratch = base + L.scratch;
-    const wn_config& c = h->cfg;
+    auto at = [base](size_t off) { return reinterpret_cast<float*>(base + off); };
+    c.B = B; c.F = F; c.mel = mel;
+    c.st = reinterpret_cast<hipStream_t>(stream);
+    c.enc = at(L.enc); c.lA = at(L.lA); c.lB = at(L.lB); c.Mt = at(L.M); c.St = at(L.S); c.Cc = at(L.C);
+    c.xbuf0 = c.x = at(L.x);
+    c.status = reinterpret_cast<unsigned*>(base + L.status);
+    c.scratch = base + L.scratch;
+    c.prec = h->generic_student ? WN_PREC_F32 : wn_form_precision(h, form);
+    c.f16x3 = c.prec == WN_PREC_F16X3;
+    c.hoist = L.form == WN_COND_HOISTED;
+    c.use_groups = c.f16x3 && wn_iaf_use_groups(h, B, L.T, L.form);
+    c.tiles_per_row = (int)(L.T / 64);
+    c.ntiles = B * c.tiles_per_row;
+    c.grid = std::min(c.ntiles, h->num_cu);
+    c.rb_floats = (size_t)(L.T / 16) * 1024;
+    const IafRunner run_flow = iaf_runner(c);
 
-    if (h->generic_student)
-        return iaf_generate_generic(h, L, mel, B, F, noise, seed, wav, idx, x_raw, mean_tot, scale_tot, rand_out, base, st);
-    const int prec = wn_form_precision(h, form);
-    const bool f16x3 = prec == WN_PREC_F16X3;
-
-    const bool use_groups = f16x3 && wn_iaf_use_groups(h, B, L.T, L.form);
-    // measurement aid (wn_profile_parts_begin): an event where a part of the call begins.  Parts: 0 prologue / epilogue
-    // (pads, noise, final), 1 upsampler, 2 conditioning GEMM, 3 residual stack (start convs, layers, heads)
-    int part_now = -2;
-    constexpr size_t MAX_PART_EVENTS = 4096;            // a power loop of thousands of calls stops recording, not allocating
-    auto record = [&](std::vector<hipEvent_t>& list, int tag) -> int {
-        hipEvent_t ev;
-        WN_HIP(h, hipEventCreate(&ev));
-        {
-            std::lock_guard<std::mutex> g(h->list_mu);
-            list.push_back(ev);
-            if (&list == &h->part_events) h->part_tags.push_back(tag);
-        }
-        WN_HIP(h, hipEventRecord(ev, st));
-        return WN_OK;
-    };
-    auto part = [&](int tag) -> int {
-        if (!parts_on || tag == part_now) return WN_OK;
-        part_now = tag;
-        {
-            std::lock_guard<std::mutex> g(h->list_mu);
-            if (h->part_events.size() >= MAX_PART_EVENTS) return WN_OK;
-        }
-        return record(h->part_events, tag);
-    };
-    if (int rc = part(0)) return rc;
-    // prologue: zero left pads + the flow input (drawn on the device, or the caller's noise), one launch
+    if (int rc = c.part(0)) return rc;
+    float* x0g = at(L.x0);
     const float* x0 = noise ? noise : x0g;
-    {
-        PrologueArgs A{};
-        // G4 layout (f16x3) and the Q4 rows of the hoisted fp32 form: 16 interleaved group rows per batch element, each
-        // 4*(LP+T) words; fused fp32 form: 64 planar rows
-        const bool rows16 = f16x3 || L.form == WN_COND_HOISTED;
-        A.rows = rows16 ? B * 16 : B * IAF_W;
-        A.rs = rows16 ? 4 * L.RS : L.RS;
-        A.pad = rows16 ? 4 * IAF_LP : IAF_LP;
-        A.lA = lA; A.lB = lB; A.x = x; A.x0g = x0g; A.noise = noise; A.status = status;
-        A.xrs = (int64_t)L.XR; A.xpad = IAF_XP; A.xrows = 2 * B;
-        A.dl_rj = use_groups ? 64 + (int)(L.T / 32) : 0;
-        A.pgx = (A.pad + 255) / 256;
-        A.pgy = std::min(std::max(A.rows, 2 * B), 32768);
-        A.npad = A.pgx * A.pgy * 3;
-        A.T = L.T; A.XR = L.XR; A.seed = seed; A.gauss = c.loss_type == WN_LOSS_GAUSS ? 1 : 0;
-        A.ngx = (int)((L.T / 4 + 255) / 256);
-        hipLaunchKernelGGL(iaf_prologue_kernel, dim3((unsigned)(A.npad + A.ngx * B)), dim3(256), 0, st, A);
-    }
-    const bool hoist = L.form == WN_COND_HOISTED;
-    auto blob_u = [&](size_t off) { return reinterpret_cast<const unsigned*>(h->d_blob + off); };
-    const unsigned* cond_tab = blob_u(h->cond_tab_off);
-    const size_t rb_floats = (size_t)(L.T / 16) * 1024;     // C floats of one row block
-    if (c.share_deconv) {
-        if (int rc = part(1)) return rc;
-        int rc = (pmask & 2) ? wn_run_deconv(h, 0, mel, B, F, enc, L.TE, scratch, st, f16x3, status, prec) : WN_OK;
-        if (rc) return rc;
-        if (hoist) if (int rc2 = part(2)) return rc2;
-        if (hoist && (pmask & 4)) {
-            if (f16x3)
-                wn_iaf_c_cond(enc, h->d_blob, cond_tab, blob_u(use_groups ? h->order_all_off : h->order_id_off),
-                              use_groups ? h->n_nat_all : h->cond_rows, Cc, L.c_bstride, L.TE, L.c0, h->cond_rows, B, L.T,
-                              h->num_cu, st);
-            else
-                wn_iaf_f_cond(h, enc, blob_u(h->cond_tab_f_off), h->cond_rows, Cc, L.c_bstride, L.TE, L.c0, B, L.T, st);
-        }
-    }
-    const int tiles_per_row = (int)(L.T / 64);
-    const int ntiles = B * tiles_per_row;
-    const int grid = ntiles < h->num_cu ? ntiles : h->num_cu;
-    const float* encc = enc + L.c0;
-    for (int k = 0; k < c.n_flows; ++k) {
-        const IafFlowPack& fp = h->flows[k];
-        if (!c.share_deconv) {
-            if (int rc = part(1)) return rc;
-            int rc = (pmask & 2) ? wn_run_deconv(h, fp.deconv_stack, mel, B, F, enc, L.TE, scratch, st, f16x3, status, prec) : WN_OK;
-            if (rc) return rc;
-            if (hoist) if (int rc2 = part(2)) return rc2;
-            if (hoist && (pmask & 4)) {
-                if (f16x3)
-                    wn_iaf_c_cond(enc, h->d_blob, cond_tab + fp.rb_base,
-                                  use_groups ? blob_u(h->order_flow_off) + fp.rb_base : blob_u(h->order_id_off),
-                                  use_groups ? h->n_nat_flow[k] : (int)fp.layers.size() + 1, Cc, L.c_bstride, L.TE, L.c0,
-                                  (int)fp.layers.size() + 1, B, L.T, h->num_cu, st);
-                else
-                    wn_iaf_f_cond(h, enc, blob_u(h->cond_tab_f_off) + 2 * fp.rb_base, (int)fp.layers.size() + 1, Cc,
-                                  L.c_bstride, L.TE, L.c0, B, L.T, st);
-            }
-        }
-        if (int rc = part(3)) return rc;
-        if (!(pmask & 8)) continue;
+    iaf_prologue(c, noise, x0g, seed);
+    if (cfg.share_deconv)
+        if (int rc = iaf_upsample_cond(c, 0, 0, h->cond_rows, c.blob_u(c.use_groups ? h->order_all_off : h->order_id_off),
+                                       c.use_groups ? h->n_nat_all : h->cond_rows))
+            return rc;
+    for (int k = 0; k < cfg.n_flows; ++k) {
+        // the flow's row blocks in the conditioning tables (the generic student has none: it is never hoisted)
+        const IafFlowPack* fp = h->generic_student ? nullptr : &h->flows[k];
+        const int rb0 = fp ? fp->rb_base : 0, R = fp ? (int)fp->layers.size() + 1 : 0;
+        if (!cfg.share_deconv)
+            if (int rc = iaf_upsample_cond(c, fp ? fp->deconv_stack : h->flows_x[k].deconv_stack, rb0, R,
+                                           c.use_groups ? c.blob_u(h->order_flow_off) + rb0 : c.blob_u(h->order_id_off),
+                                           c.use_groups ? h->n_nat_flow[k] : R))
+                return rc;
+        if (int rc = c.part(3)) return rc;
+        if (!(c.pmask & 8)) continue;
         // row blocks of this flow inside C (all flows when the deconv stack is shared)
-        const float* Cf = Cc + (c.share_deconv ? (size_t)fp.rb_base * rb_floats : 0);
-        if (use_groups) {
-            // natural / decimated layer groups in LDS: lA natural, lB DL; the first group computes the start conv
-            // from x, the last one runs the flow head
-            float* gin = lA;
-            float* gout = lB;
-            if (prof_on) if (int rc = record(h->prof_events, 0)) return rc;
-            for (size_t gi = 0; gi < fp.groups.size(); ++gi) {
-                const WnGroup& g = fp.groups[gi];
-                const bool lastg = gi + 1 == fp.groups.size();
-                // a flow that is ONE group reads x (start conv, with its halo) and writes x (head) in the same launch:
-                // the new x goes to the other copy, which becomes the flow input from then on
-                float* xnew = (gi == 0 && lastg) ? (x == xbuf0 ? xbuf0 + (size_t)B * L.XR : xbuf0) : x;
-                wn_iaf_g_run(h, g, fp.layers.data(), Cf + (size_t)g.begin * rb_floats, rb_floats, L.c_bstride, gin, gout,
-                             L.RS, lastg ? 0 : fp.groups[gi + 1].kind, B, L.T, gi == 0 ? x : nullptr, L.XR,
-                             h->d_blob + fp.start_off, lastg, h->d_blob + fp.head_off_h, x, xnew, Mt, St, k == 0 ? 1 : 0,
-                             status, st);
-                x = xnew;
-                std::swap(gin, gout);
-            }
-            if (prof_on) {
-                if (int rc = record(h->prof_events, 0)) return rc;
-                std::lock_guard<std::mutex> g(h->list_mu);
-                h->prof_launches += (int64_t)fp.groups.size();
-            }
-            continue;
-        }
-        // fused f16x3 form: the start conv runs inside the first layer kernel of the flow (dilation 1)
-        const bool fuse_start = f16x3 && !hoist && !fp.layers.empty() && fp.layers[0].dilation == 1;
-        // hoisted form: layer pairs with small dilations run as one launch (wn_iaf_c_pair); when the flow
-        // starts with such a pair the start conv runs inside it as well
-        const bool pair_start = hoist && f16x3 && fp.layers.size() >= 2 && fp.layers[0].dilation == 1 &&
-                                wn_iaf_c_pair_ok(fp.layers[0].dilation, fp.layers[1].dilation);
-        // fp32 hoisted form: the start conv runs in front of the first layer (dilation 1, at least two layers: the last one carries the head)
-        static const bool no_start_fuse = getenv("WN_F32_NO_STARTFUSE") != nullptr;
-        const bool start_in_layer = hoist && !f16x3 && !no_start_fuse && fp.layers.size() >= 2 && fp.layers[0].dilation == 1;
-        if (fuse_start || pair_start || start_in_layer) {
-        } else if (f16x3) {
-            wn_iaf_h_start(x, h->d_blob + fp.start_off, lA, L.T, L.XR, L.RS, B, st, status);
-        } else if (hoist) {
-            dim3 g((unsigned)((L.T + 255) / 256), B);
-            hipLaunchKernelGGL(iaf_start_q4_kernel, g, dim3(256), 0, st, x, h->d_blob + fp.start_off, lA, L.T,
-                               L.XR, L.RS);
-        } else {
-            dim3 g((unsigned)((L.T / 4 + 255) / 256), B);
-            hipLaunchKernelGGL(iaf_start_kernel, g, dim3(256), 0, st, x, h->d_blob + fp.start_off, lA, L.T,
-                               L.XR, L.RS);
-        }
-        float* lin = lA;
-        float* lout = lB;
-        // bench.py measurement aid: event pairs around every maximal run of single-layer launches
-        // (the dominant kernel); two-layer launches and heads stay outside the brackets
-        bool prof_open = false;
-        auto prof_mark = [&](bool open, int launches) -> int {
-            if (!prof_on) return WN_OK;
-            if (open != prof_open) {
-                if (int rc = record(h->prof_events, 0)) return rc;
-                prof_open = open;
-            }
-            if (open) {
-                std::lock_guard<std::mutex> g(h->list_mu);
-                h->prof_launches += launches;
-            }
-            return WN_OK;
-        };
-        size_t li = 0;
-        bool head_done = false;
-        for (size_t i = 0; i < fp.layers.size(); ++i) {
-            const IafLayerPack& lp = fp.layers[i];
-            if (hoist && f16x3 && i + 1 < fp.layers.size() && wn_iaf_c_pair_ok(lp.dilation, fp.layers[i + 1].dilation)) {
-                const IafLayerPack& lq = fp.layers[i + 1];
-                if (int rc = prof_mark(false, 0)) return rc;
-                wn_iaf_c_pair(lin, lout, Cf + li * rb_floats, Cf + (li + 1) * rb_floats, L.c_bstride,
-                              h->d_blob + lp.off_h, h->d_blob + lq.off_h, L.RS, lp.dilation, lq.dilation, B, L.T,
-                              h->num_cu, st, (i == 0 && pair_start) ? x : nullptr, L.XR, h->d_blob + fp.start_off, status);
-                float* t = lin; lin = lout; lout = t;
-                li += 2;
-                ++i;
-                continue;
-            }
-            if (hoist && f16x3 && i + 1 == fp.layers.size() && wn_iaf_c_last_ok()) {
-                // last layer of the flow: the head runs in its epilogue
-                if (int rc = prof_mark(false, 0)) return rc;
-                wn_iaf_c_layer_head(lin, Cf + li * rb_floats, Cf + (li + 1) * rb_floats, L.c_bstride,
-                                    h->d_blob + lp.off_h, h->d_blob + fp.head_off_h, x, Mt, St, L.RS, L.XR, lp.dilation,
-                                    k == 0 ? 1 : 0, B, L.T, h->num_cu, st, status);
-                head_done = true;
-                ++li;
-                continue;
-            }
-            if (int rc = prof_mark(true, 1)) return rc;
-            if (hoist && f16x3)
-                wn_iaf_c_layer(lin, lout, Cf + li * rb_floats, L.c_bstride, h->d_blob + lp.off_h, L.RS, lp.dilation, B,
-                               L.T, h->num_cu, st, status);
-            else if (hoist && i + 1 == fp.layers.size()) {
-                // fp32 hoisted form, last layer of the flow: the head runs in its epilogue (iaf_layer_kernel<true, true>)
-                if (int rc = prof_mark(false, 0)) return rc;
-                const HeadF hd{h->d_blob + fp.head_off, Cf + (li + 1) * rb_floats, x, Mt, St, L.XR, L.T, k == 0 ? 1 : 0};
-                hipLaunchKernelGGL((iaf_layer_kernel<true, true>), dim3(grid), dim3(iaf_layer_threads(true)),
-                                   (IAF_LAYER_F_FLOATS + IAF_HEAD_F_FLOATS) * sizeof(float), st, lin, lout, encc,
-                                   h->d_blob + lp.off, L.RS, L.TE, lp.dilation, tiles_per_row, ntiles, Cf + li * rb_floats,
-                                   L.c_bstride, hd, StartF{});
-                head_done = true;
-                ++li;
-                continue;
-            } else if (hoist && i == 0 && start_in_layer)
-                // fp32 hoisted form, first layer of the flow: the start conv runs in front of it (iaf_layer_kernel<true, false, true>)
-                hipLaunchKernelGGL((iaf_layer_kernel<true, false, true>), dim3(grid), dim3(iaf_layer_threads(true)), IAF_LAYER_F_FLOATS * sizeof(float), st,
-                                   lin, lout, encc, h->d_blob + lp.off, L.RS, L.TE, lp.dilation, tiles_per_row, ntiles,
-                                   Cf + li * rb_floats, L.c_bstride, HeadF{}, StartF{x, h->d_blob + fp.start_off, L.XR});
-            else if (hoist)
-                hipLaunchKernelGGL((iaf_layer_kernel<true, false>), dim3(grid), dim3(iaf_layer_threads(true)), IAF_LAYER_F_FLOATS * sizeof(float), st,
-                                   lin, lout, encc, h->d_blob + lp.off, L.RS, L.TE, lp.dilation, tiles_per_row, ntiles,
-                                   Cf + li * rb_floats, L.c_bstride, HeadF{}, StartF{});
-            else if (f16x3)
-                wn_iaf_h_layer(lin, lout, enc, h->d_blob + lp.off_h, L.RS, L.TE, L.c0, lp.dilation, B, L.T, h->num_cu, st, status,
-                               (li == 0 && fuse_start) ? x : nullptr, L.XR, h->d_blob + fp.start_off);
-            else
-                hipLaunchKernelGGL((iaf_layer_kernel<false, false>), dim3(grid), dim3(256), IAF_LAYER_FLOATS * sizeof(float), st,
-                                   lin, lout, encc, h->d_blob + lp.off, L.RS, L.TE, lp.dilation, tiles_per_row,
-                                   ntiles, (const float*)nullptr, (int64_t)0, HeadF{}, StartF{});
-            float* t = lin; lin = lout; lout = t;
-            ++li;
-        }
-        if (int rc = prof_mark(false, 0)) return rc;
-        if (head_done) {
-        } else if (hoist && !f16x3)
-            hipLaunchKernelGGL(iaf_head_kernel<true>, dim3(grid), dim3(256), IAF_HEAD_F_FLOATS * sizeof(float), st, lin,
-                               encc, h->d_blob + fp.head_off, x, Mt, St, L.RS, L.TE, L.XR, L.T, k == 0 ? 1 : 0,
-                               tiles_per_row, ntiles, Cf + li * rb_floats, L.c_bstride);
-        else if (hoist)
-            wn_iaf_c_head(lin, Cf + li * rb_floats, L.c_bstride, h->d_blob + fp.head_off_h, x, Mt, St, L.RS, L.XR, L.T,
-                          k == 0 ? 1 : 0, B, h->num_cu, st);
-        else if (f16x3)
-            wn_iaf_h_head(lin, enc, h->d_blob + fp.head_off_h, x, Mt, St, L.RS, L.TE, L.c0, L.XR, L.T, k == 0 ? 1 : 0, B,
-                          h->num_cu, st);
-        else
-            hipLaunchKernelGGL(iaf_head_kernel<false>, dim3(grid), dim3(256), IAF_HEAD_FLOATS * sizeof(float), st, lin,
-                               encc, h->d_blob + fp.head_off, x, Mt, St, L.RS, L.TE, L.XR, L.T, k == 0 ? 1 : 0,
-                               tiles_per_row, ntiles, (const float*)nullptr, (int64_t)0);
+        if (int rc = run_flow(c, k, c.Cc + (cfg.share_deconv ? (size_t)rb0 * c.rb_floats : 0))) return rc;
     }
-    if (int rc = part(0)) return rc;
+    if (int rc = c.part(0)) return rc;
     {
         const int64_t nn = (int64_t)B * L.T;
-        const int Q = c.use_mu_law ? 256 : 65536;
-        hipLaunchKernelGGL(iaf_final_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, x0, Mt, St, nn,
-                           Q, c.use_mu_law, wav, idx, x_raw, mean_tot, scale_tot, status);
+        const int Q = cfg.use_mu_law ? 256 : 65536;
+        hipLaunchKernelGGL(iaf_final_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, c.st, x0, c.Mt, c.St, nn,
+                           Q, cfg.use_mu_law, wav, idx, x_raw, mean_tot, scale_tot, c.status);
         if (rand_out && rand_out != x0)
-            WN_HIP(h, hipMemcpyAsync(rand_out, x0, nn * sizeof(float), hipMemcpyDeviceToDevice, st));
+            WN_HIP(h, hipMemcpyAsync(rand_out, x0, nn * sizeof(float), hipMemcpyDeviceToDevice, c.st));
     }
-    if (int rc = part(-1)) return rc;
-    if (parts_on) {
+    if (int rc = c.part(-1)) return rc;
+    if (c.parts_on) {
         std::lock_guard<std::mutex> g(h->list_mu);
         ++h->part_calls;
     }

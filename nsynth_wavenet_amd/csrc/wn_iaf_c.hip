@@ -17,7 +17,6 @@
 // Values are the raw fp32 accumulators of the pre-scaled weights (same scale as the layer's
 // dilated-conv fragments), so they are the C-in of the layer's first MFMA.
 #include <algorithm>
-#include <cstdlib>
 
 #include "wn_internal.h"
 #include "wn_codec.h"
@@ -241,18 +240,15 @@ struct HeadArgs {
     unsigned* status;           // range-guard word of the call (every variant; wn_codec.h)
 };
 
-// W2: ONE workgroup of 512 threads per CU instead of two of 256: its two halves walk tiles independently (like two
-// workgroups) but share one weight image -- half the staging traffic, half the workgroups to dispatch.
 // DMA: the weight image arrives by LDS-DMA, requested ahead of the first tile (short launches: few tiles per workgroup).
 // NOPF (HN = 2): no register double buffer for the next tile's operands, which lets two workgroups of the 128-column
 // form share a CU (each fragment read from LDS then feeds two column blocks: half the LDS traffic of HN = 1).
-template <int HN, bool LAST = false, bool W2 = false, bool DMA = false, bool NOPF = false>
-__global__ __launch_bounds__(W2 ? 512 : 256, ((HN == 1 && !W2) || NOPF) ? 2 : 1) void iaf_layer_c_kernel(
+template <int HN, bool LAST = false, bool DMA = false, bool NOPF = false>
+__global__ __launch_bounds__(256, (HN == 1 || NOPF) ? 2 : 1) void iaf_layer_c_kernel(
     const unsigned* __restrict__ lin, unsigned* __restrict__ lout, const float* __restrict__ C, int64_t c_bstride,
     const unsigned* __restrict__ wpack, int64_t RS, int d, int tiles_per_row, int ntiles, HeadArgs ha) {
     extern __shared__ __attribute__((aligned(16))) unsigned ldsw[];
     constexpr int TILE = 64 * HN;
-    constexpr int NT = W2 ? 512 : 256;
     float amax = 0.f;
     const int lane = threadIdx.x & 63, wave = (threadIdx.x >> 6) & 3;
     const int n = lane & 15, q = lane >> 4;
@@ -306,7 +302,7 @@ __global__ __launch_bounds__(W2 ? 512 : 256, ((HN == 1 && !W2) || NOPF) ? 2 : 1)
                 for (int mb = 0; mb < 4; ++mb) ch[mb][e] = buf_ldf4(s.rh, s.vc + (e * 4 + mb) * 1024, 0);
         }
     };
-    const TileWalk tw = W2 ? tile_walk_parts(ntiles, 2, (int)(threadIdx.x >> 8)) : tile_walk(ntiles);
+    const TileWalk tw = tile_walk(ntiles);
     const int tstep = tw.step, tend = tw.end;
     float inv_m = 0.f, inv_r = 0.f;
 
@@ -452,7 +448,7 @@ __global__ __launch_bounds__(W2 ? 512 : 256, ((HN == 1 && !W2) || NOPF) ? 2 : 1)
     KOp<HN> bA[6], bB[6];
     f4 cA[4][HN], cB[4][HN], hA[4][HN], hB[4][HN];
     int tile = tw.first;
-    if (DMA && !LAST && !W2) {
+    if (DMA && !LAST) {
         // The weight image goes to LDS by LDS-DMA and is requested BEFORE the first tile's operands: loads return in
         // order, so behind the tile's loads the image would arrive a full fabric round trip late (3.3 us of a 13 us
         // workgroup life); in front of them it comes out of L2 while the tile is still on its way.
@@ -480,12 +476,12 @@ __global__ __launch_bounds__(W2 ? 512 : 256, ((HN == 1 && !W2) || NOPF) ? 2 : 1)
     } else {
     if (tile < tend) load_tile(tile, bA, cA, hA);
     // the weight image is staged AFTER the first tile's operand loads are in flight
-    stage_words<LC_A_WORDS, NT>(wpack, ldsw);
-    stage_words<LC_TAIL_WORDS, NT>(wpack + IAF_P_FLOATS, ldsw + LC_A_WORDS);
+    stage_words<LC_A_WORDS>(wpack, ldsw);
+    stage_words<LC_TAIL_WORDS>(wpack + IAF_P_FLOATS, ldsw + LC_A_WORDS);
     }
     if (LAST) {
-        stage_words<HC_A_WORDS, NT>(ha.wpack, ldsw + LC_LDS_WORDS);
-        stage_words<HC_TAIL_WORDS, NT>(ha.wpack + IAF_PH_FLOATS, ldsw + LC_LDS_WORDS + HC_A_WORDS);
+        stage_words<HC_A_WORDS>(ha.wpack, ldsw + LC_LDS_WORDS);
+        stage_words<HC_TAIL_WORDS>(ha.wpack + IAF_PH_FLOATS, ldsw + LC_LDS_WORDS + HC_A_WORDS);
         bmean = ldsf[LC_LDS_WORDS + HC_A_WORDS + 192];
         bscale = ldsf[LC_LDS_WORDS + HC_A_WORDS + 193];
         inv_h = ldsf[LC_LDS_WORDS + HC_A_WORDS + 194];
@@ -874,8 +870,6 @@ __global__ __launch_bounds__(256, 2) void iaf_head_c_kernel(
 }
 
 int pick_hn_c(int B, int64_t T, int slots) {
-    const char* force = getenv("WN_HN");
-    if (force) return atoi(force) == 1 ? 1 : 2;
     if (T % 128) return 1;
     const int64_t n1 = B * (T / 64), n2 = B * (T / 128);
     const int64_t c1 = (n1 + slots - 1) / slots, c2 = 2 * ((n2 + slots - 1) / slots);
@@ -888,8 +882,6 @@ int wn_iaf_c_set_attrs(wn_handle* h) {
     WN_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(iaf_cond_h_kernel),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES));
     WN_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(iaf_layer_c_kernel<1, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (LC_LDS_WORDS + HC_LDS_WORDS) * 4));
-    WN_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(iaf_layer_c_kernel<1, true, true>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (LC_LDS_WORDS + HC_LDS_WORDS) * 4));
     WN_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(iaf_pair_c_kernel<2, false>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, PC_LDS_WORDS * 4));
@@ -923,11 +915,6 @@ void wn_iaf_c_cond(const float* enc, const float* wblob, const unsigned* rb_off,
 // workgroups per CU of the hoisted layer / head kernels (57 KB of LDS; the 128-column variant
 // needs the whole register file)
 static int lc_slots(int hn) { return hn == 1 ? 2 : 1; }
-// 64-column tiles: one 512-thread workgroup per CU (two halves, one weight image) instead of two of 256
-static bool lc_w2() {
-    static const bool on = getenv("WN_LC_W2") && atoi(getenv("WN_LC_W2")) != 0;   // measured slower (46.3 vs 49.2 M samples/s at one utterance): off
-    return on;
-}
 
 void wn_iaf_c_layer(const float* lin, float* lout, const float* C, int64_t c_bstride, const float* wpack, int64_t RS,
                     int d, int B, int64_t T, int num_cu, hipStream_t st, unsigned* status) {
@@ -937,52 +924,34 @@ void wn_iaf_c_layer(const float* lin, float* lout, const float* C, int64_t c_bst
     const int tiles_per_row = (int)(T / (64 * hn)), ntiles = B * tiles_per_row;
     const int slots = lc_slots(hn) * num_cu;
     const int grid = ntiles < slots ? ntiles : slots;
-    if (hn == 1 && lc_w2()) {
-        const int g2 = std::min(num_cu, (ntiles + 1) / 2);
-        hipLaunchKernelGGL((iaf_layer_c_kernel<1, false, true>), dim3(g2), dim3(512), LC_LDS_WORDS * 4, st,
-                           reinterpret_cast<const unsigned*>(lin), reinterpret_cast<unsigned*>(lout), C, c_bstride,
-                           reinterpret_cast<const unsigned*>(wpack), RS, d, tiles_per_row, ntiles, hs);
-        return;
-    }
     // many tiles per workgroup (several utterances): 128-column tiles WITHOUT the register double buffer, two workgroups
     // per CU -- every fragment read from LDS feeds two column blocks (0.61 against 0.593 of the HBM peak at eight
     // utterances); with few tiles it loses (0.35 against 0.435 at one utterance: the second tile's loads are exposed)
-    static const int nopf_env = getenv("WN_LC_NOPF") ? atoi(getenv("WN_LC_NOPF")) : -1;
-    const bool nopf = nopf_env >= 0 ? nopf_env != 0 : (int64_t)B * (T / 128) >= 8 * (int64_t)num_cu;
-    if (nopf && T % 128 == 0 && !getenv("WN_HN")) {
+    const bool nopf = (int64_t)B * (T / 128) >= 8 * (int64_t)num_cu;
+    if (nopf && T % 128 == 0) {
         const int tpr = (int)(T / 128), nt2 = B * tpr, g2 = std::min(nt2, 2 * num_cu);
-        hipLaunchKernelGGL((iaf_layer_c_kernel<2, false, false, true, true>), dim3(g2), dim3(256), LC_LDS_WORDS * 4, st,
+        hipLaunchKernelGGL((iaf_layer_c_kernel<2, false, true, true>), dim3(g2), dim3(256), LC_LDS_WORDS * 4, st,
                            reinterpret_cast<const unsigned*>(lin), reinterpret_cast<unsigned*>(lout), C, c_bstride,
                            reinterpret_cast<const unsigned*>(wpack), RS, d, tpr, nt2, hs);
         return;
     }
     // few tiles per workgroup (one utterance): the start-up is a third of the workgroup's life and the DMA-staged
     // image takes 5 % off the launch; with many tiles (eight utterances) the register-staged form is 2 % faster
-    static const int dma_env = getenv("WN_LC_DMA") ? atoi(getenv("WN_LC_DMA")) : -1;
-    const bool dma = dma_env >= 0 ? dma_env != 0 : ntiles <= 4 * grid;
-    auto kern = hn == 1 ? (dma ? iaf_layer_c_kernel<1, false, false, true> : iaf_layer_c_kernel<1>)
-                        : (dma ? iaf_layer_c_kernel<2, false, false, true> : iaf_layer_c_kernel<2>);
+    const bool dma = ntiles <= 4 * grid;
+    auto kern = hn == 1 ? (dma ? iaf_layer_c_kernel<1, false, true> : iaf_layer_c_kernel<1>)
+                        : (dma ? iaf_layer_c_kernel<2, false, true> : iaf_layer_c_kernel<2>);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LC_LDS_WORDS * 4, st, reinterpret_cast<const unsigned*>(lin),
                        reinterpret_cast<unsigned*>(lout), C, c_bstride, reinterpret_cast<const unsigned*>(wpack), RS, d,
                        tiles_per_row, ntiles, hs);
 }
 
 // Last layer of a flow with the flow head in its epilogue (64-sample tiles, two workgroups per CU).
-bool wn_iaf_c_last_ok() { return !getenv("WN_NO_HEADFUSE"); }
-
 void wn_iaf_c_layer_head(const float* lin, const float* C, const float* Ch, int64_t c_bstride, const float* wpack,
                          const float* wpack_head, float* x, float* Mt, float* St, int64_t RS, int XR, int d, int first,
                          int B, int64_t T, int num_cu, hipStream_t st, unsigned* status) {
     const int tiles_per_row = (int)(T / 64), ntiles = B * tiles_per_row;
     const int grid = ntiles < 2 * num_cu ? ntiles : 2 * num_cu;
     HeadArgs ha{Ch, reinterpret_cast<const unsigned*>(wpack_head), x, Mt, St, XR, T, first, status};
-    if (lc_w2()) {
-        hipLaunchKernelGGL((iaf_layer_c_kernel<1, true, true>), dim3(std::min(num_cu, (ntiles + 1) / 2)), dim3(512),
-                           (LC_LDS_WORDS + HC_LDS_WORDS) * 4, st, reinterpret_cast<const unsigned*>(lin),
-                           static_cast<unsigned*>(nullptr), C, c_bstride, reinterpret_cast<const unsigned*>(wpack), RS, d,
-                           tiles_per_row, ntiles, ha);
-        return;
-    }
     hipLaunchKernelGGL((iaf_layer_c_kernel<1, true>), dim3(grid), dim3(256), (LC_LDS_WORDS + HC_LDS_WORDS) * 4, st,
                        reinterpret_cast<const unsigned*>(lin), static_cast<unsigned*>(nullptr), C, c_bstride,
                        reinterpret_cast<const unsigned*>(wpack), RS, d, tiles_per_row, ntiles, ha);
@@ -990,7 +959,7 @@ void wn_iaf_c_layer_head(const float* lin, const float* C, const float* Ch, int6
 
 // Two layers (dilations da, db = 2 da, 4 da <= 16) in one launch; x != nullptr: layer A is the first
 // layer of a flow (da = 1) and the start conv runs inside.
-bool wn_iaf_c_pair_ok(int da, int db) { return db == 2 * da && (db == 2 || db == 8) && !getenv("WN_NO_PAIR"); }
+bool wn_iaf_c_pair_ok(int da, int db) { return db == 2 * da && (db == 2 || db == 8); }
 
 void wn_iaf_c_pair(const float* lin, float* lout, const float* CA, const float* CB, int64_t c_bstride, const float* wA,
                    const float* wB, int64_t RS, int da, int db, int B, int64_t T, int num_cu, hipStream_t st,
@@ -998,9 +967,8 @@ void wn_iaf_c_pair(const float* lin, float* lout, const float* CA, const float* 
     const int NB = (int)(T / 16);
     const int64_t nw = (int64_t)num_cu * (PC_THREADS / 64);
     const int64_t want = std::max<int64_t>(1, nw / B);       // runs per row that give every wave one run
-    const char* mr = getenv("WN_PAIR_MINRUN");
     int rl = (int)((NB + want - 1) / want);
-    rl = std::max(rl, mr ? atoi(mr) : 3);                    // bounds the one-block warm-up of a run to a third
+    rl = std::max(rl, 3);                                    // bounds the one-block warm-up of a run to a third
     const int rpr = (NB + rl - 1) / rl;
     const int64_t ntasks = (int64_t)B * rpr;
     int grid = (int)std::min<int64_t>(num_cu, (ntasks + PC_THREADS / 64 - 1) / (PC_THREADS / 64));

@@ -15,7 +15,6 @@
 // residual 1x1 and the gated registers are its B operand (see wn_iaf.hip).
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 
 #include "wn_internal.h"
 #include "wn_codec.h"
@@ -554,8 +553,6 @@ void wn_iaf_h_start(const float* x, const float* wb, float* l, int64_t T, int XR
 static int pick_hn(int B, int64_t T, int num_cu) {
     const int64_t n1 = B * (T / 64), n2 = B * (T / 128);
     const int64_t c1 = (n1 + num_cu - 1) / num_cu, c2 = 2 * ((n2 + num_cu - 1) / num_cu);
-    const char* force = getenv("WN_HN");
-    if (force) return atoi(force) == 1 ? 1 : 2;
     return c1 < c2 ? 1 : 2;
 }
 

@@ -312,11 +312,10 @@ void wn_iaf_c_cond(const float* enc, const float* wblob, const unsigned* rb_off,
                    float* C, int64_t c_bstride, int64_t TE, int c0, int R, int B, int64_t T, int num_cu, hipStream_t st);
 void wn_iaf_c_layer(const float* lin, float* lout, const float* C, int64_t c_bstride, const float* wpack, int64_t RS,
                     int d, int B, int64_t T, int num_cu, hipStream_t st, unsigned* status);
-bool wn_iaf_c_last_ok();
 void wn_iaf_c_layer_head(const float* lin, const float* C, const float* Ch, int64_t c_bstride, const float* wpack,
                          const float* wpack_head, float* x, float* Mt, float* St, int64_t RS, int XR, int d, int first,
                          int B, int64_t T, int num_cu, hipStream_t st, unsigned* status);
-bool wn_iaf_c_pair_ok(int da, int db);
+bool wn_iaf_c_pair_ok(int da, int db);   // layers of dilations da, db can run as one launch (a function of the dilations alone)
 // ---- layer groups resident in LDS (wn_iaf_g.hip) ----
 bool wn_iaf_g_plan(const std::vector<int>& dilations, std::vector<WnGroup>& out);
 int wn_iaf_g_set_attrs(wn_handle* h);

@@ -98,17 +98,6 @@ __device__ inline TileWalk tile_walk(int ntiles) {
 #endif
     return {(int)blockIdx.x, ntiles, (int)gridDim.x};
 }
-// the same walk for a workgroup made of `parts` independent 256-thread parts (part p of workgroup w walks like
-// workgroup parts * w + p of a grid parts times as large)
-__device__ inline TileWalk tile_walk_parts(int ntiles, int parts, int part) {
-#ifndef WN_NO_XCD_TILES
-    if ((gridDim.x & 7) == 0) {
-        const int xcd = blockIdx.x & 7, per = (ntiles + 7) >> 3;
-        return {xcd * per + parts * (int)(blockIdx.x >> 3) + part, min(ntiles, (xcd + 1) * per), parts * (int)(gridDim.x >> 3)};
-    }
-#endif
-    return {parts * (int)blockIdx.x + part, ntiles, parts * (int)gridDim.x};
-}
 
 // operand words of one K-step: hi and lo plane, HN columns
 template <int HN>

@@ -366,6 +366,53 @@ def test_layer_pairs_match_single_layer_launches(monkeypatch):
     eng.close()
 
 
+def _single_layer_launches(cfgd, no_pair, no_headfuse):
+    """Single-layer launches of one per-layer hoisted call by the dispatcher's rules: layers with dilations (1, 2) and
+    (4, 8) run as one two-layer launch, a flow's last layer carries the head unless a pair took it; neither counts."""
+    count = 0
+    for n in cfgd['num_iaf_layers']:
+        d = [1 << (i % cfgd['num_stages']) for i in range(n)]
+        i = 0
+        while i < n:
+            if not no_pair and i + 1 < n and (d[i], d[i + 1]) in ((1, 2), (4, 8)):
+                i += 2
+                continue
+            if not (i + 1 == n and not no_headfuse):
+                count += 1
+            i += 1
+    return count
+
+
+def test_pair_and_headfuse_switches_change_the_launch_structure(monkeypatch):
+    """WN_NO_PAIR / WN_NO_HEADFUSE are read at the entry of every generate call and really switch: the outputs of the
+    forms agree to rounding (test above), so what is held here is the number of single-layer launches the call reports
+    through the layer-timing aid, against the count the config gives."""
+    from oracle import wavenet_np as O
+    cfgd = load_json('parallel_wavenet.json')
+    hp = O.HP(cfgd)
+    eng = _engine(cfgd, O.synth_weights(hp, 'student', seed=4321, init='tf'), 'f16x3')
+    eng.set_layer_groups(-1)
+    B, F = 1, 8
+    assert not eng.iaf_layer_groups(B, F) and eng.iaf_cond_hoisted(B, F)
+    rs = np.random.RandomState(79)
+    mel = rs.uniform(0, 1, [B, F, 80]).astype(np.float32)
+    noise = O.logistic_from_uniform(rs.uniform(1e-5, 1 - 1e-5, [B, O.iaf_length(F, hp)]))
+    figures = {(False, False): 32, (True, False): 56, (False, True): 36, (True, True): 60}
+    for (no_pair, no_headfuse), want in figures.items():
+        assert _single_layer_launches(cfgd, no_pair, no_headfuse) == want
+        for name, on in (('WN_NO_PAIR', no_pair), ('WN_NO_HEADFUSE', no_headfuse)):
+            if on:
+                monkeypatch.setenv(name, '1')
+            else:
+                monkeypatch.delenv(name, raising=False)
+        eng.profile_begin()
+        eng.iaf_generate(mel, noise)
+        _, launches = eng.profile_end()
+        assert eng.range_fallbacks == 0
+        assert launches == want, (no_pair, no_headfuse, launches)
+    eng.close()
+
+
 def test_layer_groups_match_per_layer_launches(monkeypatch):
     """The default hoisted form runs every dilation cycle as TWO launches of the layer-group kernel (wn_iaf_g.hip): a
     natural group (1, 2, 4, 8, 16) with its 62-sample causal halo recomputed per segment, and a decimated group
