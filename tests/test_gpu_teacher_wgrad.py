@@ -59,17 +59,20 @@ class _WOracle(TS._Oracle):
 
 
 class _WCase(object):
-    def __init__(self, R, eng, shape, tag='mol', seeds=None):
+    def __init__(self, R, eng, shape, tag='mol', seeds=None, cfgd=None, near_max=None):
+        """cfgd: another model than the golden one of `tag` (same seed and init); near_max: its cap on the near-tie count"""
         import torch
         self.B, self.F, self.T = shape
-        (cfgd, seed, init) = D.golden_case(R, tag)[1]
+        (gold, seed, init) = D.golden_case(R, tag)[1]
+        cfgd = gold if cfgd is None else cfgd
+        near_max = NEAR_MAX if near_max is None else near_max
         mel, x = TS._inputs(self.F, self.T, seeds or TS.ROW_SEEDS[shape])
         self.X, self.MEL = torch.as_tensor(x).cuda(), torch.as_tensor(mel).cuda()
         self.ora = _WOracle(cfgd, seed, init, mel, x)
-        assert self.ora.near <= NEAR_MAX, (shape, self.ora.near)
+        assert self.ora.near <= near_max, (shape, self.ora.near)
         self.out, self.tape = eng.teacher_forward_train_tape(self.X, self.MEL)
         self.ora.masks(self.tape)
-        assert self.ora.nflip <= NEAR_MAX, (shape, self.ora.nflip)
+        assert self.ora.nflip <= near_max, (shape, self.ora.nflip)
         self.ow = int(self.out.shape[2])
 
     def cotangent(self, seed):

@@ -152,9 +152,9 @@ def _net(cfgd, w, precision=None):
 class _Pair(object):
     """handle A loaded from w0 and re-packed with w1, and a fresh handle B loaded from w1"""
 
-    def __init__(self, R, tag):
+    def __init__(self, R, tag, variants=None):
         from oracle import wavenet_np as O
-        over, self.precision = VARIANTS[tag]
+        over, self.precision = (VARIANTS if variants is None else variants)[tag]
         cfgd, seed, init = D.golden_case(R, 'mol')[1]
         self.cfgd = dict(json.loads(json.dumps(cfgd)), **over)
         self.w0 = O.synth_weights(O.HP(self.cfgd), 'teacher', seed=seed, init=init)
@@ -172,12 +172,11 @@ def R():
     return np.load(TS.GOLD)
 
 
-def _outputs(net, cfgd):
+def _outputs(net, cfgd, shape=(3, 2, 260), seeds=None):
     """everything the handle's packs feed, on fixed inputs: {name: device tensor}"""
     import torch
     eng = net.engine
-    shape = (3, 2, 260)
-    mel, x = TS._inputs(shape[1], shape[2], TS.ROW_SEEDS[shape])
+    mel, x = TS._inputs(shape[1], shape[2], seeds or TS.ROW_SEEDS[shape])
     X, MEL = torch.as_tensor(x).cuda(), torch.as_tensor(mel).cuda()
     out = {'teacher_forward': eng.teacher_forward(X, MEL), 'deconv': eng.deconv(MEL)}
     rs = np.random.RandomState(31)
@@ -206,8 +205,16 @@ def test_repack_equals_a_fresh_handle(R, tag):
     deconv and every tensor of loss_and_weight_grads(upsampler=True).  Then up_params=None, in the direction this handle allows
     after the first call: the stack alone is set back to w0, so the upsampler's outputs stay those of w1 while the stack follows
     w0 -- compared with a fresh handle loaded from that mixture."""
+    _repack_check(_Pair(R, tag))
+
+
+def _repack_check(pr, shape=(3, 2, 260), seeds=None):
+    """the body of test_repack_equals_a_fresh_handle on a pair of handles, with _outputs run at `shape`"""
     import torch
-    pr = _Pair(R, tag)
+    _plain = globals()['_outputs']
+
+    def _outputs(net, cfgd):
+        return _plain(net, cfgd, shape, seeds)
     try:
         ea = pr.a.engine
         before = _outputs(pr.a, pr.cfgd)
