@@ -447,6 +447,34 @@ WN_API int wn_teacher_backward_weights(wn_handle* h, const void* tape, size_t ta
                                        int F, int64_t T, float* grads, size_t grads_floats, float* d_encoding, float* d_wav,
                                        void* ws, size_t ws_bytes, void* stream);
 
+/* ---- dropout of the teacher's training pass: tf.layers.dropout(training=True) of wavenet.py:204-239, 276-278.
+ * wn_config does not carry the dropout keys: mode, seed and rate come per call.
+ *   WN_DROPOUT_INPUTS  site 0 = conv_dropout on l_0 (width channels), site 1 = skip_dropout on s = skip_start(l_0), both applied
+ *                      AFTER skip_start has read the undropped l_0;
+ *   WN_DROPOUT_ALL     site 0 = conv_dropout on l_0 before skip_start reads it, site i = res_dropout_i on the output of
+ *                      residual layer i = 1 .. num_layers - 1 (the last layer's output is read by nothing).
+ * The mask is a stateless counter hash: element (b, c, t) of `site` is kept where word (t & 3) of Philox4x32-10 with
+ * key = seed and counter = (t >> 2, c, site, b) is >= thr = min(2^32 - 1, floor(rate 2^32 + 0.5)) -- a function of these
+ * values alone, whatever the launch geometry.  A kept element is fp32(v / fp32(1 - rate)), a dropped one is 0.
+ * rate = 0 keeps everything and gives the bits of the calls without dropout. */
+#define WN_DROPOUT_INPUTS 1
+#define WN_DROPOUT_ALL    2
+/* Bytes of a dropout training tape: the training tape (the same bytes at the same offsets), and for WN_DROPOUT_INPUTS one more
+ * l row behind it, the undropped l_0 that skip_start/W's gradient multiplies.  0 for a handle the work call refuses or an
+ * unknown mode. */
+WN_API size_t wn_teacher_train_tape_dropout_bytes(const wn_handle* h, int B, int F, int64_t T, int mode);
+/* wn_teacher_forward_train_tape (same arguments, same workspace) with dropout: out_params are those of the dropped forward.
+ * The tape remembers mode, seed and rate: wn_teacher_backward_weights and wn_teacher_backward_input accept it and apply the
+ * same masks to the cotangents, with their own signatures and workspace sizes.  Refuses what wn_teacher_forward_train_tape
+ * refuses, a rate outside [0, 1) and an unknown mode (WN_EINVAL). */
+WN_API int wn_teacher_forward_train_tape_dropout(wn_handle* h, const float* wav, const float* mel, int B, int F, int64_t T,
+                                                 float* out_params, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes,
+                                                 void* stream, int mode, uint64_t seed, double rate);
+/* The keep bits themselves, for tests: keep [B][T][C] bytes (1 = kept) of `site`, written by a kernel that only calls the
+ * hash the passes above call.  No handle. */
+WN_API int wn_teacher_dropout_keep(uint64_t seed, int site, int B, int C, int64_t T, double rate, unsigned char* keep,
+                                   void* stream);
+
 /* ---- reverse pass of the upsampler: the gradients of trans_conv_j/kernel and trans_conv_j/bias of the deconv
  * stack `scope` ("" for a teacher; "iaf_share", "iaf_1" ... for a student, as in wn_deconv) from mel [B,F,n_mel] and a
  * cotangent d_enc [B, F frame_shift, deconv_width] of wn_deconv's output, e.g. d_encoding of wn_teacher_backward_weights.

@@ -2,6 +2,7 @@
 //   wn_teacher.hip        the GEMM kernel, the packing, the forward, log_prob and its gradient
 //   wn_teacher_bwd.hip    the tape and its registry, the reverse pass (input VJP)
 //   wn_teacher_wgrad.hip  the weight-gradient GEMM, its product tables and the training tape
+//   wn_teacher_dropout.hip  the dropout mask kernels of the training forward and the reverse pass
 #pragma once
 #include "wn_internal.h"
 
@@ -112,11 +113,20 @@ inline TapeLayout tape_layout(const wn_handle* h, int B, long long T) {
     L.total = L.g + h->teacher.layers.size() * cols * c.gate_width * sizeof(float);
     return L;
 }
+// dropout of a training forward and of the reverse passes over its tape (mode 0: none)
+struct TgDropout {
+    int mode = 0;               // WN_DROPOUT_INPUTS / WN_DROPOUT_ALL
+    uint64_t seed = 0;
+    uint32_t thr = 0;           // an element is kept where its hash word is >= thr
+    float keep = 1.0f;          // fp32(1 - rate): a kept element is v / keep
+};
 // where the forward writes what a tape keeps; a null member stays in the call's workspace (all null: wn_teacher_forward)
 struct TgTape {
     float *s = nullptr, *h1 = nullptr, *g = nullptr;      // plain tape
     unsigned* l = nullptr;                                // training tape: the layer inputs l_i, one slot per layer
     float *enc = nullptr, *xs = nullptr;                  //   ... the conditioning and the scaled input row
+    unsigned* lraw = nullptr;                             // dropout_inputs: the undropped l_0 (slot 0 of l holds the dropped one)
+    TgDropout drop;
 };
 inline TgTape tape_regions(const TapeLayout& TL, void* tape) {
     char* tb = reinterpret_cast<char*>(tape);
@@ -153,7 +163,9 @@ int tg_forward(wn_handle* h, const char* fn, const float* wav, const float* mel,
 // what the VJP-side calls refuse (the distillation losses' own refusals, wn_distill.hip)
 int tb_check(wn_handle* h, const char* fn);
 // registry check shared by the reverse-pass calls; *F receives the frame count of a training tape (0: a plain tape)
-int tb_tape_check(wn_handle* h, const char* fn, const void* tape, size_t tape_bytes, int B, int64_t T, int* F);
+// and *drop the dropout its forward applied
+int tb_tape_check(wn_handle* h, const char* fn, const void* tape, size_t tape_bytes, int B, int64_t T, int* F,
+                  TgDropout* drop = nullptr);
 // a tape-writing forward once its checks have passed: the header (magic, B, T, F), the forward into `regions`, and -- if that
 // succeeded -- the registry entry of the tape (a training tape under TB_MAGIC_TRAIN, a plain one otherwise)
 int tb_tape_forward(wn_handle* h, const char* fn, uint32_t magic, const float* wav, const float* mel, int B, int F, int64_t T,
@@ -162,11 +174,21 @@ int tb_tape_forward(wn_handle* h, const char* fn, uint32_t magic, const float* w
 // With wg the weight-gradient products, the d enc GEMMs and their reductions are issued between those launches, where
 // the cotangents they read are complete; they write nothing the input VJP reads, so d_wav is the same bits.
 struct TwCtx;
+// dr: the dropout of the tape's forward; its masks are applied to the cotangents where the forward applied them.
 int tb_reverse(wn_handle* h, const void* tape, const float* d_out_params, int B, int64_t T, float* d_wav, void* ws,
-               void* stream, const TwCtx* wg);
+               void* stream, const TwCtx* wg, const TgDropout& dr);
 
 // ---- wn_teacher_wgrad.hip: the weight-gradient side of the reverse pass, called where its operands are complete ----
 int tw_aux(wn_handle* h, const TwCtx& w, hipStream_t st);                  // before anything else: aux rows, d enc zeroed
 int tw_head(wn_handle* h, const TwCtx& w, hipStream_t st, int stage);      // stage 0: d h1 is complete;  1: ds is complete
 int tw_layer(wn_handle* h, const TwCtx& w, size_t li, hipStream_t st);     // dl = d l_{li+1} and dd_li are complete
 int tw_tail(wn_handle* h, const TwCtx& w, hipStream_t st);                 // dl = d l_0
+
+// ---- wn_teacher_dropout.hip: the mask kernels ----
+uint32_t wn_dropout_threshold(double rate);     // min(2^32 - 1, floor(rate 2^32 + 0.5))
+// G4 rows [B][C][rowlen] with t = 0 at column col0 (a multiple of 4): dst = mask(src) on columns [col0, col0 + T), the left
+// pad copied, zeros from column col0 + T on.  dst == src: in place.
+void wn_dropout_g4(const unsigned* src, unsigned* dst, int B, int C, long long rowlen, long long col0, long long T,
+                   const TgDropout& dr, int site, hipStream_t st);
+// accumulator-layout rows [B][Tp / 16][C / 16][64][4] in place, on columns < T
+void wn_dropout_acc(float* s, int B, int C, long long Tp, long long T, const TgDropout& dr, int site, hipStream_t st);

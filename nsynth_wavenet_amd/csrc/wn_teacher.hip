@@ -709,6 +709,11 @@ int tg_forward(wn_handle* h, const char* fn, const float* wav, const float* mel,
     float* xs = tape.xs ? tape.xs : reinterpret_cast<float*>(base + L.xs);
     const int W = c.width, S = c.skip_width, H = c.gate_width / 2, Cd = c.deconv_width;
     const TeacherPack& P = h->teacher;
+    // dropout (training tapes only).  dropout_inputs: conv_start writes the raw l_0 row, skip_start reads it, and
+    // slot 0 receives its masked copy;  dropout_all: slot 0 and every layer's output are masked in place
+    const TgDropout& dr = tape.drop;
+    const bool drop_in = dr.mode == WN_DROPOUT_INPUTS, drop_all = dr.mode == WN_DROPOUT_ALL;
+    unsigned* l_start = drop_in ? tape.lraw : l;
 
     // conditioning (wavenet.py:214-216), G4 rows of TE columns
     int rc = wn_run_deconv(h, 0, mel, B, F, enc, L.TE, base + L.scratch, st, true);
@@ -718,8 +723,9 @@ int tg_forward(wn_handle* h, const char* fn, const float* wav, const float* mel,
         dim3 g((unsigned)((TG_XP + L.Tp + 255) / 256), B);
         hipLaunchKernelGGL(tg_input_kernel, g, dim3(256), 0, st, wav, xs, (long long)T, L.Tp, c.use_mu_law);
         dim3 g2((unsigned)((L.RS + 255) / 256), W / 8, B);
-        hipLaunchKernelGGL(tg_start_kernel, g2, dim3(256), 0, st, xs, h->d_blob + h->ar.start_off, l, W, L.Tp, L.RS);
+        hipLaunchKernelGGL(tg_start_kernel, g2, dim3(256), 0, st, xs, h->d_blob + h->ar.start_off, l_start, W, L.Tp, L.RS);
     }
+    if (drop_all) wn_dropout_g4(l, l, B, W, L.RS, IAF_LP, T, dr, 0, st);        // conv_dropout (wavenet.py:229-230)
     auto seg_acc = [&](const float* p, int nks) {
         TgSeg sg;
         sg.base = reinterpret_cast<const unsigned*>(p); sg.bstride = (long long)S * L.Tp; sg.rowlen = S / 16;
@@ -733,9 +739,13 @@ int tg_forward(wn_handle* h, const char* fn, const float* wav, const float* mel,
     // s = skip_start(l)  (wavenet.py:231-233)
     {
         TgArgs a = tg_pack_args(h, P.skip_start, T);
-        a.seg[0] = seg_l; a.nseg = 1;
+        a.seg[0] = seg_l; a.seg[0].base = l_start; a.nseg = 1;
         a.oacc = s; a.oacc_bstride = (long long)S * L.Tp; a.oacc_nmb = S / 16;
         wn_tg_launch(TG_EPI_ACC, a, P.skip_start.mtiles, B, L.Tp, st);
+    }
+    if (drop_in) {      // conv_dropout on l, skip_dropout on s (wavenet.py:204-206, 237-239)
+        wn_dropout_g4(l_start, l, B, W, L.RS, IAF_LP, T, dr, 0, st);
+        wn_dropout_acc(s, B, S, L.Tp, T, dr, 1, st);
     }
     for (size_t li = 0; li < P.layers.size(); ++li) {
         const TeacherLayerPack& tl = P.layers[li];
@@ -769,6 +779,8 @@ int tg_forward(wn_handle* h, const char* fn, const float* wav, const float* mel,
             a.res_mtiles = W / 64;
             wn_tg_launch(TG_EPI_RS, a, tl.rs.mtiles, B, L.Tp, st);
         }
+        // res_dropout (wavenet.py:276-278); the last layer's output is read by nothing
+        if (drop_all && li + 1 < P.layers.size()) wn_dropout_g4(l, l, B, W, L.RS, IAF_LP, T, dr, (int)li + 1, st);
     }
     {   // out1(relu(s)) + mel_cond_out1(enc)  (wavenet.py:283-289)
         TgArgs a = tg_pack_args(h, P.out1, T);

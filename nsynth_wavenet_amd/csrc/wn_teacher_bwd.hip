@@ -20,6 +20,7 @@ struct TapeRec {
     int B;
     long long T;
     int F;              // > 0: a training tape (wn_teacher_forward_train_tape) for F mel frames
+    TgDropout drop;     // the dropout its forward applied (wn_teacher_forward_train_tape_dropout; mode 0: none)
 };
 std::mutex g_tape_mu;
 std::unordered_map<const void*, TapeRec> g_tapes;   // tape address -> the handle and shape that last wrote it
@@ -147,7 +148,7 @@ int tb_tape_forward(wn_handle* h, const char* fn, uint32_t magic, const float* w
                        reinterpret_cast<unsigned*>(tape));
     if (int rc = tg_forward(h, fn, wav, mel, B, F, T, out_params, ws, ws_bytes, regions, stream)) return rc;
     std::lock_guard<std::mutex> lk(g_tape_mu);
-    g_tapes[tape] = TapeRec{ser, B, (long long)T, magic == TB_MAGIC_TRAIN ? F : 0};
+    g_tapes[tape] = TapeRec{ser, B, (long long)T, magic == TB_MAGIC_TRAIN ? F : 0, regions.drop};
     return WN_OK;
 }
 
@@ -164,7 +165,8 @@ extern "C" int wn_teacher_forward_tape(wn_handle* h, const float* wav, const flo
     return tb_tape_forward(h, fn, TB_MAGIC, wav, mel, B, F, T, out_params, tape, tape_regions(TL, tape), ws, ws_bytes, stream);
 }
 
-int tb_tape_check(wn_handle* h, const char* fn, const void* tape, size_t tape_bytes, int B, int64_t T, int* F) {
+int tb_tape_check(wn_handle* h, const char* fn, const void* tape, size_t tape_bytes, int B, int64_t T, int* F,
+                  TgDropout* drop) {
     const TapeLayout TL = tape_layout(h, B, T);
     if (tape_bytes < TL.total)
         return wn_fail(h, WN_EINVAL, "%s: a tape of %zu bytes cannot hold B = %d, T = %lld (%zu bytes)", fn, tape_bytes, B,
@@ -177,11 +179,12 @@ int tb_tape_check(wn_handle* h, const char* fn, const void* tape, size_t tape_by
         return wn_fail(h, WN_EINVAL, "%s: the tape holds B = %d, T = %lld, not B = %d, T = %lld", fn, it->second.B,
                        it->second.T, B, (long long)T);
     *F = it->second.F;
+    if (drop) *drop = it->second.drop;
     return WN_OK;
 }
 
 int tb_reverse(wn_handle* h, const void* tape, const float* d_out_params, int B, int64_t T, float* d_wav, void* ws,
-               void* stream, const TwCtx* wg) {
+               void* stream, const TwCtx* wg, const TgDropout& dr) {
     const BLayout L = b_layout(h, B, T);
     const wn_config& c = h->cfg;
     const int W = c.width, S = c.skip_width, G = c.gate_width, H = G / 2;
@@ -222,8 +225,12 @@ int tb_reverse(wn_handle* h, const void* tape, const float* d_out_params, int B,
     }
     if (wg)
         if (int rc = tw_head(h, *wg, st, 1)) return rc;
+    const bool drop_in = dr.mode == WN_DROPOUT_INPUTS, drop_all = dr.mode == WN_DROPOUT_ALL;
     for (size_t li = P.layers.size(); li-- > 0;) {
         const TeacherLayerPack& tl = P.layers[li];
+        // res_dropout of layer li's output: dl = d l_{li+1} passes the mask before the residual conv and the
+        // identity path see it; the last layer's output was neither masked nor read
+        if (drop_all && li + 1 < P.layers.size()) wn_dropout_g4(w.dl, w.dl, B, W, Tp, 0, T, dr, (int)li + 1, st);
         {   // dm = W_res^T dl + W_skip^T ds -> dd through the gate derivative  (wavenet.py:264-277 transposed)
             TgArgs a = args(tl.rs_t, w.dd, (long long)G * L.RD, L.RD, G);
             a.seg[0] = seg_dl; a.seg[1] = seg_ds; a.nseg = 2;
@@ -241,12 +248,17 @@ int tb_reverse(wn_handle* h, const void* tape, const float* d_out_params, int B,
             wn_tg_launch(TG_EPI_RS, a, tl.gate_t.mtiles, B, Tp, st);
         }
     }
+    if (drop_in) {      // l_0 and s = skip_start(l_0) were masked after skip_start read the raw l_0: ds reaches it masked
+        wn_dropout_g4(w.dl, w.dl, B, W, Tp, 0, T, dr, 0, st);
+        wn_dropout_g4(w.ds, w.ds, B, S, Tp, 0, T, dr, 1, st);
+    }
     {   // dl0 += W_skip_start^T ds  (wavenet.py:231-233)
         TgArgs a = args(P.skip_start_t, w.dl, (long long)W * Tp, Tp, W);
         a.seg[0] = seg_ds; a.nseg = 1;
         a.res_mtiles = W / 64;
         wn_tg_launch(TG_EPI_RS, a, P.skip_start_t.mtiles, B, Tp, st);
     }
+    if (drop_all) wn_dropout_g4(w.dl, w.dl, B, W, Tp, 0, T, dr, 0, st);         // skip_start read the masked l_0
     if (wg)
         if (int rc = tw_tail(h, *wg, st)) return rc;
     if (d_wav)
@@ -262,9 +274,10 @@ extern "C" int wn_teacher_backward_input(wn_handle* h, const void* tape, size_t 
     if (int rc = tb_check(h, fn)) return rc;
     if (B < 1 || T < 1 || !tape || !d_out_params || !d_wav || !ws) return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
     int F = 0;
-    if (int rc = tb_tape_check(h, fn, tape, tape_bytes, B, T, &F)) return rc;
+    TgDropout dr;
+    if (int rc = tb_tape_check(h, fn, tape, tape_bytes, B, T, &F, &dr)) return rc;
     const BLayout L = b_layout(h, B, T);
     if (ws_bytes < L.total) return wn_fail(h, WN_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, L.total);
     const WnWork work(h);
-    return tb_reverse(h, tape, d_out_params, B, T, d_wav, ws, stream, nullptr);
+    return tb_reverse(h, tape, d_out_params, B, T, d_wav, ws, stream, nullptr, dr);
 }

@@ -236,10 +236,11 @@ __global__ __launch_bounds__(256) void tw_denc_kernel(const unsigned* __restrict
 }  // namespace
 
 struct TrainLayout {
-    size_t l, enc, xs, total;       // after the plain tape's regions
+    size_t l, enc, xs, lraw, total; // after the plain tape's regions
     long long RS, TE;
 };
-static TrainLayout train_layout(const wn_handle* h, int B, int F, long long T) {
+// raw: a dropout_inputs tape, which keeps the undropped l_0 row behind everything else
+static TrainLayout train_layout(const wn_handle* h, int B, int F, long long T, bool raw = false) {
     const wn_config& c = h->cfg;
     const TapeLayout TL = tape_layout(h, B, T);
     TrainLayout L;
@@ -250,6 +251,7 @@ static TrainLayout train_layout(const wn_handle* h, int B, int F, long long T) {
     L.l = carve(h->teacher.layers.size() * (size_t)B * c.width * L.RS);
     L.enc = carve((size_t)B * c.deconv_width * (L.TE + TG_TN) + 64);      // the forward's over-read margin (t_layout)
     L.xs = carve((size_t)B * (TG_XP + TL.Tp));
+    L.lraw = carve(raw ? (size_t)B * c.width * L.RS : 0);
     L.total = o;
     return L;
 }
@@ -261,6 +263,7 @@ static TgTape train_regions(const wn_handle* h, const TrainLayout& TR, int B, lo
     t.l = reinterpret_cast<unsigned*>(tb + TR.l);
     t.enc = reinterpret_cast<float*>(tb + TR.enc);
     t.xs = reinterpret_cast<float*>(tb + TR.xs);
+    if (TR.total > TR.lraw) t.lraw = reinterpret_cast<unsigned*>(tb + TR.lraw);
     return t;
 }
 
@@ -469,7 +472,8 @@ int tw_tail(wn_handle* h, const TwCtx& w, hipStream_t st) {
     const int W = c.width, S = c.skip_width;
     const long long Tp = w.L.Tp, RS = w.TR.RS;
     TwBatch k;
-    const long long sw = k.add(w.rw.ds, S, Tp, w.tp.l, W, RS, IAF_LP);
+    // skip_start read the raw l_0 where dropout_inputs put the dropped one into slot 0
+    const long long sw = k.add(w.rw.ds, S, Tp, w.tp.lraw ? w.tp.lraw : w.tp.l, W, RS, IAF_LP);
     const long long sb = k.add(w.rw.ds, S, Tp, w.aux, TW_AUXC, Tp, 0);
     const long long cs = k.add(w.rw.dl, W, Tp, w.aux, TW_AUXC, Tp, 0);
     k.red(sw, W, S, S, grad_off(w.tab, "skip_start/W"), S);
@@ -536,6 +540,38 @@ extern "C" int wn_teacher_forward_train_tape(wn_handle* h, const float* wav, con
                            ws_bytes, stream);
 }
 
+// the dropout calls' own refusals
+static int tw_dropout_check(wn_handle* h, const char* fn, int mode, double rate) {
+    if (mode != WN_DROPOUT_INPUTS && mode != WN_DROPOUT_ALL)
+        return wn_fail(h, WN_EINVAL, "%s: unknown dropout mode %d (WN_DROPOUT_INPUTS or WN_DROPOUT_ALL)", fn, mode);
+    if (!(rate >= 0.0 && rate < 1.0)) return wn_fail(h, WN_EINVAL, "%s: dropout rate %g is outside [0, 1)", fn, rate);
+    return WN_OK;
+}
+
+extern "C" size_t wn_teacher_train_tape_dropout_bytes(const wn_handle* h, int B, int F, int64_t T, int mode) {
+    if (!tw_supported(h) || B < 1 || F < 1 || T < 1 || (mode != WN_DROPOUT_INPUTS && mode != WN_DROPOUT_ALL)) return 0;
+    return train_layout(h, B, F, T, mode == WN_DROPOUT_INPUTS).total;
+}
+
+extern "C" int wn_teacher_forward_train_tape_dropout(wn_handle* h, const float* wav, const float* mel, int B, int F, int64_t T,
+                                                     float* out_params, void* tape, size_t tape_bytes, void* ws,
+                                                     size_t ws_bytes, void* stream, int mode, uint64_t seed, double rate) {
+    const char* fn = "wn_teacher_forward_train_tape_dropout";
+    if (int rc = tw_check(h, fn)) return rc;
+    if (int rc = tw_dropout_check(h, fn, mode, rate)) return rc;
+    if (int rc = tg_forward_check(h, fn, wav, mel, B, F, T, out_params, ws)) return rc;
+    if (!tape) return wn_fail(h, WN_EINVAL, "%s: bad argument (tape)", fn);
+    const TrainLayout TR = train_layout(h, B, F, T, mode == WN_DROPOUT_INPUTS);
+    if (tape_bytes < TR.total) return wn_fail(h, WN_ENOMEM, "%s: tape %zu < %zu bytes", fn, tape_bytes, TR.total);
+    const WnWork work(h);
+    TgTape regions = train_regions(h, TR, B, T, tape);
+    regions.drop.mode = mode;
+    regions.drop.seed = seed;
+    regions.drop.thr = wn_dropout_threshold(rate);
+    regions.drop.keep = (float)(1.0 - rate);
+    return tb_tape_forward(h, fn, TB_MAGIC_TRAIN, wav, mel, B, F, T, out_params, tape, regions, ws, ws_bytes, stream);
+}
+
 extern "C" int wn_teacher_backward_weights(wn_handle* h, const void* tape, size_t tape_bytes, const float* d_out_params, int B,
                                            int F, int64_t T, float* grads, size_t grads_floats, float* d_encoding, float* d_wav,
                                            void* ws, size_t ws_bytes, void* stream) {
@@ -543,13 +579,14 @@ extern "C" int wn_teacher_backward_weights(wn_handle* h, const void* tape, size_
     if (int rc = tw_check(h, fn)) return rc;
     if (B < 1 || F < 1 || T < 1 || !tape || !d_out_params || !grads || !ws) return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
     int tape_F = 0;
-    if (int rc = tb_tape_check(h, fn, tape, tape_bytes, B, T, &tape_F)) return rc;
+    TgDropout dr;
+    if (int rc = tb_tape_check(h, fn, tape, tape_bytes, B, T, &tape_F, &dr)) return rc;
     if (tape_F == 0)
         return wn_fail(h, WN_EINVAL, "%s: a plain tape of wn_teacher_forward_tape holds no layer inputs and no conditioning; "
                        "the weight gradients need a tape of wn_teacher_forward_train_tape", fn);
     if (tape_F != F) return wn_fail(h, WN_EINVAL, "%s: the tape holds F = %d mel frames, not %d", fn, tape_F, F);
     TwCtx w;
-    w.TR = train_layout(h, B, F, T);
+    w.TR = train_layout(h, B, F, T, dr.mode == WN_DROPOUT_INPUTS);
     if (tape_bytes < w.TR.total)
         return wn_fail(h, WN_EINVAL, "%s: a tape of %zu bytes cannot hold the training tape of B = %d, F = %d, T = %lld "
                        "(%zu bytes)", fn, tape_bytes, B, F, (long long)T, w.TR.total);
@@ -573,7 +610,7 @@ extern "C" int wn_teacher_backward_weights(wn_handle* h, const void* tape, size_
     w.tp = train_regions(h, w.TR, B, T, const_cast<void*>(tape));
     w.grads = grads;
     w.want_denc = d_encoding != nullptr;
-    if (int rc = tb_reverse(h, tape, d_out_params, B, T, d_wav, ws, stream, &w)) return rc;
+    if (int rc = tb_reverse(h, tape, d_out_params, B, T, d_wav, ws, stream, &w, dr)) return rc;
     if (d_encoding) {
         hipStream_t st = reinterpret_cast<hipStream_t>(stream);
         const int Cd = h->cfg.deconv_width;

@@ -398,10 +398,28 @@ class Engine(object):
         """[(tf variable name, float offset, TF shape)] of the flat gradient buffer, in the library's fixed order."""
         return self._grad_table(self.lib.wn_teacher_grad_count, self.lib.wn_teacher_grad_info)
 
-    def teacher_forward_train_tape(self, wav, mel):
+    DROPOUT_MODES = {'dropout_inputs': 1, 'dropout_all': 2}        # WN_DROPOUT_INPUTS, WN_DROPOUT_ALL
+
+    def teacher_dropout_keep(self, seed, site, B, C, T, rate):
+        """The keep bits of dropout site `site` as the device evaluates them: bool [B,T,C], written by a kernel
+        that only calls the hash the training passes call.  train.dropout_keep is its numpy twin."""
+        keep = torch.empty((int(B), int(T), int(C)), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.wn_teacher_dropout_keep(ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), int(site), int(B), int(C),
+                                                         int(T), float(rate), _ptr(keep), self._stream()))
+        return keep.bool()
+
+    def teacher_forward_train_tape(self, wav, mel, dropout=None):
         """teacher_forward (bit-identical out_params) that also returns the TRAINING tape teacher_backward_weights reads: the
         tape of teacher_forward_tape plus every layer's input, the conditioning and the scaled audio.  teacher_backward_input
-        accepts it too.  The engine remembers the tape's frame count by its address."""
+        accepts it too.  The engine remembers the tape's frame count by its address.
+        dropout = (mode, seed, rate), mode 'dropout_inputs' or 'dropout_all' (or WN_DROPOUT_INPUTS / WN_DROPOUT_ALL): the
+        forward of train_wavenet.py with tf.layers.dropout(training=True) under the counter-hash mask of DESIGN.md 17;
+        out_params are those of the dropped forward and the reverse calls apply the same masks.  None: no dropout."""
+        if dropout is not None:
+            mode, seed, rate = dropout
+            mode = self.DROPOUT_MODES.get(mode, 0) if isinstance(mode, str) else int(mode)    # unknown: the library refuses
+            seed = ctypes.c_uint64(int(seed) & (2 ** 64 - 1))
         wav, mel = self._dev(wav), self._dev(mel)
         if wav.dim() != 2 or mel.dim() != 3 or wav.shape[0] != mel.shape[0]:
             raise ValueError('teacher_forward_train_tape: wav must be [B,T] and mel [B,F,n_mel] with equal B')
@@ -411,11 +429,18 @@ class Engine(object):
         B, T, F = int(wav.shape[0]), int(wav.shape[1]), int(mel.shape[1])
         out = torch.empty((B, T, cfg.teacher_out_width(self.hp)), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            tape = torch.empty(max(self.teacher_train_tape_bytes(B, F, T), 256), dtype=torch.uint8, device=self.device)
+            nb = self.teacher_train_tape_bytes(B, F, T) if dropout is None else \
+                int(self.lib.wn_teacher_train_tape_dropout_bytes(self._h, B, F, T, mode))
+            tape = torch.empty(max(nb, 256), dtype=torch.uint8, device=self.device)
             ws = torch.empty(max(int(self.lib.wn_teacher_workspace_bytes(self._h, B, F, T)), 256), dtype=torch.uint8,
                              device=self.device)
-            self._check(self.lib.wn_teacher_forward_train_tape(self._h, _ptr(wav), _ptr(mel), B, F, T, _ptr(out), _ptr(tape),
-                                                               tape.numel(), _ptr(ws), ws.numel(), self._stream()))
+            if dropout is None:
+                self._check(self.lib.wn_teacher_forward_train_tape(self._h, _ptr(wav), _ptr(mel), B, F, T, _ptr(out), _ptr(tape),
+                                                                   tape.numel(), _ptr(ws), ws.numel(), self._stream()))
+            else:
+                self._check(self.lib.wn_teacher_forward_train_tape_dropout(
+                    self._h, _ptr(wav), _ptr(mel), B, F, T, _ptr(out), _ptr(tape), tape.numel(), _ptr(ws), ws.numel(),
+                    self._stream(), mode, seed, float(rate)))
         # the library identifies a tape by its address (a copy is refused), so the frame count is kept by address too
         if len(self._train_frames) >= 256:
             self._train_frames.clear()

@@ -31,6 +31,53 @@ def scheduled_lr(lr, global_step):
     return float(cur)
 
 
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_U32 = np.uint64(0xFFFFFFFF)
+
+
+def _philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 on uint64 arrays that hold 32-bit words (broadcast against each other) -> the four output words"""
+    c0, c1, c2, c3 = [np.asarray(c, np.uint64) for c in (c0, c1, c2, c3)]
+    for _ in range(10):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2                   # 32 x 32 -> 64 bits, exact in uint64
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0), p1 & _U32, (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1), p0 & _U32
+        k0, k1 = (k0 + _PHILOX_W0) & 0xFFFFFFFF, (k1 + _PHILOX_W1) & 0xFFFFFFFF
+    return c0, c1, c2, c3
+
+
+def dropout_threshold(rate):
+    """min(2^32 - 1, floor(rate 2^32 + 0.5)): an element is kept where its 32-bit hash word is >= this"""
+    if not 0.0 <= rate < 1.0:
+        raise ValueError('dropout rate {} is outside [0, 1)'.format(rate))
+    return min(2 ** 32 - 1, int(math.floor(float(rate) * 2.0 ** 32 + 0.5)))
+
+
+def dropout_keep(seed, site, B, C, T, rate):
+    """The dropout mask of the device-side training step, on the host: bool [B, T, C], True = kept.
+    Element (b, c, t) of site `site` is kept where word t % 4 of Philox4x32-10(key = the 64-bit seed, counter =
+    (t // 4, c, site, b)) is >= dropout_threshold(rate).  The bit depends on (seed, site, b, c, t) and the rate alone, so a
+    larger B, C or T extends the mask without changing it.  Sites: dropout_inputs 0 = conv_dropout (l, C = width),
+    1 = skip_dropout (s, C = skip_width); dropout_all 0 = conv_dropout, i = res_dropout_i.  Engine.teacher_dropout_keep
+    returns the same bits from the device function the kernels call."""
+    seed = int(seed) & (2 ** 64 - 1)
+    thr = dropout_threshold(rate)
+    T4 = (int(T) + 3) // 4
+    b = np.arange(int(B), dtype=np.uint64)[:, None, None]
+    t4 = np.arange(T4, dtype=np.uint64)[None, :, None]
+    c = np.arange(int(C), dtype=np.uint64)[None, None, :]
+    words = _philox4x32_10(t4, c, np.uint64(int(site)), b, seed & 0xFFFFFFFF, seed >> 32)
+    words = np.stack(np.broadcast_arrays(*words), axis=2)           # [B, T4, 4, C]
+    return (words >= np.uint64(thr)).reshape(int(B), 4 * T4, int(C))[:, :int(T)]
+
+
+def dropout_step_seed(base, step):
+    """The mask seed of training step `step` (0 = the first) under the trainer's dropout_seed `base`: the 64-bit value
+    (base + step * 0x9E3779B97F4A7C15) mod 2^64.  The multiplier is odd, so for one base the seeds of 2^64 consecutive steps
+    are distinct, and a trainer resumed at step n continues the sequence it would have run."""
+    return (int(base) + int(step) * 0x9E3779B97F4A7C15) & (2 ** 64 - 1)
+
+
 class TeacherTrainer(object):
     """One teacher handle trained step after step.
 
@@ -39,19 +86,27 @@ class TeacherTrainer(object):
     lr:       a float or a {step: lr} schedule keyed by the number of completed steps (scheduled_lr).
     clip_norm: None, or the bound of tf.clip_by_global_norm over all trained variables.
     upsampler: also train trans_conv_j/kernel and /bias; with False the upsampler keeps its weights.
+    dropout:  apply the hparams' dropout_inputs / dropout_all (rate dropout_rate) in every step, as train_wavenet.py does
+              (DESIGN.md 17); off by default.  Step k (k completed steps before it) draws its masks from the seed
+              dropout_step_seed(dropout_seed, k), so a trainer built with global_step = n set continues the same sequence.
+              feed_forward, calculate_loss and generation on the handle stay deterministic, like the reference's
+              use_as_teacher graph.
 
     Order inside a step (the reference's tf.group leaves it open): Adam first, with t = completed steps + 1; then the EMA of
     the UPDATED weights with num_updates = the number of steps completed BEFORE this one, i.e. the decay of step 1 is
     min(ema_decay, 1 / 10).  The shadows start equal to the weights."""
 
     def __init__(self, wavenet, weights, lr=2e-4, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay=0.9999, clip_norm=None,
-                 upsampler=True):
+                 upsampler=True, dropout=False, dropout_seed=0):
         self.net = wavenet
         self.eng = eng = wavenet.engine
         self.lr, self.beta1, self.beta2, self.eps = lr, float(beta1), float(beta2), float(eps)
         self.ema_decay = float(ema_decay)
         self.clip_norm = None if clip_norm is None else float(clip_norm)
         self.upsampler = bool(upsampler)
+        self.dropout, self.dropout_seed = bool(dropout), int(dropout_seed)
+        if self.dropout and not (wavenet.dropout_inputs or wavenet.dropout_all):
+            raise ValueError('TeacherTrainer: dropout=True, but the hparams set neither dropout_inputs nor dropout_all')
         scheduled_lr(lr, 0)
         self.tables = [eng.teacher_grad_table()]
         if self.upsampler:
@@ -82,7 +137,8 @@ class TeacherTrainer(object):
         self.lr_history = []              # the scheduled rate of every step
 
     def _grads(self, inputs):
-        out = self.net.loss_and_weight_grads(inputs, upsampler=self.upsampler)
+        seed = dropout_step_seed(self.dropout_seed, self.global_step) if self.dropout else None
+        out = self.net.loss_and_weight_grads(inputs, upsampler=self.upsampler, dropout_seed=seed)
         flats = [out['flat_grads']]
         if self.upsampler:
             flats.append(out['flat_upsampler_grads'])
@@ -108,8 +164,9 @@ class TeacherTrainer(object):
 
     def step(self, inputs):
         """One training step on {'wav': [B,T], 'mel': [B,F,80]} -> {'loss': the loss BEFORE the update (the bits of
-        calculate_loss(feed_forward(.)) under the weights in force at entry), 'log_probs': [B,T], 'grad_norm': the global
-        norm of the gradient before clipping}, all device tensors."""
+        calculate_loss(feed_forward(.)) under the weights in force at entry; with dropout those of
+        loss_and_weight_grads(dropout_seed=dropout_step_seed(dropout_seed, global_step))), 'log_probs': [B,T], 'grad_norm':
+        the global norm of the gradient before clipping}, all device tensors."""
         out, flats = self._grads(inputs)
         norm = self._update(flats)
         self._repack(self.p)

@@ -106,21 +106,37 @@ class Wavenet(_TeacherBase):
             lp = self.engine.teacher_log_prob(out_params, wav)
         return {'loss': -lp.mean(), 'log_probs': lp}
 
-    def loss_and_weight_grads(self, inputs, upsampler=False):
+    @property
+    def dropout_rate(self):
+        """wavenet.py:132-135"""
+        return getattr(self.hparams, 'dropout_rate', 0.5 if self.dropout_inputs else 0.05)
+
+    def loss_and_weight_grads(self, inputs, upsampler=False, dropout_seed=None):
         """The loss train_wavenet.py minimises and its gradient: 'wav' [B,T] raw audio and 'mel' [B,F,80] ->
         {'loss': -mean log p (the bits of the no-grad calculate_loss(feed_forward(.))), 'log_probs': [B,T],
          'grads': {tf variable name: d loss / d variable, in the TF shape} for every loaded variable of the residual stack and
          output head, 'flat_grads': the same values as one float32 vector (Engine.teacher_grad_table gives the offsets),
          'd_encoding': d loss / d encoding [B, F frame_shift, deconv_width], the cotangent the upsampler's variables need}.
         One training-tape forward and one reverse pass on the device.  MoL and Gauss teachers without mu-law
-        and without weight norm.  `dropout_inputs` / `dropout_all` are training-time perturbations and are NOT applied: the
-        gradient is that of the deterministic forward feed_forward evaluates.
+        and without weight norm.
+        dropout_seed=None: the deterministic forward feed_forward evaluates, whatever the hparams say about dropout.
+        dropout_seed=s (an integer, 64 bits are used): the training graph of train_wavenet.py -- the hparams' `dropout_inputs`
+        (conv_dropout on l and skip_dropout on s after skip_start, default rate 0.5) or `dropout_all` (conv_dropout and every
+        res_dropout_i, default rate 0.05) at rate `dropout_rate`, with the masks train.dropout_keep(s, site, ...) gives
+        (DESIGN.md 17).  'loss', 'log_probs' and every gradient are those of the dropped forward.  ValueError when the hparams
+        ask for neither.
         upsampler=True: 'grads' also holds trans_conv_j/kernel and trans_conv_j/bias, from one Engine.deconv_backward on this
         call's own d_encoding, and 'flat_upsampler_grads' is that call's flat vector
         (Engine.deconv_grad_table gives the offsets).  Everything else is the bits of the default call."""
+        dropout = None
+        if dropout_seed is not None:
+            if not (self.dropout_inputs or self.dropout_all):
+                raise ValueError('loss_and_weight_grads: dropout_seed given, but the hparams set neither dropout_inputs nor '
+                                 'dropout_all')
+            dropout = ('dropout_inputs' if self.dropout_inputs else 'dropout_all', int(dropout_seed), float(self.dropout_rate))
         eng = self.engine
         wav = eng._dev(inputs['wav'])
-        out, tape = eng.teacher_forward_train_tape(wav, inputs['mel'])
+        out, tape = eng.teacher_forward_train_tape(wav, inputs['mel'], dropout=dropout)
         lp = eng.teacher_log_prob(out, wav)
         d_lp = torch.full_like(lp, -1.0 / lp.numel())
         d_out, _ = eng.teacher_log_prob_grad(out, wav, d_lp, want_wav=False)
