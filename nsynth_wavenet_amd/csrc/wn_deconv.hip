@@ -635,40 +635,7 @@ __global__ void cm_to_tm_kernel(const float* __restrict__ in, float* __restrict_
     }
 }
 
-// Same, but the output is written as split-fp16 pair planes (wn_codec.h): one workgroup =
-// one channel PAIR x 64 q columns; hi words to row cp, lo words to row cout/2 + cp.
-__global__ __launch_bounds__(256) void deconv_interleave_split_kernel(
-    const float* __restrict__ yp, const float* __restrict__ bias, unsigned* __restrict__ y,
-    int cout, int Qp, int64_t ys, int yoff, int L, int S, int pL, int act, unsigned* __restrict__ status) {
-    __shared__ float tile[2][DI_MAXS][DC_QT + 1];
-    const int cp = blockIdx.y, b = blockIdx.z;
-    const int q0 = blockIdx.x * DC_QT;
-    for (int i = threadIdx.x; i < 2 * S * DC_QT; i += 256) {
-        const int h = i / (S * DC_QT), j = i - h * S * DC_QT;
-        const int r = j / DC_QT, q = j - r * DC_QT;
-        tile[h][r][q] = yp[(((size_t)b * S + r) * cout + 2 * cp + h) * Qp + q0 + q];
-    }
-    __syncthreads();
-    const float b0 = bias[2 * cp], b1 = bias[2 * cp + 1];
-    const int64_t SL = (int64_t)S * L;
-    unsigned* yh = y + ((size_t)b * cout + cp) * ys + yoff;
-    unsigned* yl = yh + (size_t)(cout / 2) * ys;
-    const int64_t n0 = (int64_t)S * q0 - pL;
-    float amax = 0.f;
-    for (int i = threadIdx.x; i < S * DC_QT; i += 256) {
-        const int q = i / S, r = i - q * S;
-        const int64_t nn = n0 + i;
-        if (nn >= 0 && nn < SL) {
-            unsigned hw, lw;
-            wn_split_pair_t(apply_act(tile[0][r][q] + b0, act), apply_act(tile[1][r][q] + b1, act), hw, lw, amax);
-            yh[nn] = hw;
-            yl[nn] = lw;
-        }
-    }
-    wn_range_flag(amax, status);
-}
-
-// Last layer of the split-fp16 path: weave the phases AND emit the G4 layout of wn_iaf_h.hip
+// Last layer of the split-fp16 path (and every hidden one): weave the phases AND emit the G4 layout of wn_iaf_h.hip
 // (4 pair rows interleaved per 16-byte word group).  One workgroup = one group (8 channels) x
 // 32 q columns = 32*S consecutive output samples, 16-byte stores.
 // SC: the stride as a compile-time constant (0 = run-time value): the index arithmetic of both loops divides by it
@@ -975,8 +942,8 @@ int wn_run_deconv(wn_handle* h, int si, const float* mel, int B, int F, float* e
         }
         const int Q = L + (lp.pL + lp.S - 1) / lp.S + 1;      // phase columns q = (t + pL) / S
         const int Qp = ((Q + DC_QW - 1) / DC_QW) * DC_QW;
-        // the fp16 GEMM of the NEXT layer reads G4 words when its input width allows it
-        const bool next_g4 = h_gemm && !last && (lp.cout % 32 == 0);
+        // the fp16 GEMM of the NEXT layer reads G4 words (deconv_width is a multiple of 64: validate, wn_host.cpp)
+        const bool next_g4 = h_gemm && !last;
         // zero pads of an intermediate output: the G4 interleave writes them itself, the other forms get a memset
         if (!last && !next_g4) WN_HIP(h, hipMemsetAsync(y, 0, (size_t)B * lp.cout * ys * sizeof(float), st));
         // (h->dc_no_pg: WN_DC_NO_PG=1 at wn_create keeps the phase-major GEMM + interleave of rounds 1-4: A/B runs, cross-form test)
@@ -1026,9 +993,19 @@ int wn_run_deconv(wn_handle* h, int si, const float* mel, int B, int F, float* e
             const int Lp = (L + 63) / 64 * 64;
             wn_deconv_f_gemm(h, x, xs, DC_XOFF, reinterpret_cast<const unsigned*>(h->d_blob + lp.tab_f_off), lp.tab_f_R, lp.taps,
                              (lp.cout / 16) * 256, phase, lp.S, lp.cout, L, Lp, B, st);
-            dim3 gi(Lp / DC_QT, lp.cout, B);
-            hipLaunchKernelGGL(deconv_interleave_kernel, gi, dim3(256), 0, st, phase, h->d_blob + lp.b_off, y,
-                               lp.cout, Lp, ys, yoff, L, lp.S, 0, c.upsample_act);
+            if (last && split_out) {
+                // a consumer of G4 words behind fp32 GEMMs (a teacher handle created with precision f32; a split-fp16 handle
+                // whose stack has a layer without a split-fp16 pack): the same weave, split in its epilogue
+                dim3 gi(Lp / DG_Q, lp.cout / 8, B);
+                auto ik = lp.S == 20 ? deconv_interleave_g4_kernel<20> : lp.S == 10 ? deconv_interleave_g4_kernel<10>
+                                                                                     : deconv_interleave_g4_kernel<0>;
+                hipLaunchKernelGGL(ik, gi, dim3(256), 0, st, phase, h->d_blob + lp.b_off, reinterpret_cast<unsigned*>(y),
+                                   lp.cout, Lp, ys, yoff, L, lp.S, 0, c.upsample_act, status, 0);
+            } else {
+                dim3 gi(Lp / DC_QT, lp.cout, B);
+                hipLaunchKernelGGL(deconv_interleave_kernel, gi, dim3(256), 0, st, phase, h->d_blob + lp.b_off, y,
+                                   lp.cout, Lp, ys, yoff, L, lp.S, 0, c.upsample_act);
+            }
             in_g4 = false;
             x = y;
             xs = (int)ys;
@@ -1050,12 +1027,9 @@ int wn_run_deconv(wn_handle* h, int si, const float* mel, int B, int F, float* e
             hipLaunchKernelGGL(ik, gi, dim3(256), 0, st, phase, h->d_blob + lp.b_off,
                                reinterpret_cast<unsigned*>(y), lp.cout, Qp, ys, yoff, L, lp.S, lp.pL, c.upsample_act,
                                status, last ? 0 : 1);
-        } else if (!last && h_gemm) {
-            dim3 gi(Qp / DC_QT, lp.cout / 2, B);
-            hipLaunchKernelGGL(deconv_interleave_split_kernel, gi, dim3(256), 0, st, phase, h->d_blob + lp.b_off,
-                               reinterpret_cast<unsigned*>(y), lp.cout, Qp, ys, yoff, L, lp.S, lp.pL,
-                               c.upsample_act, status);
         } else {
+            // fp32 rows: the last layer of Engine.deconv, every layer of the fp32 GEMMs (a hidden layer of the split-fp16
+            // GEMMs always takes the G4 branch above: wn_create admits only deconv_width % 64 == 0)
             dim3 gi(Qp / DC_QT, lp.cout, B);
             hipLaunchKernelGGL(deconv_interleave_kernel, gi, dim3(256), 0, st, phase, h->d_blob + lp.b_off, y,
                                lp.cout, Qp, ys, yoff, L, lp.S, lp.pL, c.upsample_act);
