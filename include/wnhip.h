@@ -475,6 +475,39 @@ WN_API int wn_teacher_forward_train_tape_dropout(wn_handle* h, const float* wav,
 WN_API int wn_teacher_dropout_keep(uint64_t seed, int site, int B, int C, int64_t T, double rate, unsigned char* keep,
                                    void* stream);
 
+/* ---- weight gradients of the ParallelWavenet student: the training forward of the IAF flows onto a tape and
+ * one reverse pass over it, on the GEMM kernels of the teacher's training passes.  Student handles with width % 64 == 0 and
+ * deconv_width % 64 == 0, without weight norm and without mu-law; any num_iaf_layers and num_stages; shared, teacher or
+ * private deconv stacks.  Everything else is refused with WN_EINVAL and the size queries return 0 for it.  T and F obey the
+ * rules of wn_iaf_generate: T is a multiple of 2^(num_stages - 1), T <= F frame_shift, and the conditioning is centre-cropped
+ * to T columns.  Work calls as above: asynchronous on `stream`, no allocation, no host synchronisation, no atomics -- one
+ * writer per output element, a repeated call is bit-identical.
+ *
+ * The gradients live in ONE flat float32 buffer of wn_iaf_grad_floats(h) floats, laid out like wn_teacher_grad_info's: per
+ * flow k = 1 .. in order "iaf_k/start_conv", per layer "iaf_k/dilated_conv_i", "iaf_k/mel_cond_i", "iaf_k/res_i", then
+ * "iaf_k/out1", "iaf_k/mel_cond_out1", "iaf_k/out2_mean", "iaf_k/out2_scale"; "/W" in the TF shape before "/biases". ---- */
+WN_API int wn_iaf_grad_count(const wn_handle* h);
+WN_API int wn_iaf_grad_info(const wn_handle* h, int i, char* name, size_t name_cap, int64_t* offset, int64_t* shape4, int* ndim);
+WN_API size_t wn_iaf_grad_floats(const wn_handle* h);
+WN_API size_t wn_iaf_train_tape_bytes(const wn_handle* h, int B, int F, int64_t T);
+WN_API size_t wn_iaf_train_workspace_bytes(const wn_handle* h, int B, int F, int64_t T);
+/* ParallelWavenet.feed_forward on the caller's draw noise [B,T]: mean_tot, scale_tot = min(prod_k scale_k, e^7) and
+ * x = noise scale_tot + mean_tot, each [B,T], and the tape wn_iaf_backward_weights reads (identified by its address: a copy
+ * is refused). */
+WN_API int wn_iaf_forward_train_tape(wn_handle* h, const float* noise, const float* mel, int B, int F, int64_t T, float* x,
+                                     float* mean_tot, float* scale_tot, void* tape, size_t tape_bytes, void* ws,
+                                     size_t ws_bytes, void* stream);
+WN_API size_t wn_iaf_backward_weights_workspace_bytes(const wn_handle* h, int B, int F, int64_t T);
+/* d_x, d_mean_tot, d_scale_tot [B,T]: the cotangents of the three RETURNED tensors as independent outputs; the call adds x's
+ * dependence on the other two (d mean_tot += d_x; d scale_tot += d_x noise where the e^7 clamp is not active).  grads: every
+ * element overwritten (grads_floats >= wn_iaf_grad_floats).  d_encoding: NULL, or float32 [n_stacks, B, F frame_shift,
+ * deconv_width], zero outside the centre crop; n_stacks is 1 for a shared or teacher-owned deconv stack (every flow
+ * accumulates into it) and the number of flows for private stacks.  Ties: a clamp passes the gradient at the tie and none
+ * beyond it, a ReLU at exactly 0 passes none.  The tape must be one this handle wrote for the same B, F and T. */
+WN_API int wn_iaf_backward_weights(wn_handle* h, const void* tape, size_t tape_bytes, const float* d_x,
+                                   const float* d_mean_tot, const float* d_scale_tot, int B, int F, int64_t T, float* grads,
+                                   size_t grads_floats, float* d_encoding, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- reverse pass of the upsampler: the gradients of trans_conv_j/kernel and trans_conv_j/bias of the deconv
  * stack `scope` ("" for a teacher; "iaf_share", "iaf_1" ... for a student, as in wn_deconv) from mel [B,F,n_mel] and a
  * cotangent d_enc [B, F frame_shift, deconv_width] of wn_deconv's output, e.g. d_encoding of wn_teacher_backward_weights.

@@ -291,6 +291,8 @@ extern "C" int wn_finalize(wn_handle* h) {
     if (h->cfg.kind == WN_KIND_STUDENT) {
         if (!h->generic_student) rc = wn_pack_iaf_h(h, blob);
         if (rc) return rc;
+        rc = wn_pack_iaf_train(h, blob);
+        if (rc) return rc;
     } else {
         rc = wn_pack_teacher(h, blob);
         if (rc) return rc;

@@ -140,6 +140,28 @@ struct TeacherPack {
     uint64_t serial = 0;            // identity of the handle in the tapes it writes (wn_teacher_forward_tape)
 };
 
+// Student training (wn_iaf_train.hip): every flow as a dilated stack with a two-row head on the teacher's GEMM
+// kernels -- the packs of the forward and their transposes, in TeacherGemmPack's fragment order
+struct IafTrainLayer {
+    TeacherGemmPack gate, res;            // [width][3 width + deconv_width] in gate row order, [width][width / 2]
+    TeacherGemmPack gate_t, res_t;        // [width][3 width], [width / 2 padded to 64 rows][width]
+    TeacherGemmPack cond_t;               // [deconv_width][width]
+    int dilation;
+};
+struct IafTrainFlow {
+    size_t start_off;                     // w[3][W] | b[W]
+    std::vector<IafTrainLayer> layers;
+    TeacherGemmPack out1, out2;           // [width][width + deconv_width], [out2_mean; out2_scale][width]
+    TeacherGemmPack out1_t, out2_t;       // [width][width], [width][2 padded to 32]
+    TeacherGemmPack cond_out1_t;          // [deconv_width][width]
+    int deconv_stack;
+};
+struct IafTrainPack {
+    std::vector<IafTrainFlow> flows;
+    bool ok = false;                      // the model is one the training calls accept: the packs exist
+    uint64_t serial = 0;                  // identity of the handle in the tapes it writes
+};
+
 struct wn_handle {
     wn_config cfg;
     std::map<std::string, HostTensor> vars;   // expected variables (+ data once set)
@@ -154,6 +176,7 @@ struct wn_handle {
     bool generic_student = false;             // width / deconv_width / num_stages outside the MFMA kernels' shape
     ArPack ar;
     TeacherPack teacher;
+    IafTrainPack iaf_train;
     // hoisted conditioning (wn_iaf_c.hip): word offsets of the 8-K-step cond fragment arrays of
     // every layer and head ("row block"), flow after flow, stored as uint32 inside the blob
     size_t cond_tab_off = 0;
@@ -267,6 +290,7 @@ int wn_pack_deconv(wn_handle* h, std::vector<float>& blob);
 int wn_pack_iaf(wn_handle* h, std::vector<float>& blob);
 int wn_pack_ar(wn_handle* h, std::vector<float>& blob);
 int wn_pack_teacher(wn_handle* h, std::vector<float>& blob);   // after wn_pack_ar (reuses its matrices)
+int wn_pack_iaf_train(wn_handle* h, std::vector<float>& blob);  // students the training calls accept (wn_iaf_train.hip)
 
 // Runs stack `si` on mel [B,F,n_mel]; writes channel-major enc [B][cout][enc_stride]
 // (first valid sample at column 0).  Scratch carved from ws.

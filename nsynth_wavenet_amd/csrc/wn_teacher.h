@@ -3,8 +3,11 @@
 //   wn_teacher_bwd.hip    the tape and its registry, the reverse pass (input VJP)
 //   wn_teacher_wgrad.hip  the weight-gradient GEMM, its product tables and the training tape
 //   wn_teacher_dropout.hip  the dropout mask kernels of the training forward and the reverse pass
+// and by wn_iaf_train.hip, which runs the student's flows on the same GEMM kernels with packs of its own
 #pragma once
+#include <algorithm>
 #include "wn_internal.h"
+#include "wn_pack_h.h"
 
 constexpr int TG_NT = 4;                 // 16-column blocks per wave
 constexpr int TG_TN = 4 * 16 * TG_NT;    // columns per workgroup
@@ -12,7 +15,7 @@ constexpr int TG_KC = 4;                 // K-steps of weights per LDS stage
 constexpr int TG_XP = 64;                // zero left pad of the scaled input row
 
 enum { TG_SRC_G4 = 0, TG_SRC_ACC_RELU = 1 };
-enum { TG_EPI_GATE = 0, TG_EPI_RS = 1, TG_EPI_ACC = 2, TG_EPI_OUT = 3, TG_EPI_GATE_TAPE = 4, TG_EPI_BGATE = 5, TG_EPI_MASK = 6 };
+enum { TG_EPI_GATE = 0, TG_EPI_RS = 1, TG_EPI_ACC = 2, TG_EPI_OUT = 3, TG_EPI_GATE_TAPE = 4, TG_EPI_BGATE = 5, TG_EPI_MASK = 6, TG_EPI_RSC = 7 };
 
 struct TgSeg {
     const unsigned* base;   // G4 words or accumulator-layout floats
@@ -45,6 +48,8 @@ struct TgArgs {
     float* tape;
     long long tape_bstride;
     int tape_nmb, tape_hoff;
+    int bg_rows;            // BGATE: rows of the pack that exist (0: all) -- a 32-row half of a tile at or beyond it is skipped
+    const unsigned* ig4;    // RSC: the rows the residual is added to (og4's geometry); og4 receives the sum
 };
 
 // tg_gemm_kernel<epi, U> on a grid of Tp / TG_TN x mtiles / U x B workgroups (U = 2 for an even number of m-tiles)
@@ -55,6 +60,21 @@ inline TgSeg tg_seg_g4(const unsigned* p, long long bstride, long long rowlen, l
     sg.base = p; sg.bstride = bstride; sg.rowlen = (int)rowlen; sg.col0 = (int)col0; sg.nks = C / 32; sg.ng = C / 8;
     sg.kind = TG_SRC_G4;
     return sg;
+}
+// A fragments of a row-major [M][K] matrix (leading dimension ld), 64-row tiles, rows picked by rowfn (< 0: a zero row)
+template <class RowFn>
+inline void pack_tiles(std::vector<float>& blob, size_t dst_off, const float* src, int ld, int K, int mtiles, float scale,
+                       RowFn rowfn) {
+    const int nks = K / 32;
+    unsigned* P = reinterpret_cast<unsigned*>(blob.data() + dst_off);
+    for (int mt = 0; mt < mtiles; ++mt)
+        for (int ks = 0; ks < nks; ++ks)
+            for (int mb = 0; mb < 4; ++mb)
+                pack_afrag(P + (((size_t)mt * nks + ks) * 4 + mb) * 512, [&](int e, int kg, int i16) {
+                    const int row = rowfn(mt * 64 + 16 * mb + i16);
+                    if (row < 0) return 0.f;
+                    return scale * src[(size_t)row * ld + 32 * ks + 16 * (e >> 2) + 4 * kg + (e & 3)];
+                });
 }
 inline TgArgs tg_pack_args(const wn_handle* h, const TeacherGemmPack& g, long long T) {
     TgArgs a{};
@@ -159,7 +179,19 @@ int tg_forward_check(wn_handle* h, const char* fn, const float* wav, const float
 int tg_forward(wn_handle* h, const char* fn, const float* wav, const float* mel, int B, int F, int64_t T, float* out_params,
                void* ws, size_t ws_bytes, const TgTape& tape, void* stream);
 
+uint64_t wn_tape_serial_next();       // identity of a handle in the tapes it writes: unique per process
+// the input row [B][TG_XP + Tp] of a start conv (zero pad | the signal | zeros from T on) and the conv itself -> G4 rows
+// [B][W][RS] with their zero left pad (wb: w[3][W] | b[W])
+void wn_tg_input(const float* wav, float* xs, int B, long long T, long long Tp, int mu, hipStream_t st);
+void wn_tg_start(const float* xs, const float* wb, unsigned* l, int B, int W, long long Tp, long long RS, hipStream_t st);
+
 // ---- wn_teacher_bwd.hip ----
+// the address registry of the tapes: who wrote the tape at this address last, and for which shape
+void wn_tape_register(const void* tape, uint64_t serial, int B, long long T, int F);
+bool wn_tape_lookup(const void* tape, uint64_t* serial, int* B, long long* T, int* F);
+// d out [B,T,ow] times scal[0] -> G4 rows of Kp channels, zero beyond ow and from column T on
+void wn_tb_dout(const float* dout, const float* scal, unsigned* g4, int B, long long T, long long Tp, int ow, int Kp,
+                hipStream_t st);
 // what the VJP-side calls refuse (the distillation losses' own refusals, wn_distill.hip)
 int tb_check(wn_handle* h, const char* fn);
 // registry check shared by the reverse-pass calls; *F receives the frame count of a training tape (0: a plain tape)
@@ -183,6 +215,92 @@ int tw_aux(wn_handle* h, const TwCtx& w, hipStream_t st);                  // be
 int tw_head(wn_handle* h, const TwCtx& w, hipStream_t st, int stage);      // stage 0: d h1 is complete;  1: ds is complete
 int tw_layer(wn_handle* h, const TwCtx& w, size_t li, hipStream_t st);     // dl = d l_{li+1} and dd_li are complete
 int tw_tail(wn_handle* h, const TwCtx& w, hipStream_t st);                 // dl = d l_0
+
+// the product tables of tw_gemm_kernel / tw_reduce_kernel and one batch of them
+constexpr int TW_MAXOP = 10;
+constexpr int TW_MAXRED = 12;
+constexpr int TW_AUXC = 32;         // channels of aux: x(t-3), x(t-2), x(t-1), 1, zeros
+constexpr int TW_SLABS = 64;        // slabs (batch elements x chunks) aimed at
+struct TwOp {
+    const unsigned* dy;             // G4 rows of M channels (cotangent)
+    const unsigned* x;              // G4 rows of N channels (activation)
+    long long dy_bs, x_bs;          // words per batch element
+    long long out_off;              // floats inside a slab, [N][M]
+    int dy_rowlen, dy_col0, M;
+    int x_rowlen, x_col0, N;
+};
+struct TwArgs {
+    TwOp op[TW_MAXOP];
+    float* slab;
+    long long slab_stride;          // floats per slab
+    long long T;
+    int nchunk, chunk;              // chunks per batch element, columns per chunk
+};
+struct TwRed {
+    long long src_off, dst_off;     // floats inside a slab / inside grads
+    int rows, cols, src_ld, dst_ld;
+};
+struct TwRedArgs {
+    TwRed r[TW_MAXRED];
+    const float* slab;
+    long long slab_stride;
+    int nslab;
+    const float* scal;
+    float* grads;
+};
+// where a batch runs: the slabs, the time chunks, the scale pair whose scal[1] the reduction applies, the gradient buffer
+struct TwRun {
+    const char* fn;                 // message prefix
+    float* slab;
+    size_t slab_floats;
+    int B;
+    long long T;
+    int nchunk, chunk;
+    const float* scal;
+    float* grads;
+};
+// time chunks of B x Tp columns: one 256-column tile per chunk up to TW_SLABS / B tiles, so that about TW_SLABS slabs exist
+inline void tw_chunks(int B, long long Tp, long long T, int* chunk, int* nchunk) {
+    const long long ntiles = Tp / TG_TN, want = std::min<long long>(ntiles, std::max(1, TW_SLABS / B));
+    *chunk = (int)((ntiles + want - 1) / want) * TG_TN;
+    *nchunk = (int)((T + *chunk - 1) / *chunk);
+}
+constexpr size_t GRAD_NONE = ~(size_t)0;
+struct TwBatch {
+    TwArgs a{};
+    TwRedArgs r{};
+    int nop = 0, nred = 0;
+    long long used = 0;
+    int max_tiles = 0;
+    bool bad = false;               // a table overflow or an unknown gradient name: nothing was written, run() refuses
+    // dY (M channels, rows of rowlen) x X (N channels): returns the slab offset of the [N][M] product
+    long long add(const unsigned* dy, int M, long long dy_rowlen, const unsigned* x, int N, long long x_rowlen, long long x_col0) {
+        if (nop >= TW_MAXOP) { bad = true; return 0; }
+        TwOp& o = a.op[nop++];
+        o.dy = dy; o.dy_bs = (long long)M * dy_rowlen; o.dy_rowlen = (int)dy_rowlen; o.dy_col0 = 0; o.M = M;
+        o.x = x; o.x_bs = (long long)N * x_rowlen; o.x_rowlen = (int)x_rowlen; o.x_col0 = (int)x_col0; o.N = N;
+        o.out_off = used;
+        used += (long long)M * N;
+        max_tiles = std::max(max_tiles, ((M + 127) / 128) * ((N + 127) / 128));
+        return o.out_off;
+    }
+    void red(long long src_off, int rows, int cols, int src_ld, size_t dst_off, int dst_ld) {
+        if (nred >= TW_MAXRED || dst_off == GRAD_NONE) { bad = true; return; }
+        TwRed& q = r.r[nred++];
+        q.src_off = src_off; q.dst_off = (long long)dst_off; q.rows = rows; q.cols = cols; q.src_ld = src_ld; q.dst_ld = dst_ld;
+    }
+    int run(wn_handle* h, const TwRun& w, hipStream_t st);      // wn_teacher_wgrad.hip: the two launches
+};
+inline size_t wn_grad_off(const std::vector<WnGradEntry>& t, const std::string& name) {
+    for (const WnGradEntry& e : t)
+        if (e.name == name) return e.off;
+    return GRAD_NONE;       // an unknown name: TwBatch::red records it and run() refuses to launch
+}
+// accumulator-layout tape rows -> G4 activation rows of C channels, zero from column T on (mode 0: relu(src); 1: sigma * tanh
+// of a gate tape), and the aux rows [B][TW_AUXC][Tp] of an input row xs
+void wn_tw_act(const float* src, long long src_bs, int nmb, int hoff, unsigned* g4, int B, long long T, long long Tp, int C,
+               int mode, hipStream_t st);
+void wn_tw_aux(const float* xs, unsigned* g4, int B, long long T, long long Tp, hipStream_t st);
 
 // ---- wn_teacher_dropout.hip: the mask kernels ----
 uint32_t wn_dropout_threshold(double rate);     // min(2^32 - 1, floor(rate 2^32 + 0.5))

@@ -187,16 +187,18 @@ __global__ __launch_bounds__(256, 2) void tg_gemm_kernel(const TgArgs a) {
             o[16 * e] = gh;
             o[lo + 16 * e] = gl;
         }
-    } else if (EPI == TG_EPI_RS && mt < a.res_mtiles) {
+    } else if ((EPI == TG_EPI_RS || EPI == TG_EPI_RSC) && mt < a.res_mtiles) {
         // residual rows 64 mt .. +63: l += res  (wavenet.py:272-274), two 32-channel operand groups
+        // (RSC: the sum goes to og4 and the rows at ig4 stay as they are -- a training tape keeps every layer's input)
         const size_t lo = (size_t)a.og4_ng * a.og4_rowlen;
 #pragma unroll
         for (int st = 0; st < 2; ++st) {
-            wn_u4* o = reinterpret_cast<wn_u4*>(a.og4 + (size_t)b * a.og4_bstride) +
-                       (size_t)(4 * (2 * mt + st) + q) * a.og4_rowlen + a.og4_col0 + t0 + n;
+            const size_t oo = (size_t)b * a.og4_bstride + ((size_t)(4 * (2 * mt + st) + q) * a.og4_rowlen + a.og4_col0 + t0 + n) * 4;
+            wn_u4* o = reinterpret_cast<wn_u4*>(a.og4 + oo);
+            const wn_u4* in = EPI == TG_EPI_RSC ? reinterpret_cast<const wn_u4*>(a.ig4 + oo) : o;
 #pragma unroll
             for (int e = 0; e < TG_NT; ++e) {
-                const wn_u4 oh = o[16 * e], ol = o[lo + 16 * e];
+                const wn_u4 oh = in[16 * e], ol = in[lo + 16 * e];
                 wn_u4 nh, nl;
 #pragma unroll
                 for (int mg = 0; mg < 2; ++mg)
@@ -239,6 +241,7 @@ __global__ __launch_bounds__(256, 2) void tg_gemm_kernel(const TgArgs a) {
         const f4* tp = reinterpret_cast<const f4*>(a.tape + (size_t)b * a.tape_bstride) + lane;
 #pragma unroll
         for (int st = 0; st < 2; ++st) {
+            if (a.bg_rows && 64 * mt + 32 * st >= a.bg_rows) continue;      // zero rows of a padded pack: no gate channel
             wn_u4* os = reinterpret_cast<wn_u4*>(a.og4 + (size_t)b * a.og4_bstride) +
                         (size_t)(4 * (2 * mt + st) + q) * a.og4_rowlen + a.og4_col0 + t0 + n;
             wn_u4* ot = os + (size_t)(2 * a.tape_hoff) * a.og4_rowlen;
@@ -381,6 +384,17 @@ void tg_launch(const TgArgs& a, int mtiles, int B, long long Tp, hipStream_t st)
 
 }  // namespace
 
+void wn_tg_input(const float* wav, float* xs, int B, long long T, long long Tp, int mu, hipStream_t st) {
+    hipLaunchKernelGGL(tg_input_kernel, dim3((unsigned)((TG_XP + Tp + 255) / 256), B), dim3(256), 0, st, wav, xs, T, Tp, mu);
+}
+void wn_tg_start(const float* xs, const float* wb, unsigned* l, int B, int W, long long Tp, long long RS, hipStream_t st) {
+    hipLaunchKernelGGL(tg_start_kernel, dim3((unsigned)((RS + 255) / 256), W / 8, B), dim3(256), 0, st, xs, wb, l, W, Tp, RS);
+}
+uint64_t wn_tape_serial_next() {
+    static std::atomic<uint64_t> next_serial{1};
+    return next_serial++;
+}
+
 void wn_tg_launch(int epi, const TgArgs& a, int mtiles, int B, long long Tp, hipStream_t st) {
     switch (epi) {
         case TG_EPI_GATE: return tg_launch<TG_EPI_GATE>(a, mtiles, B, Tp, st);
@@ -390,23 +404,8 @@ void wn_tg_launch(int epi, const TgArgs& a, int mtiles, int B, long long Tp, hip
         case TG_EPI_GATE_TAPE: return tg_launch<TG_EPI_GATE_TAPE>(a, mtiles, B, Tp, st);
         case TG_EPI_BGATE: return tg_launch<TG_EPI_BGATE>(a, mtiles, B, Tp, st);
         case TG_EPI_MASK: return tg_launch<TG_EPI_MASK>(a, mtiles, B, Tp, st);
+        case TG_EPI_RSC: return tg_launch<TG_EPI_RSC>(a, mtiles, B, Tp, st);
     }
-}
-
-// ---- packing: A fragments of a row-major [M][K] matrix, 64-row tiles, rows picked by rowfn ----
-template <class RowFn>
-static void pack_tiles(std::vector<float>& blob, size_t dst_off, const float* src, int ld, int K, int mtiles, float scale,
-                       RowFn rowfn) {
-    const int nks = K / 32;
-    unsigned* P = reinterpret_cast<unsigned*>(blob.data() + dst_off);
-    for (int mt = 0; mt < mtiles; ++mt)
-        for (int ks = 0; ks < nks; ++ks)
-            for (int mb = 0; mb < 4; ++mb)
-                pack_afrag(P + (((size_t)mt * nks + ks) * 4 + mb) * 512, [&](int e, int kg, int i16) {
-                    const int row = rowfn(mt * 64 + 16 * mb + i16);
-                    if (row < 0) return 0.f;
-                    return scale * src[(size_t)row * ld + 32 * ks + 16 * (e >> 2) + 4 * kg + (e & 3)];
-                });
 }
 
 int wn_pack_teacher(wn_handle* h, std::vector<float>& blob) {
@@ -453,8 +452,7 @@ int wn_pack_teacher(wn_handle* h, std::vector<float>& blob) {
     T.out2 = gemm(A.wo2_off, A.bo2_off, OW, S, (OW + 63) / 64, ident(OW));
 
     // transposed packs of the input VJP (wn_teacher_backward_input): A = W^T, zero bias, same fragment order and scaling
-    static std::atomic<uint64_t> next_serial{1};
-    T.serial = next_serial++;
+    T.serial = wn_tape_serial_next();
     T.vjp_ok = W % 64 == 0 && S % 64 == 0 && H % 64 == 0 && OW <= 64;
     if (!T.vjp_ok) return WN_OK;
     auto gemm_t = [&](const std::vector<float>& src, int M, int K) {
@@ -720,10 +718,8 @@ int tg_forward(wn_handle* h, const char* fn, const float* wav, const float* mel,
     if (rc) return rc;
     // l0 = conv_start(shift_right(x_scaled))  (wavenet.py:223-226)
     {
-        dim3 g((unsigned)((TG_XP + L.Tp + 255) / 256), B);
-        hipLaunchKernelGGL(tg_input_kernel, g, dim3(256), 0, st, wav, xs, (long long)T, L.Tp, c.use_mu_law);
-        dim3 g2((unsigned)((L.RS + 255) / 256), W / 8, B);
-        hipLaunchKernelGGL(tg_start_kernel, g2, dim3(256), 0, st, xs, h->d_blob + h->ar.start_off, l_start, W, L.Tp, L.RS);
+        wn_tg_input(wav, xs, B, T, L.Tp, c.use_mu_law, st);
+        wn_tg_start(xs, h->d_blob + h->ar.start_off, l_start, B, W, L.Tp, L.RS, st);
     }
     if (drop_all) wn_dropout_g4(l, l, B, W, L.RS, IAF_LP, T, dr, 0, st);        // conv_dropout (wavenet.py:229-230)
     auto seg_acc = [&](const float* p, int nks) {

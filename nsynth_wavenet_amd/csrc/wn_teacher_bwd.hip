@@ -90,6 +90,23 @@ __global__ __launch_bounds__(256) void tb_dx_kernel(const unsigned* __restrict__
 }
 }  // namespace
 
+void wn_tape_register(const void* tape, uint64_t serial, int B, long long T, int F) {
+    std::lock_guard<std::mutex> lk(g_tape_mu);
+    g_tapes[tape] = TapeRec{serial, B, T, F, TgDropout{}};
+}
+bool wn_tape_lookup(const void* tape, uint64_t* serial, int* B, long long* T, int* F) {
+    std::lock_guard<std::mutex> lk(g_tape_mu);
+    auto it = g_tapes.find(tape);
+    if (it == g_tapes.end()) return false;
+    *serial = it->second.serial; *B = it->second.B; *T = it->second.T; *F = it->second.F;
+    return true;
+}
+void wn_tb_dout(const float* dout, const float* scal, unsigned* g4, int B, long long T, long long Tp, int ow, int Kp,
+                hipStream_t st) {
+    hipLaunchKernelGGL(tb_dout_kernel, dim3((unsigned)((Tp + 255) / 256), Kp / 8, B), dim3(256), 0, st, dout, scal, g4, T, Tp,
+                       ow, Kp);
+}
+
 BLayout b_layout(const wn_handle* h, int B, long long T) {
     const wn_config& c = h->cfg;
     BLayout L;
@@ -196,8 +213,7 @@ int tb_reverse(wn_handle* h, const void* tape, const float* d_out_params, int B,
 
     // operand scale
     wn_pow2_scale(d_out_params, (long long)B * T * c.out_width, w.scal + 4, w.scal, nullptr, st);
-    hipLaunchKernelGGL(tb_dout_kernel, dim3((unsigned)((Tp + 255) / 256), L.Kp / 8, B), dim3(256), 0, st, d_out_params, w.scal,
-                       w.dout, (long long)T, Tp, c.out_width, L.Kp);
+    wn_tb_dout(d_out_params, w.scal, w.dout, B, T, Tp, c.out_width, L.Kp, st);
     WN_HIP(h, hipMemsetAsync(w.dl, 0, (size_t)B * W * Tp * 4, st));
     WN_HIP(h, hipMemsetAsync(w.dd, 0, (size_t)B * G * L.RD * 4, st));
 

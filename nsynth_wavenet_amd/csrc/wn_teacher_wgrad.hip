@@ -24,40 +24,8 @@
 #include "wn_mfma_h.h"
 
 namespace {
-constexpr int TW_SLABS = 64;        // slabs (batch elements x chunks) aimed at
 constexpr int TW_KT = 32;           // columns per LDS stage (one K-step)
 constexpr int TW_LD = TW_KT + 8;    // halves per LDS row: 80 bytes, 16 lanes of a ds_read_b128 hit 16 distinct bank quads
-constexpr int TW_MAXOP = 10;
-constexpr int TW_MAXRED = 12;
-constexpr int TW_AUXC = 32;         // channels of aux: x(t-3), x(t-2), x(t-1), 1, zeros
-
-struct TwOp {
-    const unsigned* dy;             // G4 rows of M channels (cotangent)
-    const unsigned* x;              // G4 rows of N channels (activation)
-    long long dy_bs, x_bs;          // words per batch element
-    long long out_off;              // floats inside a slab, [N][M]
-    int dy_rowlen, dy_col0, M;
-    int x_rowlen, x_col0, N;
-};
-struct TwArgs {
-    TwOp op[TW_MAXOP];
-    float* slab;
-    long long slab_stride;          // floats per slab
-    long long T;
-    int nchunk, chunk;              // chunks per batch element, columns per chunk
-};
-struct TwRed {
-    long long src_off, dst_off;     // floats inside a slab / inside grads
-    int rows, cols, src_ld, dst_ld;
-};
-struct TwRedArgs {
-    TwRed r[TW_MAXRED];
-    const float* slab;
-    long long slab_stride;
-    int nslab;
-    const float* scal;
-    float* grads;
-};
 
 // eight columns of one G4 group -> eight rows [channel][8 columns] of an LDS operand image.  r[j] = the four words of
 // column j: word i holds channels wn_g4_channel(g, i) + {0, 1}
@@ -281,9 +249,7 @@ static WLayout w_layout(const wn_handle* h, int B, int F, long long T) {
     L.TE = (long long)F * h->frame_shift;
     L.c0 = (int)((L.TE - T) / 2);
     L.RE = std::max<long long>(L.TE, L.c0 + L.Tp);
-    const long long ntiles = L.Tp / TG_TN, want = std::min<long long>(ntiles, std::max(1, TW_SLABS / B));
-    L.chunk = (int)((ntiles + want - 1) / want) * TG_TN;
-    L.nchunk = (int)((T + L.chunk - 1) / L.chunk);
+    tw_chunks(B, L.Tp, T, &L.chunk, &L.nchunk);
     size_t o = align_up(BL.total, 256);
     auto carve = [&](size_t words) { size_t r = o; o += align_up(words * 4, 256); return r; };
     L.aux = carve((size_t)B * TW_AUXC * L.Tp);
@@ -325,12 +291,7 @@ static std::vector<WnGradEntry> grad_table(const wn_handle* h) {
     conv("out2", 1, S, OW);
     return t;
 }
-constexpr size_t GRAD_NONE = ~(size_t)0;
-static size_t grad_off(const std::vector<WnGradEntry>& t, const std::string& name) {
-    for (const WnGradEntry& e : t)
-        if (e.name == name) return e.off;
-    return GRAD_NONE;       // an unknown name: TwBatch::red records it and run() refuses to launch
-}
+static size_t grad_off(const std::vector<WnGradEntry>& t, const std::string& name) { return wn_grad_off(t, name); }
 
 struct TwCtx {
     int B;
@@ -345,47 +306,34 @@ struct TwCtx {
     const unsigned* enc() const { return reinterpret_cast<const unsigned*>(tp.enc); }
     float* grads;
     bool want_denc;
+    TwRun run() const {
+        return TwRun{"wn_teacher_backward_weights", slab, L.slab_floats, B, T, L.nchunk, L.chunk, rw.scal, grads};
+    }
 };
+
+// one batch of products and the reduction of their slabs
+int TwBatch::run(wn_handle* h, const TwRun& w, hipStream_t st) {
+    if (bad || used > (long long)w.slab_floats)
+        return wn_fail(h, WN_EIO, "%s: internal product table overflow or unknown gradient name", w.fn);
+    a.slab = w.slab; a.slab_stride = (long long)w.slab_floats; a.T = w.T; a.nchunk = w.nchunk; a.chunk = w.chunk;
+    hipLaunchKernelGGL(tw_gemm_kernel, dim3(max_tiles, nop, w.B * w.nchunk), dim3(256), 0, st, a);
+    r.slab = w.slab; r.slab_stride = a.slab_stride; r.nslab = w.B * w.nchunk; r.scal = w.scal; r.grads = w.grads;
+    int most = 0;
+    for (int i = 0; i < nred; ++i) most = std::max(most, r.r[i].rows * r.r[i].cols);
+    hipLaunchKernelGGL(tw_reduce_kernel, dim3(std::min(1024, (most + 255) / 256), nred), dim3(256), 0, st, r);
+    WN_HIP(h, hipGetLastError());
+    return WN_OK;
+}
+void wn_tw_act(const float* src, long long src_bs, int nmb, int hoff, unsigned* g4, int B, long long T, long long Tp, int C,
+               int mode, hipStream_t st) {
+    hipLaunchKernelGGL(tw_act_kernel, dim3((unsigned)(Tp / 256), C / 8, B), dim3(256), 0, st, src, src_bs, nmb, hoff, g4, T, Tp,
+                       C, mode);
+}
+void wn_tw_aux(const float* xs, unsigned* g4, int B, long long T, long long Tp, hipStream_t st) {
+    hipLaunchKernelGGL(tw_aux_kernel, dim3((unsigned)(Tp / 256), TW_AUXC / 8, B), dim3(256), 0, st, xs, g4, T, Tp);
+}
 
 namespace {
-// one batch of products and the reduction of their slabs
-struct TwBatch {
-    TwArgs a{};
-    TwRedArgs r{};
-    int nop = 0, nred = 0;
-    long long used = 0;
-    int max_tiles = 0;
-    // dY (M channels, rows of rowlen) x X (N channels): returns the slab offset of the [N][M] product
-    bool bad = false;               // a table overflow or an unknown gradient name: nothing was written, run() refuses
-    long long add(const unsigned* dy, int M, long long dy_rowlen, const unsigned* x, int N, long long x_rowlen, long long x_col0) {
-        if (nop >= TW_MAXOP) { bad = true; return 0; }
-        TwOp& o = a.op[nop++];
-        o.dy = dy; o.dy_bs = (long long)M * dy_rowlen; o.dy_rowlen = (int)dy_rowlen; o.dy_col0 = 0; o.M = M;
-        o.x = x; o.x_bs = (long long)N * x_rowlen; o.x_rowlen = (int)x_rowlen; o.x_col0 = (int)x_col0; o.N = N;
-        o.out_off = used;
-        used += (long long)M * N;
-        max_tiles = std::max(max_tiles, ((M + 127) / 128) * ((N + 127) / 128));
-        return o.out_off;
-    }
-    void red(long long src_off, int rows, int cols, int src_ld, size_t dst_off, int dst_ld) {
-        if (nred >= TW_MAXRED || dst_off == GRAD_NONE) { bad = true; return; }
-        TwRed& q = r.r[nred++];
-        q.src_off = src_off; q.dst_off = (long long)dst_off; q.rows = rows; q.cols = cols; q.src_ld = src_ld; q.dst_ld = dst_ld;
-    }
-    int run(wn_handle* h, const TwCtx& w, hipStream_t st) {
-        if (bad || used > (long long)w.L.slab_floats)
-            return wn_fail(h, WN_EIO, "wn_teacher_backward_weights: internal product table overflow or unknown gradient name");
-        a.slab = w.slab; a.slab_stride = (long long)w.L.slab_floats; a.T = w.T; a.nchunk = w.L.nchunk; a.chunk = w.L.chunk;
-        hipLaunchKernelGGL(tw_gemm_kernel, dim3(max_tiles, nop, w.B * w.L.nchunk), dim3(256), 0, st, a);
-        r.slab = w.slab; r.slab_stride = a.slab_stride; r.nslab = w.B * w.L.nchunk; r.scal = w.rw.scal; r.grads = w.grads;
-        int most = 0;
-        for (int i = 0; i < nred; ++i) most = std::max(most, r.r[i].rows * r.r[i].cols);
-        hipLaunchKernelGGL(tw_reduce_kernel, dim3(std::min(1024, (most + 255) / 256), nred), dim3(256), 0, st, r);
-        WN_HIP(h, hipGetLastError());
-        return WN_OK;
-    }
-};
-
 // in-place accumulation of W^T dY into the d enc rows (tg_gemm_kernel, RS epilogue with residual rows only)
 void tw_denc_gemm(wn_handle* h, const TwCtx& w, const TeacherGemmPack& g, const unsigned* dy, int C, long long rowlen,
                   hipStream_t st) {
@@ -400,7 +348,7 @@ void tw_denc_gemm(wn_handle* h, const TwCtx& w, const TeacherGemmPack& g, const 
 
 int tw_aux(wn_handle* h, const TwCtx& w, hipStream_t st) {
     const long long Tp = w.L.Tp;
-    hipLaunchKernelGGL(tw_aux_kernel, dim3((unsigned)(Tp / 256), TW_AUXC / 8, w.B), dim3(256), 0, st, w.tp.xs, w.aux, w.T, Tp);
+    wn_tw_aux(w.tp.xs, w.aux, w.B, w.T, Tp, st);
     if (w.want_denc) WN_HIP(h, hipMemsetAsync(w.denc, 0, (size_t)w.B * h->cfg.deconv_width * w.L.RE * 4, st));
     return WN_OK;
 }
@@ -428,7 +376,7 @@ int tw_head(wn_handle* h, const TwCtx& w, hipStream_t st, int stage) {
     k.red(c1w, Cd, S, S, grad_off(w.tab, "mel_cond_out1/W"), S);
     k.red(o1b + 3 * S, 1, S, S, grad_off(w.tab, "out1/biases"), S);
     k.red(o1b + 3 * S, 1, S, S, grad_off(w.tab, "mel_cond_out1/biases"), S);
-    if (int rc = k.run(h, w, st)) return rc;
+    if (int rc = k.run(h, w.run(), st)) return rc;
     if (w.want_denc) tw_denc_gemm(h, w, h->teacher.cond_out1_t, w.rw.dh1, S, Tp, st);
     return WN_OK;
 }
@@ -461,7 +409,7 @@ int tw_layer(wn_handle* h, const TwCtx& w, size_t li, hipStream_t st) {
     k.red(cw, Cd, G, G, grad_off(w.tab, "mel_cond_" + n + "/W"), G);
     k.red(db + 3 * G, 1, G, G, grad_off(w.tab, "dilated_conv_" + n + "/biases"), G);
     k.red(db + 3 * G, 1, G, G, grad_off(w.tab, "mel_cond_" + n + "/biases"), G);
-    if (int rc = k.run(h, w, st)) return rc;
+    if (int rc = k.run(h, w.run(), st)) return rc;
     if (w.want_denc) tw_denc_gemm(h, w, tl.cond_t, w.rw.dd, G, w.rw.RD, st);
     return WN_OK;
 }
@@ -480,7 +428,7 @@ int tw_tail(wn_handle* h, const TwCtx& w, hipStream_t st) {
     k.red(sb + 3 * S, 1, S, S, grad_off(w.tab, "skip_start/biases"), S);
     k.red(cs, 3, W, W, grad_off(w.tab, "conv_start/W"), W);
     k.red(cs + 3 * W, 1, W, W, grad_off(w.tab, "conv_start/biases"), W);
-    return k.run(h, w, st);
+    return k.run(h, w.run(), st);
 }
 
 // what the weight-gradient calls refuse beyond tb_check

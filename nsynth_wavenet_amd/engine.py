@@ -471,6 +471,75 @@ class Engine(object):
             grads = self._grad_views(flat, self.teacher_grad_table())
         return {'grads': grads, 'flat_grads': flat[:n], 'd_encoding': denc, 'd_wav': dwav}
 
+    # ---- weight gradients of the student (DESIGN.md 19) ----
+    def iaf_grad_table(self):
+        """[(tf variable name, float offset, TF shape)] of iaf_backward_weights' flat gradient buffer: every variable of every
+        flow in the order weights.expected_variables lists them (the upsampler's are deconv_backward's).  Empty for a
+        model the training calls refuse."""
+        return self._grad_table(self.lib.wn_iaf_grad_count, self.lib.wn_iaf_grad_info)
+
+    def iaf_train_tape_bytes(self, B, F):
+        return int(self.lib.wn_iaf_train_tape_bytes(self._h, int(B), int(F), self.iaf_length(F)))
+
+    def iaf_forward_train_tape(self, mel, noise=None, seed=0):
+        """ParallelWavenet.feed_forward for training: mel [B,F,n_mel] -> ({'x', 'mean_tot', 'scale_tot', 'rand_input'}, tape),
+        each tensor [B,T] on the device, the tape a uint8 device tensor iaf_backward_weights reads (identified by its
+        address).  noise [B,T] injects the draw; None draws it with iaf_generate's generator from `seed`."""
+        mel = self._dev(mel)
+        if mel.dim() != 3 or mel.shape[2] != self.n_mel:
+            raise ValueError('mel must be [batch, frames, {}], got {}'.format(self.n_mel, tuple(mel.shape)))
+        B, F = int(mel.shape[0]), int(mel.shape[1])
+        T = self.iaf_length(F)
+        if noise is None:
+            noise = self.iaf_generate(mel, seed=seed, want=('rand_input',), check_range=False)['rand_input']
+        noise = self._dev(noise)
+        if tuple(noise.shape) != (B, T):
+            raise ValueError('noise must be [{}, {}], got {}'.format(B, T, tuple(noise.shape)))
+        new = lambda: torch.empty((B, T), dtype=torch.float32, device=self.device)
+        x, mt, st = new(), new(), new()
+        with torch.cuda.device(self.device):
+            tape = torch.empty(max(int(self.lib.wn_iaf_train_tape_bytes(self._h, B, F, T)), 256), dtype=torch.uint8,
+                               device=self.device)
+            ws = torch.empty(max(int(self.lib.wn_iaf_train_workspace_bytes(self._h, B, F, T)), 256), dtype=torch.uint8,
+                             device=self.device)
+            self._check(self.lib.wn_iaf_forward_train_tape(self._h, _ptr(noise), _ptr(mel), B, F, T, _ptr(x), _ptr(mt),
+                                                           _ptr(st), _ptr(tape), tape.numel(), _ptr(ws), ws.numel(),
+                                                           self._stream()))
+        if len(self._train_frames) >= 256:
+            self._train_frames.clear()
+        self._train_frames[tape.data_ptr()] = F
+        return {'x': x, 'mean_tot': mt, 'scale_tot': st, 'rand_input': noise}, tape
+
+    def iaf_n_stacks(self):
+        """deconv stacks of the student: 1 when shared or teacher-owned, else one per flow"""
+        share = getattr(self.hp, 'use_share_deconv', False) or getattr(self.hp, 'use_teacher_deconv', False)
+        return 1 if share else max(1, len(getattr(self.hp, 'num_iaf_layers', ())))
+
+    def iaf_backward_weights(self, tape, d_x, d_mean_tot, d_scale_tot, want_encoding=True, n_frames=None):
+        """One reverse pass on a tape of iaf_forward_train_tape.  d_x, d_mean_tot, d_scale_tot [B,T]: the cotangents of the
+        three returned tensors as independent outputs (x's dependence on the other two is added by the call) ->
+        {'grads': {tf name: device tensor in the TF shape} (views into 'flat_grads'), 'flat_grads': [n] float32,
+        'd_encoding': [n_stacks, B, F frame_shift, deconv_width] or None}."""
+        g = [self._dev(v) for v in (d_x, d_mean_tot, d_scale_tot)]
+        if g[0].dim() != 2 or any(tuple(v.shape) != tuple(g[0].shape) for v in g):
+            raise ValueError('iaf_backward_weights: d_x, d_mean_tot and d_scale_tot must be [B,T]')
+        F = int(n_frames if n_frames is not None else self._train_frames.get(tape.data_ptr(), 0))
+        if F < 1:
+            raise ValueError('iaf_backward_weights: pass n_frames for a tape this engine object did not write')
+        B, T = int(g[0].shape[0]), int(g[0].shape[1])
+        with torch.cuda.device(self.device):
+            n = int(self.lib.wn_iaf_grad_floats(self._h))
+            flat = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
+            denc = torch.empty((self.iaf_n_stacks(), B, F * self.frame_shift, int(self.hp.deconv_width)), dtype=torch.float32,
+                               device=self.device) if want_encoding else None
+            ws = torch.empty(max(int(self.lib.wn_iaf_backward_weights_workspace_bytes(self._h, B, F, T)), 256),
+                             dtype=torch.uint8, device=self.device)
+            self._check(self.lib.wn_iaf_backward_weights(self._h, _ptr(tape), tape.numel(), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]),
+                                                         B, F, T, _ptr(flat), n, _ptr(denc), _ptr(ws), ws.numel(),
+                                                         self._stream()))
+            grads = self._grad_views(flat, self.iaf_grad_table())
+        return {'grads': grads, 'flat_grads': flat[:n], 'd_encoding': denc}
+
     # ---- reverse pass of the upsampler (DESIGN.md 15) ----
     def deconv_grad_table(self, scope=''):
         """[(tf variable name, float offset, TF shape)] of deconv_backward's flat gradient buffer: per layer

@@ -171,3 +171,41 @@ class ParallelWavenet(object):
             loss_dict.update(cl_dict)
         loss_dict.update({'loss': loss})
         return loss_dict
+
+    def loss_and_weight_grads(self, inputs, seed=0, noise=None, upsampler=True):
+        """The loss train_parallel_wavenet.py minimises and its gradient with respect to the student's own variables
+        (DESIGN.md 19).  inputs: 'mel' [B,F,80] and 'wav' [B,T'], plus 'mel_rand' where contrastive_loss_factor > 0.
+        `noise` [B,T] injects the student's draw (None: the device generator under `seed`); `seed` also drives the
+        Monte-Carlo draws of calculate_loss, as in calculate_loss(feed_forward(inputs, seed=seed), seed=seed).
+        One tape forward (Engine.iaf_forward_train_tape), calculate_loss on its x, mean_tot and scale_tot as leaves,
+        backward() through the frozen teacher, one reverse pass over the tape (Engine.iaf_backward_weights).
+        Returns calculate_loss's dict -- the bits of the no-grad calculate_loss on the same forward values -- plus
+        'grads': {tf variable name: d loss / d variable in the TF shape}, 'flat_grads' (Engine.iaf_grad_table gives the
+        offsets) and 'd_encoding' [n_stacks, B, F frame_shift, deconv_width].
+        upsampler=True: 'grads' also holds '<scope>/trans_conv_j/kernel' and '/bias' of every deconv stack the student owns
+        ('iaf_share', or 'iaf_k' per flow), from one Engine.deconv_backward per stack on this call's d_encoding, and
+        'flat_upsampler_grads' maps the scope to that call's flat vector.  With use_teacher_deconv the encoding is the
+        teacher's and is not trained: the step is skipped.  The teacher stays frozen; the optimiser is the caller's."""
+        eng = self.engine
+        mel = eng._dev(inputs['mel'])
+        ff, tape = eng.iaf_forward_train_tape(mel, noise=noise, seed=seed)
+        leaves = {k: ff[k].detach().requires_grad_(True) for k in ('x', 'mean_tot', 'scale_tot')}
+        ff_dict = dict(leaves, mel=mel, wav=inputs['wav'], rand_input=ff['rand_input'])
+        if 'mel_rand' in inputs:
+            ff_dict['mel_rand'] = inputs['mel_rand']
+        with torch.enable_grad():
+            loss_dict = self.calculate_loss(ff_dict, seed=seed)
+            loss_dict['loss'].backward()
+        cot = [v.grad if v.grad is not None else torch.zeros_like(v) for v in (leaves['x'], leaves['mean_tot'], leaves['scale_tot'])]
+        res = eng.iaf_backward_weights(tape, cot[0], cot[1], cot[2], want_encoding=True)
+        ret = {k: v.detach() for k, v in loss_dict.items()}
+        ret.update({'grads': res['grads'], 'flat_grads': res['flat_grads'], 'd_encoding': res['d_encoding']})
+        if upsampler and not self.use_teacher_deconv:
+            scopes = ['iaf_share'] if self.use_share_deconv else ['iaf_{:d}'.format(k + 1) for k in range(eng.iaf_n_stacks())]
+            ret['grads'] = dict(res['grads'])
+            ret['flat_upsampler_grads'] = {}
+            for s, scope in enumerate(scopes):
+                up = eng.deconv_backward(mel, res['d_encoding'][s], scope)
+                ret['grads'].update(up['grads'])
+                ret['flat_upsampler_grads'][scope] = up['flat_grads']
+        return ret
