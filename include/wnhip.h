@@ -562,6 +562,36 @@ WN_API size_t wn_teacher_set_weights_workspace_bytes(const wn_handle* h);
 WN_API int wn_teacher_set_weights(wn_handle* h, const float* params, size_t params_floats, const float* up_params,
                                   size_t up_floats, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Student training step on the device ----
+ *
+ * wn_iaf_set_weights is wn_teacher_set_weights' counterpart for a FINALIZED student handle.  `params` is a flat device buffer
+ * in the layout of wn_iaf_grad_info (wn_iaf_grad_floats floats).  `up_params` is a HOST array of n_up device pointers, one
+ * per deconv stack in the order of d_encoding's leading axis (the one stack "iaf_share", or "iaf_k" per flow), each in the
+ * layout of wn_deconv_grad_info(h, scope) with up_floats[s] floats; n_up == 0 or a NULL entry: that stack keeps its packs.
+ * After the call every word of the device blob that a kernel reads, and every host-side value passed as a kernel argument,
+ * equals what wn_finalize of a fresh handle loaded with the same values would have produced: the plain tensors of a generic
+ * student (and its two head biases, which are host floats), or the fp32 fragments and the split-fp16 packs of the three
+ * launch forms; the GEMM packs of the training calls with their transposes; for every stack handed in, the packs
+ * wn_teacher_set_weights rewrites for a teacher's.  Layer ids, row-block tables, launch plans, zero pad rows and the zero
+ * biases of transposed packs do not depend on the variables and are left alone.  No pointer changes, nothing is allocated.
+ *
+ * The call is table-driven: one launch per KIND of pack over a descriptor table built on the host and uploaded into `ws`, so
+ * its launch count depends on the number of deconv stacks handed in, not on flows or layers.  The maxima behind the scales
+ * (and a generic student's head biases) are READ BACK: the call SYNCHRONISES `stream` once, midway, and returns with the
+ * rest enqueued; `params`, the stacks' buffers and `ws` must stay unchanged until `stream` has passed the call.
+ *
+ * Exclusive like the switches ("Concurrency"): WN_ESTATE while a work call of another thread is inside the library; work
+ * enqueued earlier on other streams that reads the handle's weights must have finished.  The handle's tape serial changes
+ * before the first launch: a tape of wn_iaf_forward_train_tape written before the call is refused afterwards, also after a
+ * failure midway (the weights are then undefined until a later call succeeds).
+ * WN_EINVAL, by name: a teacher handle; a handle the student's training calls refuse (mu-law, weight norm, width or
+ * deconv_width no multiple of 64); n_up neither 0 nor the number of stacks; a float count that is not the table's;
+ * use_resize_conv with a non-NULL entry; a workspace below wn_iaf_set_weights_workspace_bytes (0 for a handle the call
+ * refuses).  WN_ESTATE: a handle that is not finalized. */
+WN_API size_t wn_iaf_set_weights_workspace_bytes(const wn_handle* h);
+WN_API int wn_iaf_set_weights(wn_handle* h, const float* params, size_t params_floats, const float* const* up_params,
+                              const size_t* up_floats, int n_up, void* ws, size_t ws_bytes, void* stream);
+
 /* Sum of squares of n device floats in double: a fixed-order two-stage reduction without atomics (a repeated call gives the
  * same bits).  acc[0] (one device double) is written, or added to when `accumulate` is non-zero, so that the buffers of the
  * residual stack and of the upsampler chain into one global norm.  Needs no handle; errors through wn_last_error(NULL).

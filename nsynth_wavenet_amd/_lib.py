@@ -27,7 +27,7 @@ SYMBOLS = ['wn_abi_version', 'wn_create', 'wn_set_weight', 'wn_finalize', 'wn_ia
            'wn_teacher_train_tape_dropout_bytes', 'wn_teacher_forward_train_tape_dropout', 'wn_teacher_dropout_keep',
            'wn_iaf_grad_count', 'wn_iaf_grad_info', 'wn_iaf_grad_floats', 'wn_iaf_train_tape_bytes',
            'wn_iaf_train_workspace_bytes', 'wn_iaf_forward_train_tape', 'wn_iaf_backward_weights_workspace_bytes',
-           'wn_iaf_backward_weights']
+           'wn_iaf_backward_weights', 'wn_iaf_set_weights_workspace_bytes', 'wn_iaf_set_weights']
 
 
 class WnConfig(ctypes.Structure):
@@ -147,6 +147,9 @@ def load():
     lib.wn_teacher_set_weights_workspace_bytes.argtypes = [vp]
     lib.wn_teacher_set_weights_workspace_bytes.restype = sz
     lib.wn_teacher_set_weights.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp]
+    lib.wn_iaf_set_weights_workspace_bytes.argtypes = [vp]
+    lib.wn_iaf_set_weights_workspace_bytes.restype = sz
+    lib.wn_iaf_set_weights.argtypes = [vp, vp, sz, vp, vp, i32, vp, sz, vp]
     lib.wn_grad_sumsq_workspace_bytes.argtypes = [sz]
     lib.wn_grad_sumsq_workspace_bytes.restype = sz
     lib.wn_grad_sumsq.argtypes = [vp, sz, vp, i32, vp, sz, vp]

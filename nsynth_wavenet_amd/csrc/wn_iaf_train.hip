@@ -495,6 +495,10 @@ extern "C" size_t wn_iaf_grad_floats(const wn_handle* h) {
     return wn_grad_floats(it_grad_table(h));
 }
 
+// for wn_iaf_set_weights (wn_iaf_repack.hip): the layout of the flat parameter buffer and the refusals by name
+std::vector<WnGradEntry> wn_iaf_grad_table(const wn_handle* h) { return it_grad_table(h); }
+int wn_iaf_train_check(wn_handle* h, const char* fn) { return it_check(h, fn); }
+
 extern "C" int wn_iaf_forward_train_tape(wn_handle* h, const float* noise, const float* mel, int B, int F, int64_t T, float* x,
                                          float* mean_tot, float* scale_tot, void* tape, size_t tape_bytes, void* ws,
                                          size_t ws_bytes, void* stream) {

@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <shared_mutex>
 #include <string>
@@ -177,6 +178,7 @@ struct wn_handle {
     ArPack ar;
     TeacherPack teacher;
     IafTrainPack iaf_train;
+    std::shared_ptr<void> repack_keep;        // host tables the last wn_iaf_set_weights uploaded (wn_iaf_repack.hip)
     // hoisted conditioning (wn_iaf_c.hip): word offsets of the 8-K-step cond fragment arrays of
     // every layer and head ("row block"), flow after flow, stored as uint32 inside the blob
     size_t cond_tab_off = 0;
@@ -254,6 +256,8 @@ inline size_t wn_grad_floats(const std::vector<WnGradEntry>& t) { return t.empty
 // entry i for the *_grad_info calls (message prefix fn); refuses a bad index, a null output or a short name buffer
 std::vector<WnGradEntry> wn_teacher_grad_table(const wn_handle* h);        // wn_teacher_wgrad.hip: residual stack and head
 std::vector<WnGradEntry> wn_deconv_grad_table(const wn_handle* h, int si);   // wn_deconv_bwd.hip: stack si
+std::vector<WnGradEntry> wn_iaf_grad_table(const wn_handle* h);            // wn_iaf_train.hip: every flow of a student
+int wn_iaf_train_check(wn_handle* h, const char* fn);                       // ... and what its training calls refuse, by name
 int wn_grad_info(const wn_handle* h, const char* fn, const std::vector<WnGradEntry>& t, int i, char* name, size_t name_cap,
                  int64_t* offset, int64_t* shape4, int* ndim);
 

@@ -7,15 +7,15 @@
 // sources of the teacher's GEMM packs, then -- once the absolute maxima of the split packs have come back and pick_scale has
 // chosen their scales -- every split-fp16 pack.  The roundings are wn_pack_h.h's integer code on both sides, the composite
 // bias accumulates in double in the host's order, the composite matrices come from wn_finalize's own kernels (wn_ar_compose), so every word equals what a fresh handle would have uploaded.
+//
+// The index maps live in wn_repack.h as __device__ functions, shared with the student's table-driven re-pack
+// (wn_iaf_repack.hip); the per-stack code of the upsampler's re-pack (wn_repack_deconv_*) is defined here and
+// runs for both calls.
 #include <atomic>
 
-#include "wn_internal.h"
-#include "wn_pack_h.h"
+#include "wn_repack.h"
 
 namespace {
-
-constexpr int TR_NT = 256;
-inline unsigned tr_blocks(size_t n) { return (unsigned)((n + TR_NT - 1) / TR_NT); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // optimiser
@@ -104,17 +104,9 @@ __global__ __launch_bounds__(TR_NT) void tr_adam_kernel(AdamArgs a) {
 // ---------------------------------------------------------------------------------------------------------------------
 // re-pack: plain fp32 parts
 // ---------------------------------------------------------------------------------------------------------------------
-// HWIO [1,1,cin,cout] -> dst[o * ld + col0 + ci] (pack_T of wn_pack_ar); cin = 1, ld = 1 is a plain copy of cout floats
-struct ScatterArgs {
-    const float* src;
-    float* dst;
-    int cin, cout, ld, col0;
-};
+// the index maps are wn_repack.h's; one thread per packed word
 __global__ __launch_bounds__(TR_NT) void tr_scatter_kernel(ScatterArgs a) {
-    const size_t i = (size_t)blockIdx.x * TR_NT + threadIdx.x;
-    if (i >= (size_t)a.cin * a.cout) return;
-    const int o = (int)(i / a.cin), ci = (int)(i % a.cin);
-    a.dst[(size_t)o * a.ld + a.col0 + ci] = a.src[(size_t)ci * a.cout + o];
+    tr_scatter_word(a, (size_t)blockIdx.x * TR_NT + threadIdx.x);
 }
 // dst = x + y: the summed biases
 __global__ __launch_bounds__(TR_NT) void tr_add_kernel(const float* __restrict__ x, const float* __restrict__ y,
@@ -132,90 +124,21 @@ __global__ __launch_bounds__(TR_NT) void tr_bm_kernel(const float* __restrict__ 
     for (int cc = 0; cc < W; ++cc) acc += (double)wd[(size_t)o * K + 2 * W + cc] * (double)brs_prev[cc];
     bm[o] = (float)acc;
 }
-// A-fragment order [row block][k-group of 16][lane][4] of a row-major [rows][KA] matrix; rows beyond `rows` are zero (frag of
-// wn_pack_ar)
 __global__ __launch_bounds__(TR_NT) void tr_frag_kernel(const float* __restrict__ a, float* __restrict__ dst, int rows, int KA) {
-    const int nks4 = KA / 16, mbs = (rows + 15) / 16;
-    const size_t i = (size_t)blockIdx.x * TR_NT + threadIdx.x;
-    if (i >= (size_t)mbs * nks4 * 256) return;
-    const int jj = i & 3, lane = (i >> 2) & 63;
-    const size_t blk = i >> 8;
-    const int k4 = (int)(blk % nks4), mb = (int)(blk / nks4);
-    const int row = 16 * mb + (lane & 15), k = 16 * k4 + 4 * jj + (lane >> 4);
-    dst[i] = row >= rows ? 0.f : a[(size_t)row * KA + k];
+    tr_frag_word(a, dst, rows, KA, (size_t)blockIdx.x * TR_NT + threadIdx.x);
 }
-// fp32 A fragments of one transposed-conv layer: [S][tap, block][mb][lane][4] of W [K][cout][cin] (wn_pack_deconv)
 __global__ __launch_bounds__(TR_NT) void tr_deconv_frag_kernel(const float* __restrict__ W, float* __restrict__ P, int S, int taps,
                                                                int cin, int cout) {
-    const int nmb = cout / 16, cblk = cin / 16, nks4 = taps * cblk;
-    const size_t i = (size_t)blockIdx.x * TR_NT + threadIdx.x;
-    if (i >= (size_t)S * nks4 * nmb * 256) return;
-    const int jj = i & 3, lane = (i >> 2) & 63;
-    size_t rest = i >> 8;
-    const int mb = (int)(rest % nmb);
-    rest /= nmb;
-    const int ks4 = (int)(rest % nks4), r = (int)(rest / nks4);
-    const int tap = ks4 / cblk, c4 = ks4 % cblk;
-    const int co = 16 * mb + (lane & 15), ci = 16 * c4 + 4 * jj + (lane >> 4), k = S * tap + r;
-    P[i] = W[((size_t)k * cout + co) * cin + ci];
+    tr_deconv_frag_word(W, P, S, taps, cin, cout, (size_t)blockIdx.x * TR_NT + threadIdx.x);
 }
-
-// largest |x| of n floats, as the bit pattern of a non-negative float (exact in any order); NaNs are passed over like
-// std::max does in pick_scale.  *out starts at zero.
 __global__ __launch_bounds__(TR_NT) void tr_absmax_kernel(const float* __restrict__ x, size_t n, unsigned* __restrict__ out) {
-    float mx = 0.f;
-    for (size_t i = (size_t)blockIdx.x * TR_NT + threadIdx.x; i < n; i += (size_t)gridDim.x * TR_NT) {
-        const float v = fabsf(x[i]);
-        if (v > mx) mx = v;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    if ((threadIdx.x & 63) == 0 && mx > 0.f) atomicMax(out, __float_as_uint(mx));
+    tr_absmax_block(x, n, out, blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // re-pack: split-fp16 packs.  One thread per packed word of pack_afrag's layout [fragment][plane][lane][4].
 // ---------------------------------------------------------------------------------------------------------------------
-enum { ROW_IDENT = 0, ROW_GATE = 1 };              // rowfn of wn_pack_teacher
-enum { SRC_DIRECT = 0, SRC_T = 1, SRC_GATE_T = 2 };   // the matrix as stored, a transposed column range, gate_t's tap-major form
-__device__ inline int tr_row(int kind, int M, int H, int i) {
-    if (kind == ROW_IDENT) return i < M ? i : -1;
-    const int j = i / 64, lr = i % 64;
-    return lr < 32 ? 32 * j + lr : H + 32 * j + lr - 32;
-}
-struct TileArgs {
-    const float* src;      // row-major matrix inside the blob
-    unsigned* dst;
-    float sc;
-    int ld, nks, mtiles;
-    int rowkind, M, H;     // ROW_*: rows of the pack (ident) / half gate width (gate)
-    int srckind;           // SRC_*
-    int R, c0;             // SRC_T: rows of the source, first column taken
-    int G, W;              // SRC_GATE_T
-};
-__device__ inline float tile_elem(const TileArgs& a, int row, int col) {
-    if (a.srckind == SRC_DIRECT) return a.src[(size_t)row * a.ld + col];
-    if (a.srckind == SRC_T) return col < a.R ? a.src[(size_t)col * a.ld + a.c0 + row] : 0.f;
-    const int k = col / a.G, g = col % a.G;
-    return a.src[(size_t)g * a.ld + k * a.W + row];
-}
-__global__ __launch_bounds__(TR_NT) void tr_tile_kernel(TileArgs a) {
-    const size_t i = (size_t)blockIdx.x * TR_NT + threadIdx.x;
-    if (i >= (size_t)a.mtiles * a.nks * 4 * 512) return;
-    const int ii = i & 3, lane = (i >> 2) & 63, plane = (i >> 8) & 1;
-    const size_t f = i >> 9;
-    const int mb = f & 3, ks = (int)((f >> 2) % a.nks), mt = (int)((f >> 2) / a.nks);
-    const int i16 = lane & 15, kg = lane >> 4;
-    const int row = tr_row(a.rowkind, a.M, a.H, mt * 64 + 16 * mb + i16);
-    uint16_t hh[2];
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const int e = 2 * ii + p;
-        const float v = row < 0 ? 0.f : __fmul_rn(a.sc, tile_elem(a, row, 32 * ks + 16 * (e >> 2) + 4 * kg + (e & 3)));
-        hh[p] = split_half(v, plane);
-    }
-    a.dst[i] = (uint32_t)hh[0] | ((uint32_t)hh[1] << 16);
-}
+__global__ __launch_bounds__(TR_NT) void tr_tile_kernel(TileArgs a) { tr_tile_word(a, (size_t)blockIdx.x * TR_NT + threadIdx.x); }
 // tile-ordered bias of a TeacherGemmPack
 __global__ __launch_bounds__(TR_NT) void tr_tile_bias_kernel(const float* __restrict__ bsrc, float* __restrict__ dst, int n,
                                                              int rowkind, int M, int H) {
@@ -342,7 +265,69 @@ ScaleSlots scale_slots(const wn_handle* h) {
 
 std::atomic<uint64_t> g_repack_serial{1ull << 62};   // tape serials of re-packed handles: apart from wn_finalize's counter
 
+inline void absmax_launch(const float* x, size_t n, unsigned* out, hipStream_t st) {
+    const unsigned nb = (unsigned)std::min<size_t>(256, (n + 4 * TR_NT - 1) / (4 * TR_NT));
+    hipLaunchKernelGGL(tr_absmax_kernel, dim3(nb), dim3(TR_NT), 0, st, x, n, out);
+}
+
 }  // namespace
+
+uint64_t wn_repack_serial_next() { return g_repack_serial++; }
+
+// ---- one upsampler stack (wn_repack.h): kernel, then bias per layer (dgrad_table of wn_deconv_bwd.hip)
+void wn_repack_deconv_absmax(const DeconvStackPack& sp, const std::vector<WnGradEntry>& UT, const float* up, unsigned* amax,
+                             hipStream_t st) {
+    for (size_t j = 0; j < sp.layers.size(); ++j) {
+        const DeconvLayerPack& lp = sp.layers[j];
+        absmax_launch(up + UT[2 * j].off, (size_t)lp.K * lp.cout * lp.cin, amax + j, st);
+    }
+}
+
+void wn_repack_deconv_plain(wn_handle* h, const DeconvStackPack& sp, const std::vector<WnGradEntry>& UT, const float* up,
+                            hipStream_t st) {
+    float* blob = h->d_blob;
+    for (size_t j = 0; j < sp.layers.size(); ++j) {
+        const DeconvLayerPack& lp = sp.layers[j];
+        const size_t total = (size_t)lp.S * lp.taps * (lp.cin / 16) * (lp.cout / 16) * 256;
+        hipLaunchKernelGGL(tr_deconv_frag_kernel, dim3(tr_blocks(total)), dim3(TR_NT), 0, st, up + UT[2 * j].off, blob + lp.w_off,
+                           lp.S, lp.taps, lp.cin, lp.cout);
+        hipLaunchKernelGGL(tr_scatter_kernel, dim3(tr_blocks((size_t)lp.cout)), dim3(TR_NT), 0, st,
+                           ScatterArgs{up + UT[2 * j + 1].off, blob + lp.b_off, 1, lp.cout, 1, 0});
+    }
+}
+
+void wn_repack_deconv_split(wn_handle* h, DeconvStackPack& sp, const std::vector<WnGradEntry>& UT, const float* up, const float* mx,
+                            hipStream_t st) {
+    float* blob = h->d_blob;
+    for (size_t j = 0; j < sp.layers.size(); ++j) {
+        DeconvLayerPack& lp = sp.layers[j];
+        const float* W = up + UT[2 * j].off;
+        const float sc = pick_scale(mx + j, 1);
+        if (lp.w_off_h) {
+            lp.inv_scale_h = 1.0f / sc;
+            const size_t words = (size_t)lp.S * (lp.taps * (lp.cin / 16) / 2) * (lp.cout / 16) * 512;
+            hipLaunchKernelGGL(tr_deconv_h_kernel, dim3(tr_blocks(words)), dim3(TR_NT), 0, st,
+                               DeconvHArgs{W, reinterpret_cast<unsigned*>(blob + lp.w_off_h), sc, lp.S, lp.taps, lp.cin, lp.cout,
+                                           lp.pL, 0, 0, 0});
+        }
+        if (lp.w_off_pg) {
+            const int nb32 = lp.cin / 32;
+            for (int g = 0; g < lp.pg_n; ++g) {
+                const int nsub = lp.pg_nph[g] == 4 ? lp.cout / 32 : lp.cout / 64;
+                const size_t words = (size_t)nsub * nb32 * 4 * 8 * 512;
+                unsigned* dst = reinterpret_cast<unsigned*>(blob + lp.w_off_pg) + (size_t)lp.pg_rg0[g] * nb32 * 4 * 8 * 512;
+                hipLaunchKernelGGL(tr_deconv_h_kernel, dim3(tr_blocks(words)), dim3(TR_NT), 0, st,
+                                   DeconvHArgs{W, dst, sc, lp.S, lp.taps, lp.cin, lp.cout, lp.pL, lp.pg_nph[g], lp.pg_p0[g], nsub});
+            }
+        }
+        if (lp.wt_off) {
+            lp.wt_inv_scale = 1.0f / sc;
+            const size_t n2 = (size_t)lp.K * lp.cin * lp.cout / 2;
+            hipLaunchKernelGGL(tr_deconv_t_kernel, dim3(tr_blocks(n2)), dim3(TR_NT), 0, st, W,
+                               reinterpret_cast<unsigned*>(blob + lp.wt_off), sc, lp.K, lp.cin, lp.cout);
+        }
+    }
+}
 
 extern "C" size_t wn_grad_sumsq_workspace_bytes(size_t n) { return align_up((size_t)ss_blocks(std::max<size_t>(n, 1)) * sizeof(double), 256); }
 
@@ -422,10 +407,7 @@ extern "C" int wn_teacher_set_weights(wn_handle* h, const float* params, size_t 
     auto add = [&](const float* x, const float* y, size_t dst_off, int n) {
         hipLaunchKernelGGL(tr_add_kernel, dim3(tr_blocks(n)), dim3(TR_NT), 0, st, x, y, blob + dst_off, n);
     };
-    auto absmax = [&](const float* x, size_t n, int slot) {
-        const unsigned nb = (unsigned)std::min<size_t>(256, (n + 4 * TR_NT - 1) / (4 * TR_NT));
-        hipLaunchKernelGGL(tr_absmax_kernel, dim3(nb), dim3(TR_NT), 0, st, x, n, amax + slot);
-    };
+    auto absmax = [&](const float* x, size_t n, int slot) { absmax_launch(x, n, amax + slot, st); };
     auto frag = [&](size_t src_off, size_t dst_off, int rows, int Kc) {
         const size_t total = (size_t)((rows + 15) / 16) * (Kc / 16) * 256;
         hipLaunchKernelGGL(tr_frag_kernel, dim3(tr_blocks(total)), dim3(TR_NT), 0, st, blob + src_off, blob + dst_off, rows,
@@ -435,7 +417,7 @@ extern "C" int wn_teacher_set_weights(wn_handle* h, const float* params, size_t 
     TeacherParams Q;
     if (!resolve_params(PT, params, nl, Q)) return wn_fail(h, WN_EINVAL, "%s: the parameter layout is not the model's", fn);
     // From here on the handle changes: tapes written under the old weights are refused, also after a failure below
-    T.serial = g_repack_serial++;
+    T.serial = wn_repack_serial_next();
 
     // ---- 1. absolute maxima of the sources of every split pack
     WN_HIP(h, hipMemsetAsync(amax, 0, (size_t)SL.total() * sizeof(unsigned), st));
@@ -450,14 +432,7 @@ extern "C" int wn_teacher_set_weights(wn_handle* h, const float* params, size_t 
         absmax(Q.skip[i].W, (size_t)H * S, SL.skip((int)i));
     }
     DeconvStackPack* sp = up_params ? &h->stacks[0] : nullptr;
-    std::vector<const float*> upW, upB;
-    if (sp)
-        for (size_t j = 0; j < sp->layers.size(); ++j) {
-            upW.push_back(up_params + UT[2 * j].off);          // kernel, then bias (dgrad_table of wn_deconv_bwd.hip)
-            upB.push_back(up_params + UT[2 * j + 1].off);
-            const DeconvLayerPack& lp = sp->layers[j];
-            absmax(upW[j], (size_t)lp.K * lp.cout * lp.cin, SL.up((int)j));
-        }
+    if (sp) wn_repack_deconv_absmax(*sp, UT, up_params, amax + SL.up(0), st);
 
     // ---- 2. the plain fp32 matrices and biases (wn_pack_ar), the composites, the fp32 fragments
     copy(Q.start.W, A.start_off, 3 * W);
@@ -500,14 +475,7 @@ extern "C" int wn_teacher_set_weights(wn_handle* h, const float* params, size_t 
         frag(A.wo1_off, A.wo1_b_off, S, S + Cd);
         frag(A.wo2_off, A.wo2_b_off, OW, S);
     }
-    if (sp)
-        for (size_t j = 0; j < sp->layers.size(); ++j) {
-            const DeconvLayerPack& lp = sp->layers[j];
-            const size_t total = (size_t)lp.S * lp.taps * (lp.cin / 16) * (lp.cout / 16) * 256;
-            hipLaunchKernelGGL(tr_deconv_frag_kernel, dim3(tr_blocks(total)), dim3(TR_NT), 0, st, upW[j], blob + lp.w_off, lp.S,
-                               lp.taps, lp.cin, lp.cout);
-            copy(upB[j], lp.b_off, lp.cout);
-        }
+    if (sp) wn_repack_deconv_plain(h, *sp, UT, up_params, st);
 
     // ---- 3. the maxima come back (the call's one read-back: it synchronises the stream); pick_scale on the host
     std::vector<float> mx(SL.total());
@@ -559,34 +527,7 @@ extern "C" int wn_teacher_set_weights(wn_handle* h, const float* params, size_t 
         }
         if (T.denc_ok) tile(T.cond_out1_t, scale_of({SL.wo1b()}), A.wo1_off, S + Cd, ROW_IDENT, Cd, SRC_T, S, S);
     }
-    if (sp)
-        for (size_t j = 0; j < sp->layers.size(); ++j) {
-            DeconvLayerPack& lp = sp->layers[j];
-            const float sc = scale_of({SL.up((int)j)});
-            if (lp.w_off_h) {
-                lp.inv_scale_h = 1.0f / sc;
-                const size_t words = (size_t)lp.S * (lp.taps * (lp.cin / 16) / 2) * (lp.cout / 16) * 512;
-                hipLaunchKernelGGL(tr_deconv_h_kernel, dim3(tr_blocks(words)), dim3(TR_NT), 0, st,
-                                   DeconvHArgs{upW[j], reinterpret_cast<unsigned*>(blob + lp.w_off_h), sc, lp.S, lp.taps, lp.cin, lp.cout,
-                                               lp.pL, 0, 0, 0});
-            }
-            if (lp.w_off_pg) {
-                const int nb32 = lp.cin / 32;
-                for (int g = 0; g < lp.pg_n; ++g) {
-                    const int nsub = lp.pg_nph[g] == 4 ? lp.cout / 32 : lp.cout / 64;
-                    const size_t words = (size_t)nsub * nb32 * 4 * 8 * 512;
-                    unsigned* dst = reinterpret_cast<unsigned*>(blob + lp.w_off_pg) + (size_t)lp.pg_rg0[g] * nb32 * 4 * 8 * 512;
-                    hipLaunchKernelGGL(tr_deconv_h_kernel, dim3(tr_blocks(words)), dim3(TR_NT), 0, st,
-                                       DeconvHArgs{upW[j], dst, sc, lp.S, lp.taps, lp.cin, lp.cout, lp.pL, lp.pg_nph[g], lp.pg_p0[g], nsub});
-                }
-            }
-            if (lp.wt_off) {
-                lp.wt_inv_scale = 1.0f / sc;
-                const size_t n2 = (size_t)lp.K * lp.cin * lp.cout / 2;
-                hipLaunchKernelGGL(tr_deconv_t_kernel, dim3(tr_blocks(n2)), dim3(TR_NT), 0, st, upW[j],
-                                   reinterpret_cast<unsigned*>(blob + lp.wt_off), sc, lp.K, lp.cin, lp.cout);
-            }
-        }
+    if (sp) wn_repack_deconv_split(h, *sp, UT, up_params, mx.data() + SL.up(0), st);
     WN_HIP(h, hipGetLastError());
     return WN_OK;
 }

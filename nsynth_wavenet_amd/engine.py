@@ -589,6 +589,43 @@ class Engine(object):
         self._train_frames.clear()
         return self
 
+    # ---- student training step on the device (the trainer is train.StudentTrainer) ----
+    def iaf_stack_scopes(self):
+        """scopes of the student's deconv stacks, in the order of d_encoding's leading axis"""
+        if getattr(self.hp, 'use_share_deconv', False):
+            return ['iaf_share']
+        return ['iaf_{:d}'.format(k + 1) for k in range(self.iaf_n_stacks())]
+
+    def iaf_set_weights(self, params, up_params=None):
+        """Re-pack this finalized student's weights in place from flat float32 device buffers: `params` in the layout of
+        iaf_grad_table(), `up_params` {scope: buffer in the layout of deconv_grad_table(scope)} or None; a stack whose scope is
+        missing keeps its packs.  The handle then holds what load_weights of the same values would have built, for generation
+        in every launch form and for the training calls.  Synchronises the current stream once (the scales' maxima are read
+        back); tapes written before the call are refused afterwards.  A switch: RuntimeError (WN_ESTATE) while another
+        thread's work call is inside the library."""
+        _flat_f32('iaf_set_weights', 'params', params)
+        up_params = dict(up_params or {})
+        scopes = self.iaf_stack_scopes()
+        unknown = sorted(set(up_params) - set(scopes))
+        if unknown:
+            raise ValueError('iaf_set_weights: no deconv stack with scope {} (the student has {})'.format(unknown, scopes))
+        for scope, t in up_params.items():
+            _flat_f32('iaf_set_weights', 'up_params[{!r}]'.format(scope), t)
+        n_up = len(scopes) if up_params else 0
+        ptrs = (ctypes.c_void_p * max(n_up, 1))(*[up_params[s].data_ptr() if s in up_params else None for s in scopes[:n_up]])
+        sizes = (ctypes.c_size_t * max(n_up, 1))(*[up_params[s].numel() if s in up_params else 0 for s in scopes[:n_up]])
+        with torch.cuda.device(self.device):
+            nb = int(self.lib.wn_iaf_set_weights_workspace_bytes(self._h))
+            ws = torch.empty(max(nb, 256), dtype=torch.uint8, device=self.device)
+            self._check(self.lib.wn_iaf_set_weights(self._h, _ptr(params), params.numel(), ptrs, sizes, n_up, _ptr(ws),
+                                                    nb if nb else ws.numel(), self._stream()))
+        self._train_frames.clear()
+        return self
+
+    def iaf_grad_floats(self):
+        """floats of the flat buffer iaf_grad_table() lays out (0 for a model the training calls refuse)"""
+        return int(self.lib.wn_iaf_grad_floats(self._h))
+
     def teacher_grad_floats(self):
         """floats of the flat buffer teacher_grad_table() lays out"""
         return int(self.lib.wn_teacher_grad_floats(self._h))

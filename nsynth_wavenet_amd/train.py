@@ -1,4 +1,4 @@
-"""Training the teacher on the device: train_wavenet.py's AdamOptimizer(lr, epsilon=1e-8), its optional
+"""Training on the device.  The teacher: train_wavenet.py's AdamOptimizer(lr, epsilon=1e-8), its optional
 clip_by_global_norm and its ExponentialMovingAverage(0.9999, num_updates=global_step) on top of
 Wavenet.loss_and_weight_grads, with the updated weights re-packed into the SAME handle by Engine.teacher_set_weights.  No
 weight and no gradient crosses to the host during a step.
@@ -8,6 +8,14 @@ weight and no gradient crosses to the host during a step.
     for batch in batches:                       # {'wav': [B,T], 'mel': [B,F,80]}
         out = trainer.step(batch)               # {'loss', 'log_probs', 'grad_norm'}: device tensors
     np.savez('eval.npz', **trainer.weights(ema=True))
+
+The student: train_parallel_wavenet.py's loop -- the same optimiser and shadow over the variables of the flows
+and of the deconv stacks the student owns -- on top of ParallelWavenet.loss_and_weight_grads and Engine.iaf_set_weights.
+
+    student = ParallelWavenet(hparams, teacher=teacher).load_weights(w)
+    trainer = StudentTrainer(student, w, lr={0: 2e-4, 90000: 6e-5})
+    for batch in batches:                       # {'wav': [B,T'], 'mel': [B,F,80]} (+ 'mel_rand')
+        out = trainer.step(batch)               # calculate_loss's entries and 'grad_norm': device tensors
 """
 import math
 
@@ -78,7 +86,79 @@ def dropout_step_seed(base, step):
     return (int(base) + int(step) * 0x9E3779B97F4A7C15) & (2 ** 64 - 1)
 
 
-class TeacherTrainer(object):
+class _DeviceTrainer(object):
+    """What the two trainers share: the flat (p, m, v, ema) buffers of one or more gradient tables scattered from a weights
+    dict, the Adam / EMA update with its learning-rate bookkeeping, and weights() / use_ema() / use_weights().  A subclass sets
+    self.eng and implements _repack(bufs)."""
+
+    def _init_optimiser(self, lr, beta1, beta2, eps, ema_decay, clip_norm):
+        self.lr, self.beta1, self.beta2, self.eps = lr, float(beta1), float(beta2), float(eps)
+        self.ema_decay = float(ema_decay)
+        self.clip_norm = None if clip_norm is None else float(clip_norm)
+        scheduled_lr(lr, 0)
+
+    def _init_buffers(self, weights, tables, sizes):
+        """tables: [[(tf name, float offset, TF shape)]], sizes: the library's float count of each"""
+        who = type(self).__name__
+        dev = self.eng.device
+        self.tables = tables
+        self.p, self.m, self.v, self.ema = [], [], [], []
+        for tab, size in zip(tables, sizes):
+            flat = np.zeros(size, np.float32)        # the library's own count; anything a table does not cover stays zero
+            for name, off, shape in tab:
+                a = np.asarray(weights[name], np.float32)
+                if a.size != int(np.prod(shape)):
+                    raise ValueError('{}: {} has {} values, the model expects shape {}'.format(who, name, a.size, shape))
+                flat[off:off + a.size] = a.reshape(-1)          # Saver(reshape=True): same element count
+            p = torch.from_numpy(flat).to(dev)
+            self.p.append(p)
+            self.m.append(torch.zeros_like(p))
+            self.v.append(torch.zeros_like(p))
+            self.ema.append(p.clone())
+        trained = set(name for tab in tables for name, _, _ in tab)
+        self._frozen = {k: np.array(a, np.float32) for k, a in weights.items() if k not in trained}   # upsampler=False
+        self.sumsq = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.global_step = 0              # completed steps
+        self.lr_t = None                  # the bias-corrected rate of the last step, as handed to the kernel (float32)
+        self.lr_history = []              # the scheduled rate of every step
+
+    def _update(self, flats):
+        """grad_sumsq chained over the buffers and adam_ema_step on each; returns the global norm (0-d float64 device tensor)"""
+        n, t = self.global_step, self.global_step + 1
+        lr = scheduled_lr(self.lr, n)
+        self.lr_history.append(lr)
+        self.lr_t = float(np.float32(lr * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t)))
+        decay_t = min(self.ema_decay, (1.0 + n) / (10.0 + n))
+        for i, g in enumerate(flats):
+            grad_sumsq(g, self.sumsq, accumulate=i > 0)
+        for p, g, m, v, e in zip(self.p, flats, self.m, self.v, self.ema):
+            adam_ema_step(p, g, m, v, e, self.lr_t, self.beta1, self.beta2, self.eps, decay_t,
+                          sumsq=self.sumsq if self.clip_norm is not None else None,
+                          clip_norm=self.clip_norm if self.clip_norm is not None else 1.0)
+        return self.sumsq.sqrt()[0]
+
+    def weights(self, ema=False):
+        """{tf name: numpy array in the TF shape} of every variable of the model: the weights, or with ema=True the shadow
+        values under the plain names (what make_eval_model.py writes), for load_weights or an .npz for restore.  Variables that
+        are not trained (the upsampler's with upsampler=False) come back as they were given."""
+        out = {k: a.copy() for k, a in self._frozen.items()}
+        for tab, buf in zip(self.tables, self.ema if ema else self.p):
+            host = buf.cpu().numpy()
+            for name, off, shape in tab:
+                out[name] = host[off:off + int(np.prod(shape))].reshape(shape).copy()
+        return out
+
+    def use_ema(self):
+        """Pack the shadow values into the handle, for generation after training (use_weights() puts the weights back)."""
+        self._repack(self.ema)
+        return self
+
+    def use_weights(self):
+        self._repack(self.p)
+        return self
+
+
+class TeacherTrainer(_DeviceTrainer):
     """One teacher handle trained step after step.
 
     wavenet:  a loaded Wavenet (MoL or Gauss, no mu-law, no weight norm; a resize-conv upsampler needs upsampler=False).
@@ -100,41 +180,19 @@ class TeacherTrainer(object):
                  upsampler=True, dropout=False, dropout_seed=0):
         self.net = wavenet
         self.eng = eng = wavenet.engine
-        self.lr, self.beta1, self.beta2, self.eps = lr, float(beta1), float(beta2), float(eps)
-        self.ema_decay = float(ema_decay)
-        self.clip_norm = None if clip_norm is None else float(clip_norm)
+        self._init_optimiser(lr, beta1, beta2, eps, ema_decay, clip_norm)
         self.upsampler = bool(upsampler)
         self.dropout, self.dropout_seed = bool(dropout), int(dropout_seed)
         if self.dropout and not (wavenet.dropout_inputs or wavenet.dropout_all):
             raise ValueError('TeacherTrainer: dropout=True, but the hparams set neither dropout_inputs nor dropout_all')
-        scheduled_lr(lr, 0)
-        self.tables = [eng.teacher_grad_table()]
+        tables = [eng.teacher_grad_table()]
         if self.upsampler:
-            self.tables.append(eng.deconv_grad_table(''))
-        if not all(self.tables):
+            tables.append(eng.deconv_grad_table(''))
+        if not all(tables):
             raise ValueError('TeacherTrainer: this model has no weight gradients on the device (mu-law, ce, weight norm or '
                              'a resize-conv upsampler with upsampler=True)')
-        dev = eng.device
-        self.p, self.m, self.v, self.ema = [], [], [], []
         sizes = [eng.teacher_grad_floats()] + ([eng.deconv_grad_floats('')] if self.upsampler else [])
-        for tab, size in zip(self.tables, sizes):
-            flat = np.zeros(size, np.float32)        # the library's own count; anything a table does not cover stays zero
-            for name, off, shape in tab:
-                a = np.asarray(weights[name], np.float32)
-                if a.size != int(np.prod(shape)):
-                    raise ValueError('TeacherTrainer: {} has {} values, the model expects shape {}'.format(name, a.size, shape))
-                flat[off:off + a.size] = a.reshape(-1)          # Saver(reshape=True): same element count
-            p = torch.from_numpy(flat).to(dev)
-            self.p.append(p)
-            self.m.append(torch.zeros_like(p))
-            self.v.append(torch.zeros_like(p))
-            self.ema.append(p.clone())
-        trained = set(name for tab in self.tables for name, _, _ in tab)
-        self._frozen = {k: np.array(a, np.float32) for k, a in weights.items() if k not in trained}   # upsampler=False
-        self.sumsq = torch.zeros(1, dtype=torch.float64, device=dev)
-        self.global_step = 0              # completed steps
-        self.lr_t = None                  # the bias-corrected rate of the last step, as handed to the kernel (float32)
-        self.lr_history = []              # the scheduled rate of every step
+        self._init_buffers(weights, tables, sizes)
 
     def _grads(self, inputs):
         seed = dropout_step_seed(self.dropout_seed, self.global_step) if self.dropout else None
@@ -143,21 +201,6 @@ class TeacherTrainer(object):
         if self.upsampler:
             flats.append(out['flat_upsampler_grads'])
         return out, flats
-
-    def _update(self, flats):
-        """grad_sumsq over both buffers and adam_ema_step on both; returns the global norm (0-d float64 device tensor)"""
-        n, t = self.global_step, self.global_step + 1
-        lr = scheduled_lr(self.lr, n)
-        self.lr_history.append(lr)
-        self.lr_t = float(np.float32(lr * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t)))
-        decay_t = min(self.ema_decay, (1.0 + n) / (10.0 + n))
-        for i, g in enumerate(flats):
-            grad_sumsq(g, self.sumsq, accumulate=i > 0)
-        for p, g, m, v, e in zip(self.p, flats, self.m, self.v, self.ema):
-            adam_ema_step(p, g, m, v, e, self.lr_t, self.beta1, self.beta2, self.eps, decay_t,
-                          sumsq=self.sumsq if self.clip_norm is not None else None,
-                          clip_norm=self.clip_norm if self.clip_norm is not None else 1.0)
-        return self.sumsq.sqrt()[0]
 
     def _repack(self, bufs):
         self.eng.teacher_set_weights(bufs[0], bufs[1] if self.upsampler else None)
@@ -173,22 +216,58 @@ class TeacherTrainer(object):
         self.global_step += 1
         return {'loss': out['loss'], 'log_probs': out['log_probs'], 'grad_norm': norm}
 
-    def weights(self, ema=False):
-        """{tf name: numpy array in the TF shape} of every variable of the model: the weights, or with ema=True the shadow
-        values under the plain names (what make_eval_model.py writes), for load_weights or an .npz for restore.  Variables that
-        are not trained (the upsampler's with upsampler=False) come back as they were given."""
-        out = {k: a.copy() for k, a in self._frozen.items()}
-        for tab, buf in zip(self.tables, self.ema if ema else self.p):
-            host = buf.cpu().numpy()
-            for name, off, shape in tab:
-                out[name] = host[off:off + int(np.prod(shape))].reshape(shape).copy()
-        return out
 
-    def use_ema(self):
-        """Pack the shadow values into the handle, for generation after training (use_weights() puts the weights back)."""
-        self._repack(self.ema)
-        return self
+class StudentTrainer(_DeviceTrainer):
+    """One student handle distilled step after step (train_parallel_wavenet.py's loop).
 
-    def use_weights(self):
+    pw:       a loaded ParallelWavenet with a teacher (logistic under a MoL teacher or Gauss under Gauss; no mu-law, no weight
+              norm; width and deconv_width multiples of 64).  The teacher stays frozen.
+    weights:  the dict the student was loaded from.
+    lr, beta1, beta2, eps, ema_decay, clip_norm: as for TeacherTrainer.
+    upsampler: also train the deconv stacks the student owns ('iaf_share', or 'iaf_k' per flow), as the reference's
+              filter_update_variables keeps them; with use_teacher_deconv the encoding is the teacher's and no stack is trained.
+    seed:     step k (k completed steps before it) runs loss_and_weight_grads(seed=seed + k): the student's draw (unless
+              `noise` is handed to step) and the Monte-Carlo draws of the losses.
+
+    Buffers: one (p, m, v, ema) set for the flows, laid out by Engine.iaf_grad_table(), and one per trained stack, laid out
+    by Engine.deconv_grad_table(scope).  Order inside a step, the learning-rate schedule and the EMA decay are
+    TeacherTrainer's."""
+
+    def __init__(self, pw, weights, lr=2e-4, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay=0.9999, clip_norm=None,
+                 upsampler=True, seed=0):
+        if getattr(pw, 'teacher', None) is None:
+            raise ValueError('StudentTrainer needs a student with a teacher: ParallelWavenet(hparams, teacher=Wavenet(te_hparams))')
+        self.net = pw
+        self.eng = eng = pw.engine
+        self._init_optimiser(lr, beta1, beta2, eps, ema_decay, clip_norm)
+        self.seed = int(seed)
+        self.upsampler = bool(upsampler) and not getattr(pw, 'use_teacher_deconv', False)
+        tables = [eng.iaf_grad_table()]
+        if not tables[0]:
+            raise ValueError('StudentTrainer: this model has no weight gradients on the device (mu-law, weight norm, or a '
+                             'width / deconv_width that is no multiple of 64)')
+        sizes = [eng.iaf_grad_floats()]
+        self.scopes = list(eng.iaf_stack_scopes()) if self.upsampler else []
+        for scope in self.scopes:
+            tables.append(eng.deconv_grad_table(scope))
+            sizes.append(eng.deconv_grad_floats(scope))
+        if not all(tables):
+            raise ValueError('StudentTrainer: a deconv stack has no weight gradients on the device (a resize-conv upsampler needs '
+                             'upsampler=False)')
+        self._init_buffers(weights, tables, sizes)
+
+    def _repack(self, bufs):
+        self.eng.iaf_set_weights(bufs[0], dict(zip(self.scopes, bufs[1:])))
+
+    def step(self, inputs, noise=None):
+        """One training step on {'mel': [B,F,80], 'wav': [B,T'] (+ 'mel_rand')} -> calculate_loss's entries BEFORE the update
+        (the bits of loss_and_weight_grads(inputs, seed=seed + global_step, noise=noise) under the weights in force at entry)
+        plus 'grad_norm', the global norm of the gradient before clipping; all device tensors."""
+        out = self.net.loss_and_weight_grads(inputs, seed=self.seed + self.global_step, noise=noise, upsampler=self.upsampler)
+        flats = [out['flat_grads']] + [out['flat_upsampler_grads'][s] for s in self.scopes]
+        norm = self._update(flats)
         self._repack(self.p)
-        return self
+        self.global_step += 1
+        ret = {k: v for k, v in out.items() if k not in ('grads', 'flat_grads', 'd_encoding', 'flat_upsampler_grads')}
+        ret['grad_norm'] = norm
+        return ret
