@@ -701,6 +701,172 @@ __global__ __launch_bounds__(256) void deconv_interleave_g4_kernel(
     wn_range_flag(amax, status);
 }
 
+// ---------------------------------------------------------------------------
+// Upsampler front: the FIRST layer of a split-fp16 stack (mel in, 4 taps, 80 -> 256 channels) in one launch, fp32 mel in,
+// finished G4 words out -- in place of mel_to_split_kernel + deconv_mfma_h_kernel<false> + deconv_interleave_g4_kernel.
+// The layer is almost no arithmetic (at 384 frames: 115 k MFMAs, 3.3 MB of fragments, 3.9 MB of words out); the three launches
+// spent their time on two launch boundaries, two round trips through memory (split mel words, phase-major fp32) and an 80-workgroup
+// GEMM that walked its ten K-steps as one dependent chain of load -> LDS -> MFMA.  Here:
+//   unit       one workgroup = one output phase p x one block of 16 frames x all 256 channels; wave w owns channels
+//              [32 w, 32 w + 32) = two MFMA row blocks, 60 MFMAs.  Sample t = S f + p is  b + sum_j W[S j + r] . mel[f + d - j]
+//              with r = (p + pL) % S, d = (p + pL) / S (the frame axis of deconv_pg_kernel), so a workgroup has ONE kernel
+//              offset r and the frame blocks tile [0, F) exactly.  10 x 24 units at 4.8 s: one round of the chip.
+//   weights    every wave reads the fragments of its rows straight into registers (4 x 16 B per lane and K-step, the first-layer
+//              pack lp.w_off_h as it is: a wave's share of a K-step is 4 KB contiguous), DF_PF = 3 K-steps ahead of the MFMAs
+//              that use them.  A workgroup pulls all 320 KB of its phase through one CU's vector-memory path (64 B/clk: 5 000
+//              clocks); with all ten K-steps requested in front of the loop the waves sat in that queue for 6 000 clocks before
+//              the first MFMA and the loop's 5 300 came on top (cycle stamps, profiles/upsampler_front_ab.txt); three steps
+//              ahead, the queue drains under the MFMAs: 8.9 against 11.3 us for the launch.
+//   mel        the 19 frames f0 + d - 3 .. f0 + d + 15 the block's four taps read are split ONCE per workgroup (760 pairs, at
+//              most two per thread; zeros outside [0, F) as the padded buffer had them) into a 6 KB LDS window while the
+//              fragments are in flight; each lane picks its operand words from there.  The range guard of the split moves along.
+//   K loop     K-step order and the term order (hh, hl, lh) of the three launches: every accumulator sees the same additions
+//              in the same order, so the words are the same bits.
+//   epilogue   de-scale (rounded), + bias (rounded), activation, split -- the operations of deconv_mfma_h_kernel's store and
+//              deconv_interleave_g4_kernel, in their order.  The two row blocks of a wave are the four pair slots of G4 group
+//              4 w + kg (as in deconv_pg_kernel), so a lane holds ONE finished word per plane: two 16-byte stores.
+//   margins    the workgroups of the last frame block also write what the interleave launch wrote around the data: the DC_XOFF
+//              zero columns left of sample 0 and the zeros from sample S F to the row stride (rows dealt out over the phases).
+// blockIdx.x = xcd + 8 k -> unit xcd * (gridDim.x / 8) + k, units ordered (phase, utterance, frame block): an XCD's L2 holds the
+// fragments of at most two phases.
+constexpr int DF_WAVES = 8;
+constexpr int DF_CIN = 80;                               // mel channels: 5 blocks of 16, 40 pairs
+constexpr int DF_NKS = 4 * (DF_CIN / 16) / 2;            // K-steps: 4 taps x 5 blocks / 2
+constexpr int DF_WIN = 16 + 3;                           // frames of mel per workgroup
+constexpr int DF_PF = 3;                                 // K-steps of fragments requested ahead of the MFMAs
+
+// a * s, rounded, then + b, rounded: what a store of the product and a later kernel's addition compute (the compiler contracts
+// a plain a * s + b into one fma, and __fmul_rn / __fadd_rn with it)
+__device__ inline float mul_round_add(float a, float s, float b) {
+#pragma clang fp contract(off)
+    const float m = a * s;
+    return m + b;
+}
+
+struct FrontArgs {
+    const float* mel;         // [B][F][80]
+    int B, F;
+    const unsigned* wp;       // lp.w_off_h: [r][ks][mb][plane][lane][4]
+    const float* bias;
+    float inv_scale;
+    unsigned* y;              // G4 rows [B][2][32][ys] x 16 B, sample t at column DC_XOFF + t
+    int ys;
+    int S, pL, act;
+    int ncb, nunits;          // frame blocks per utterance; S * B * ncb
+    unsigned* status;
+};
+
+__global__ __launch_bounds__(DF_WAVES * 64) void deconv_front_kernel(const FrontArgs A) {
+    __shared__ __attribute__((aligned(16))) unsigned win[2][DF_WIN][DF_CIN / 2];
+    const int u = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    if (u >= A.nunits) return;
+    const int cb = u % A.ncb, pb = u / A.ncb;
+    const int b = pb % A.B, p = pb / A.B;
+    const int r = (p + A.pL) % A.S, d = (p + A.pL) / A.S;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n = lane & 15, kg = lane >> 4;
+    const int f0 = 16 * cb;
+    constexpr int ng = 32, nmb = 16;
+
+    // the window's mel pairs of this thread, then the first DF_PF K-steps of fragments, then the split: their latency covers it
+    const float* melb = A.mel + (size_t)b * A.F * DF_CIN;
+    constexpr int NP = (DF_WIN * (DF_CIN / 2) + DF_WAVES * 64 - 1) / (DF_WAVES * 64);
+    wn_f2 mv[NP];
+    bool mok[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        const int i = threadIdx.x + k * DF_WAVES * 64;
+        const int fl = i / (DF_CIN / 2), pr = i - fl * (DF_CIN / 2);
+        const int fr = f0 + d - 3 + fl;
+        mok[k] = fl < DF_WIN && fr >= 0 && fr < A.F;
+        // (always a load, from a clamped frame: behind a branch the compiler waits for it before it requests the fragments)
+        mv[k] = *reinterpret_cast<const wn_f2 __attribute__((aligned(4)))*>(melb + (size_t)min(max(fr, 0), A.F - 1) * DF_CIN + 2 * pr);
+    }
+    f4 bs[2];                                            // bias of rows 4 kg .. 4 kg + 3 of the wave's two row blocks
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb) bs[mb] = *reinterpret_cast<const f4u*>(A.bias + 32 * wave + 16 * mb + 4 * kg);
+    const wn_u4* wsrc = reinterpret_cast<const wn_u4*>(A.wp) + ((size_t)r * DF_NKS * nmb + 2 * wave) * 128 + lane;
+    wn_u4 ah[DF_NKS][2], al[DF_NKS][2];
+    auto loadA = [&](int ks) {
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb) {
+            ah[ks][mb] = wsrc[(ks * nmb + mb) * 128];
+            al[ks][mb] = wsrc[(ks * nmb + mb) * 128 + 64];
+        }
+        __builtin_amdgcn_sched_barrier(0);               // (requests stay in K order, DF_PF steps ahead of their MFMAs)
+    };
+#pragma unroll
+    for (int ks = 0; ks < DF_PF; ++ks) loadA(ks);
+    float amax = 0.f;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        const int i = threadIdx.x + k * DF_WAVES * 64;
+        const int fl = i / (DF_CIN / 2), pr = i - fl * (DF_CIN / 2);
+        if (fl < DF_WIN) {
+            unsigned hw = 0, lw = 0;
+            if (mok[k]) wn_split_pair_t(mv[k].x, mv[k].y, hw, lw, amax);
+            win[0][fl][pr] = hw;
+            win[1][fl][pr] = lw;
+        }
+    }
+    __syncthreads();
+
+    f4 acc[2];
+    acc[0] = acc[1] = (f4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < DF_NKS; ++ks) {
+        if (ks + DF_PF < DF_NKS) loadA(ks + DF_PF);
+        // k-slot (kg, e) <-> channel 16 blk + 4 kg + (e & 3) of tap j, (j, blk) = flattened block 2 ks + (e >> 2): word i of the
+        // operand is pair row 8 blk + 2 kg + (i & 1) of frame f0 + n + d - j = window row n + 3 - j
+        wn_u4 vh, vl;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int g = 2 * ks + (i >> 1);
+            const int j = g / (DF_CIN / 16), blk = g - j * (DF_CIN / 16);
+            vh[i] = win[0][n + 3 - j][8 * blk + 2 * kg + (i & 1)];
+            vl[i] = win[1][n + 3 - j][8 * blk + 2 * kg + (i & 1)];
+        }
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb) {
+            f4 c = acc[mb];
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(wn_h8, ah[ks][mb]), __builtin_bit_cast(wn_h8, vh), c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(wn_h8, ah[ks][mb]), __builtin_bit_cast(wn_h8, vl), c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(wn_h8, al[ks][mb]), __builtin_bit_cast(wn_h8, vh), c, 0, 0, 0);
+            acc[mb] = c;
+        }
+    }
+
+    // ---- epilogue: rows 4 kg .. 4 kg + 3 of the wave's two row blocks = the four pair slots of G4 group 4 wave + kg ----
+    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(A.y + (size_t)b * 2 * ng * A.ys * 4), 0, 2 * ng * A.ys * 16, 0x00020000);
+    const int lo_out = ng * A.ys * 16;
+    wn_u4 hw, lw;
+#pragma unroll
+    for (int slot = 0; slot < 4; ++slot) {
+        const int mb = slot >> 1, r0 = (slot & 1) * 2;
+        // (two roundings, as the phase-major store and the interleave had them: no fma)
+        const float v0 = apply_act(mul_round_add(acc[mb][r0], A.inv_scale, bs[mb][r0]), A.act);
+        const float v1 = apply_act(mul_round_add(acc[mb][r0 + 1], A.inv_scale, bs[mb][r0 + 1]), A.act);
+        unsigned a, c2;
+        wn_split_pair_t(v0, v1, a, c2, amax);
+        hw[slot] = a;
+        lw[slot] = c2;
+    }
+    const int f = f0 + n;
+    {
+        const int vo = f < A.F ? ((4 * wave + kg) * A.ys + DC_XOFF + A.S * f + p) * 16 : (int)0x80000000;
+        buf_st4(hw, ry, vo, 0);
+        buf_st4(lw, ry, vo, lo_out);
+    }
+    wn_range_flag(amax, A.status);
+    if (cb + 1 == A.ncb) {
+        const int SL = A.S * A.F, nz = A.ys - SL;            // DC_XOFF columns on the left, the rest behind sample S F
+        for (int row = p; row < 2 * ng; row += A.S)
+            for (int i = threadIdx.x; i < nz; i += DF_WAVES * 64)
+                buf_st4((wn_u4){0u, 0u, 0u, 0u}, ry, (row * A.ys + (i < DC_XOFF ? i : SL + i)) * 16, 0);
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -913,7 +1079,16 @@ int wn_run_deconv(wn_handle* h, int si, const float* mel, int B, int F, float* e
     for (const DeconvLayerPack& lp : sp.layers) h_gemm = h_gemm && lp.w_off_h != 0;
     float* buf = reinterpret_cast<float*>(scratch);
     int xs = dc_row_stride(F);
-    if (h_gemm) {
+    // deconv_front_kernel: the first layer in one launch where it is 4 taps x 80 mel channels -> 256 channels and the stack
+    // ends in deconv_pg_kernel (the condition of that branch below); every other stack keeps the three launches
+    const DeconvLayerPack& l0 = sp.layers.front();
+    const DeconvLayerPack& ll = sp.layers.back();
+    const bool front = h_gemm && c.n_deconv >= 2 && split_out && ll.w_off_pg && !h->dc_no_pg && l0.taps == 4 &&
+                       l0.cin == DF_CIN && l0.cout == 256 &&
+                       (int64_t)64 * 16 * dc_row_stride(F * l0.S) < ((int64_t)1 << 31);      // (32-bit store offsets)
+    if (front) {
+        // mel is split inside the launch
+    } else if (h_gemm) {
         dim3 g((xs + 255) / 256, c.n_mel / 2, B);
         hipLaunchKernelGGL(mel_to_split_kernel, g, dim3(256), 0, st, mel, reinterpret_cast<unsigned*>(buf), F,
                            c.n_mel, xs, status);
@@ -946,6 +1121,23 @@ int wn_run_deconv(wn_handle* h, int si, const float* mel, int B, int F, float* e
         const bool next_g4 = h_gemm && !last;
         // zero pads of an intermediate output: the G4 interleave writes them itself, the other forms get a memset
         if (!last && !next_g4) WN_HIP(h, hipMemsetAsync(y, 0, (size_t)B * lp.cout * ys * sizeof(float), st));
+        if (front && j == 0) {
+            FrontArgs A{};
+            A.mel = mel; A.B = B; A.F = F;
+            A.wp = reinterpret_cast<const unsigned*>(h->d_blob + lp.w_off_h);
+            A.bias = h->d_blob + lp.b_off;
+            A.inv_scale = lp.inv_scale_h;
+            A.y = reinterpret_cast<unsigned*>(y);
+            A.ys = (int)ys;
+            A.S = lp.S; A.pL = lp.pL; A.act = c.upsample_act;
+            A.ncb = (F + 15) / 16;
+            A.nunits = lp.S * B * A.ncb;
+            A.status = status;
+            hipLaunchKernelGGL(deconv_front_kernel, dim3((A.nunits + 7) / 8 * 8), dim3(DF_WAVES * 64), 0, st, A);
+            in_g4 = true;
+            x = y; xs = (int)ys; next = y + (size_t)B * lp.cout * ys; L = Lout;
+            continue;
+        }
         // (h->dc_no_pg: WN_DC_NO_PG=1 at wn_create keeps the phase-major GEMM + interleave of rounds 1-4: A/B runs, cross-form test)
         if (h_gemm && in_g4 && last && split_out && lp.w_off_pg && !h->dc_no_pg) {
             PgArgs A{};
