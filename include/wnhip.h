@@ -226,6 +226,41 @@ WN_API int wn_iaf_range_status(wn_handle* h, const void* ws, void* stream);
 WN_API int wn_iaf_range_reset(wn_handle* h, void* ws, void* stream);
 WN_API int wn_iaf_range_status_since_reset(wn_handle* h, void* ws, void* stream);
 
+/* Windowed generation: utterances of any length as a batch of windows.
+ *
+ * Geometry a planner needs: `reach` = samples to the left of t that sample t depends on (sum over the flows of
+ * filter_length + (filter_length - 1) sum of the flow's dilations; 12 288 for the shipped configs); frames_before /
+ * frames_after = mel frames left / right of the frame holding an upsampled column that reach that column through the
+ * deconv stack; period = max_dilation / gcd(frame_shift, max_dilation): the centre crop of a call on F frames depends on
+ * F modulo it.  Any output pointer may be NULL.  nsynth_wavenet_amd.config.iaf_plan_windows is a planner on top of it. */
+WN_API int wn_iaf_window_geometry(const wn_handle* h, int64_t* reach, int* frames_before, int* frames_after, int* period);
+
+/* One row of a window call: an ordinary row of T_w = wn_iaf_length(h, Fw) samples whose local sample t is sample
+ * t_origin + t of utterance b; of these the local range [keep_from, keep_to) is written, to out[b][out_t ..]. */
+typedef struct wn_iaf_window_row {
+    int32_t b;
+    int64_t t_origin, keep_from, keep_to, out_t;
+} wn_iaf_window_row;
+
+/* wn_iaf_generate_form on R rows of Fw frames (mel [R,Fw,n_mel], each row in the natural layout of a call on Fw frames)
+ * with two differences.  The noise of row r is the noise of utterance b at t_origin + t: drawn from `seed` with the
+ * counter of a one-shot call at that position (a row with b = r, t_origin = 0 gets the one-shot's bits), or read from
+ * noise_abs [B_out,T_out] (0 outside [0, T_out)).  And only the kept samples leave, into COMPACT outputs
+ * wav, idx, x_raw, mean_tot, scale_tot, rand_out [B_out,T_out] (all but wav optional).  rows_host is a HOST array; the
+ * call copies it.  Refused with WN_EINVAL: everything wn_iaf_generate_form refuses; b outside [0, B_out); a t_origin
+ * that is negative or not a multiple of 4; a kept range outside [0, T_w); out_t plus the kept length past T_out; kept
+ * ranges of two rows that overlap in the output.  The 2,000,000-sample limit applies to Fw frame_shift.  Whether the
+ * residual layers run as layer groups is the one-shot's policy for a batch of form_rows rows (0: R); with a fixed
+ * form_rows a row's result does not depend on how many rows share its call.  The range guard
+ * and wn_iaf_range_status* work as for the one-shot call: a fault in any row makes every kept sample of the call NaN. */
+WN_API int wn_iaf_generate_windows(wn_handle* h, int form, int form_rows, const float* mel, int R, int Fw,
+                            const wn_iaf_window_row* rows_host, const float* noise_abs, int B_out, int64_t T_out,
+                            uint64_t seed, float* wav, int32_t* idx, float* x_raw,
+                            float* mean_tot, float* scale_tot, float* rand_out,
+                            void* ws, size_t ws_bytes, void* stream);
+/* wn_iaf_workspace_bytes_form(h, form, R, Fw) plus the row table (0 for a bad argument) */
+WN_API size_t wn_iaf_windows_workspace_bytes(const wn_handle* h, int R, int Fw, int form);
+
 /* _clip_quant_scale on its own (parallel_wavenet.py:347-359 with
  * utils.cast_quantize / inv_cast_quantize / inv_mu_law, utils.py:108-159):
  * x[n] -> wav[n], idx[n].  Bit-exact integer index. */

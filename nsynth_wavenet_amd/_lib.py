@@ -27,7 +27,14 @@ SYMBOLS = ['wn_abi_version', 'wn_create', 'wn_set_weight', 'wn_finalize', 'wn_ia
            'wn_teacher_train_tape_dropout_bytes', 'wn_teacher_forward_train_tape_dropout', 'wn_teacher_dropout_keep',
            'wn_iaf_grad_count', 'wn_iaf_grad_info', 'wn_iaf_grad_floats', 'wn_iaf_train_tape_bytes',
            'wn_iaf_train_workspace_bytes', 'wn_iaf_forward_train_tape', 'wn_iaf_backward_weights_workspace_bytes',
-           'wn_iaf_backward_weights', 'wn_iaf_set_weights_workspace_bytes', 'wn_iaf_set_weights']
+           'wn_iaf_backward_weights', 'wn_iaf_set_weights_workspace_bytes', 'wn_iaf_set_weights',
+           'wn_iaf_window_geometry', 'wn_iaf_generate_windows', 'wn_iaf_windows_workspace_bytes']
+
+
+class WindowRow(ctypes.Structure):
+    """wn_iaf_window_row"""
+    _fields_ = [('b', ctypes.c_int32), ('t_origin', ctypes.c_int64), ('keep_from', ctypes.c_int64),
+                ('keep_to', ctypes.c_int64), ('out_t', ctypes.c_int64)]
 
 
 class WnConfig(ctypes.Structure):
@@ -82,6 +89,11 @@ def load():
     lib.wn_iaf_range_status.argtypes = [vp, vp, vp]
     lib.wn_iaf_range_reset.argtypes = [vp, vp, vp]
     lib.wn_iaf_range_status_since_reset.argtypes = [vp, vp, vp]
+    lib.wn_iaf_window_geometry.argtypes = [vp, c.POINTER(i64), c.POINTER(i32), c.POINTER(i32), c.POINTER(i32)]
+    lib.wn_iaf_generate_windows.argtypes = [vp, i32, i32, vp, i32, i32, c.POINTER(WindowRow), vp, i32, i64, u64,
+                                            vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.wn_iaf_windows_workspace_bytes.argtypes = [vp, i32, i32, i32]
+    lib.wn_iaf_windows_workspace_bytes.restype = sz
     lib.wn_clip_quant.argtypes = [vp, vp, i64, vp, vp, vp]
     lib.wn_ar_n_rand.argtypes = [vp]
     lib.wn_ar_state_bytes.argtypes = [vp, i32]

@@ -122,3 +122,150 @@ def to_wn_config(hparams, kind=None, n_mel=80, precision=None):
         c.mol_mix = getattr(hparams, 'mol_mix', 0) if hparams.loss_type == 'mol' else 0
         c.out_width = teacher_out_width(hparams)
     return c
+
+
+# ---- windowed IAF generation: geometry and the window planner; wn_iaf_window_geometry is the C twin ----
+def _deconv_frame_span(hparams):
+    """(frames_before, frames_after): frames left / right of the frame that holds an enc column which reach that column
+    through the deconv stack.  One layer maps the output interval [a, b] onto the inputs it reads --
+    trans conv (filter K, stride s, pL = max(K - s, 0) // 2): y[n] reads x[i] for 0 <= n + pL - i s < K,
+        i in [ceil((a + pL - K + 1) / s), floor((b + pL) / s)];
+    resize conv (pl = (K - 1) // 2): y[n] reads the repeated input at n - pl .. n - pl + K - 1,
+        i in [floor((a - pl) / s), floor((b - pl + K - 1) / s)]
+    -- and the stack is the composition, last layer first.  The stack is shift-invariant by whole frames, so the span of
+    one frame far from the edges is the span of every frame."""
+    fs = frame_shift(hparams)
+    f = 1 << 20
+    a, b = f * fs, (f + 1) * fs - 1
+    resize = bool(getattr(hparams, 'use_resize_conv', False))
+    for K, s in reversed(hparams.deconv_config):
+        if resize:
+            pl = (K - 1) // 2
+            a, b = (a - pl) // s, (b - pl + K - 1) // s
+        else:
+            pL = max(K - s, 0) // 2
+            a, b = -((-(a + pL - K + 1)) // s), (b + pL) // s
+    return f - a, b - f
+
+
+def iaf_window_geometry(hparams):
+    """Geometry of windowed IAF generation -> Namespace(reach, frames_before, frames_after, period).
+
+    reach: samples to the LEFT of t that x, mean_tot and scale_tot at t depend on (noise and conditioning).  One flow
+    reads x[t - fl .. t - 1] in its start conv (filter_length taps on shift_right(x)) and every layer of dilation d
+    widens that by (fl - 1) d, so its mean and scale at t read x[t - r_k .. t - 1], r_k = fl + (fl - 1) sum_i d_i; its
+    output x[t] = x[t] scale[t] + mean[t] reads x[t - r_k .. t].  Flows chain on x, so the reaches add and nothing else
+    is added: reach = sum_k r_k (12 288 for the shipped configs).
+    frames_before / frames_after: see _deconv_frame_span.  period: the centre crop depends on F modulo this."""
+    from math import gcd
+    fl, ns = int(hparams.filter_length), int(hparams.num_stages)
+    reach = 0
+    for n in hparams.num_iaf_layers:
+        reach += fl + (fl - 1) * sum(2 ** (i % ns) for i in range(n))
+    fb, fa = _deconv_frame_span(hparams)
+    md = 2 ** (ns - 1)
+    return Namespace(reach=reach, frames_before=fb, frames_after=fa, period=md // gcd(frame_shift(hparams), md))
+
+
+def iaf_window_margins(hparams, Fw):
+    """(T_w, c0_w, lo, hi) of a row of Fw frames: its length and centre crop, and the local range [lo, hi) a row in the
+    MIDDLE of an utterance may keep.  Local sample t reads the conditioning of local samples t - reach .. t, i.e. enc
+    columns t - reach + c0_w .. t + c0_w of the row; a column is the utterance's own when the frames_before frames left
+    and the frames_after frames right of its frame lie inside the row."""
+    g = iaf_window_geometry(hparams)
+    fs = frame_shift(hparams)
+    Tw = iaf_length(hparams, Fw)
+    c0 = (Fw * fs - Tw) // 2
+    lo = g.reach + max(0, g.frames_before * fs - c0)
+    hi = min(Tw, (Fw - g.frames_after) * fs - c0)
+    return Tw, c0, lo, hi
+
+
+def iaf_default_window_frames(hparams):
+    """4.8 s windows for the shipped geometry (the one-shot's flagship shape), at least four times the recomputed part"""
+    g = iaf_window_geometry(hparams)
+    fs = frame_shift(hparams)
+    return max(384, 4 * (-(-g.reach // fs) + g.frames_before + g.frames_after + 1))
+
+
+def iaf_window_align(hparams):
+    """(al, q): rows start on multiples of al frames (their first sample is a multiple of 4, the granularity of the noise
+    counter) and frame counts are chosen modulo q = lcm(period, al)"""
+    from math import gcd
+    al = 4 // gcd(frame_shift(hparams), 4)
+    p = iaf_window_geometry(hparams).period
+    return al, p * al // gcd(p, al)
+
+
+def iaf_window_grid(hparams, window_frames, residue):
+    """The window grid for frame counts = residue (mod q): (Fw, c0_w, lo, S) with Fw the largest such count <=
+    window_frames that leaves a stride S >= 1 (the smallest that does, if window_frames is too small for the geometry);
+    row i of the grid starts at frame i S and keeps local [lo, lo + S frame_shift)."""
+    g = iaf_window_geometry(hparams)
+    fs = frame_shift(hparams)
+    al, q = iaf_window_align(hparams)
+    md = 2 ** (hparams.num_stages - 1)
+
+    def stride(Fw):
+        Tw, c0, lo, hi = iaf_window_margins(hparams, Fw)
+        return c0, lo, (((hi - lo) // fs) // al * al if hi > lo else 0)
+    Fw = int(window_frames) - (int(window_frames) - residue) % q
+    if Fw < 1 or stride(Fw)[2] < 1:
+        need = -(-(g.reach + (g.frames_before + g.frames_after + al + 1) * fs + md) // fs)
+        Fw = need + (residue - need) % q
+    c0, lo, S = stride(Fw)
+    if S < 1:
+        raise ValueError('iaf_window_grid: no window of {} frames fits this geometry'.format(Fw))
+    return Fw, c0, lo, S
+
+
+def iaf_plan_windows(hparams, F, window_frames=None, crop='centre'):
+    """Plan utterance of F frames as rows of one frame count -> (Fw, [(f0, t_origin, keep_from, keep_to, out_t), ...]).
+
+    Every row is an ordinary call on mel[f0 : f0 + Fw] (T_w = iaf_length(Fw), its own centre crop c0_w); its local sample t
+    is sample t_origin + t of the utterance, it may keep local [keep_from, keep_to), and those go to out_t.. of the output.
+    crop='centre': the output is iaf_generate's (T = iaf_length(F), conditioning centre-cropped); Fw = F (mod period).
+    crop='left': T = floor(F frame_shift / max_dil) max_dil samples with the conditioning cropped on the right only
+    (sample t reads enc column t); Fw = 0 (mod period); the same as 'centre' whenever F % period == 0.
+    Fw is the largest such count <= window_frames (the smallest that leaves a row something to keep, if that is larger).
+
+    Rows sit on a grid that does not depend on F: row i starts at frame i S and keeps local [lo, lo + S frame_shift)
+    (row 0 from 0), with [lo, hi) of iaf_window_margins and S = (hi - lo) // frame_shift.  Grid rows are those that end
+    before frame F; the TAIL row is placed to end at frame F and keeps what the grid rows left, up to T.  So a row that
+    is certain to be a grid row (more than i S + Fw frames known) can run before F is known -- the stream does that."""
+    if crop not in ('centre', 'left'):
+        raise ValueError("crop must be 'centre' or 'left', got {!r}".format(crop))
+    F = int(F)
+    if F < 1:
+        raise ValueError('iaf_plan_windows: F must be >= 1')
+    fs = frame_shift(hparams)
+    wf = int(window_frames) if window_frames is not None else iaf_default_window_frames(hparams)
+    if wf < 1:
+        raise ValueError('iaf_plan_windows: window_frames must be >= 1')
+    q = iaf_window_align(hparams)[1]
+    T = iaf_length(hparams, F)
+    # one row: the one-shot itself ('left': only where the two crops coincide)
+    if F <= wf and (crop == 'centre' or F % q == 0):
+        return F, [(0, 0, 0, T, 0)]
+    Fw, c0, lo, S = iaf_window_grid(hparams, min(wf, F), F % q if crop == 'centre' else 0)
+    if F <= Fw:
+        if F == Fw:
+            return F, [(0, 0, 0, T, 0)]
+        raise ValueError("iaf_plan_windows: crop='left' plans an utterance of {} frames (not a multiple of {}) as windows "
+                         "of {} frames and needs at least that many".format(F, q, Fw))
+    if ((F - Fw) * fs) % 4:
+        raise ValueError('iaf_plan_windows: the tail window would start at sample {} (frame_shift {}): the device noise '
+                         'is drawn four samples per counter'.format((F - Fw) * fs, fs))
+    c0g = c0 if crop == 'centre' else 0
+    rows, done, f0 = [], 0, 0
+    while f0 + Fw < F:                                     # grid rows
+        to = f0 * fs + c0 - c0g
+        kf = done - to
+        kt = lo + S * fs
+        rows.append((f0, to, kf, kt, done))
+        done = to + kt
+        f0 += S
+    f0 = F - Fw                                            # tail row: ends at frame F
+    to = f0 * fs + c0 - c0g
+    rows.append((f0, to, done - to, T - to, done))
+    return Fw, rows

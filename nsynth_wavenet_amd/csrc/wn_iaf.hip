@@ -71,6 +71,31 @@ __device__ inline void iaf_noise_body(float* __restrict__ x0, float* __restrict_
     *reinterpret_cast<f4*>(x + (size_t)b * XR + IAF_XP + i4 * 4) = (f4){v[0], v[1], v[2], v[3]};
 }
 
+// The draws of iaf_noise_body for Philox counter (i4, b) -- samples 4 i4 .. 4 i4 + 3 of utterance b -- for the window prologue,
+// whose counter is not the thread's index.  A copy, expression for expression: iaf_noise_body itself stays as it is, so the
+// one-shot's prologue compiles to the same instructions as before (tests/test_gpu_iaf_windows.py holds the two to the same bits).
+__device__ inline void iaf_noise_draw(int64_t i4, int b, uint64_t seed, int gauss, float (&v)[4]) {
+    uint32_t c[4] = {(uint32_t)i4, (uint32_t)(i4 >> 32), (uint32_t)b, 0x49414630u};
+    wn_philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    if (!gauss) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float u01 = (float)(c[e] >> 8) * (1.0f / 16777216.0f);
+            const float u = u01 * (1.f - 2e-5f) + 1e-5f;
+            v[e] = logf(u) - logf(1.f - u);
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; e += 2) {
+            const float u1 = ((float)(c[e] >> 8) + 1.0f) * (1.0f / 16777216.0f);   // (0,1]
+            const float u2 = (float)(c[e + 1] >> 8) * (1.0f / 16777216.0f);
+            const float rr = sqrtf(-2.f * logf(u1));
+            v[e] = rr * cosf(6.283185307179586f * u2);
+            v[e + 1] = rr * sinf(6.283185307179586f * u2);
+        }
+    }
+}
+
 __device__ inline void iaf_copy_noise_body(const float* __restrict__ noise, float* __restrict__ x, int64_t T, int XR,
                                            int bx, int b) {
     const int64_t i4 = (int64_t)bx * blockDim.x + threadIdx.x;
@@ -741,6 +766,119 @@ __global__ void clip_quant_kernel(const float* __restrict__ x, int64_t n, int Q,
     if (idx) idx[i] = qi;
 }
 
+// ---------------- windowed generation (wn_iaf_generate_windows) ----------------
+// Row r of a window call is an ordinary row of T samples whose local sample t is sample t_origin + t of utterance b.
+// Prologue: iaf_prologue_kernel's two jobs with the noise taken at ABSOLUTE positions -- Philox counter (t_origin / 4 + i4, b),
+// the one-shot's counter words (t_origin is a multiple of 4), or the caller's noise_abs [B_out][T_out] at t_origin + t, 0
+// outside it.  Both forms also fill the x0 rows, which the final kernel reads.
+struct WinPrologueArgs {
+    PrologueArgs P;
+    const wn_iaf_window_row* rows;
+    const float* noise_abs;
+    int64_t T_out;
+};
+__global__ void iaf_window_prologue_kernel(const WinPrologueArgs W) {
+    const PrologueArgs& A = W.P;
+    const int bid = blockIdx.x;
+    if (bid < A.npad) {
+        const int bx = bid % A.pgx, by = (bid / A.pgx) % A.pgy, bz = bid / (A.pgx * A.pgy);
+        zero_pads_body(A.lA, A.lB, A.rs, A.pad, A.rows, A.x, A.xrs, A.xpad, A.xrows, A.status, A.dl_rj, bx, by, bz, A.pgy);
+        return;
+    }
+    const int nb = bid - A.npad, bx = nb % A.ngx, r = nb / A.ngx;
+    const int64_t i4 = (int64_t)bx * blockDim.x + threadIdx.x;
+    if (i4 * 4 >= A.T) return;
+    const int b = W.rows[r].b;
+    const int64_t g = W.rows[r].t_origin + i4 * 4;           // absolute position of the thread's first sample
+    float v[4];
+    if (!W.noise_abs) {
+        iaf_noise_draw(g >> 2, b, A.seed, A.gauss, v);
+    } else {
+        const float* np = W.noise_abs + (size_t)b * W.T_out;
+        if (g >= 0 && g + 4 <= W.T_out && ((W.T_out | g) & 3) == 0) {      // 16-byte aligned and inside
+            const f4 w = *reinterpret_cast<const f4*>(np + g);
+            v[0] = w[0]; v[1] = w[1]; v[2] = w[2]; v[3] = w[3];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = (g + e >= 0 && g + e < W.T_out) ? np[g + e] : 0.f;
+        }
+    }
+    *reinterpret_cast<f4*>(A.x0g + (size_t)r * A.T + i4 * 4) = (f4){v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<f4*>(A.x + (size_t)r * A.XR + IAF_XP + i4 * 4) = (f4){v[0], v[1], v[2], v[3]};
+}
+
+// Final kernel: iaf_final_kernel's arithmetic over the KEPT columns [keep_from, keep_to) of every row, stored at
+// out[b][out_t + (t - keep_from)].  A thread owns one 16-byte-aligned quad of the OUTPUT row: whole quads leave as one
+// 16-byte store per output (vec: every output pointer and T_out allow it), the ragged first / last quad element by element;
+// the inputs are read 16 bytes at a time where the row's source columns happen to be aligned like its destination.
+struct WinFinalArgs {
+    const wn_iaf_window_row* rows;
+    const float *x0, *Mt, *St;                               // [R][T]
+    int64_t T, T_out;
+    int Q, mu, vec;
+    float *wav, *xraw, *mean_tot, *scale_tot, *rand_out;     // [B_out][T_out]
+    int* idx;
+    unsigned* status;
+};
+__global__ void iaf_window_final_kernel(const WinFinalArgs A) {
+    const int r = blockIdx.y;
+    const wn_iaf_window_row row = A.rows[r];
+    const int64_t n = row.keep_to - row.keep_from;
+    const int64_t e0 = (int64_t)row.b * A.T_out + row.out_t;                 // output element of the first kept column
+    const int64_t k0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4 - (e0 & 3);   // first kept column of this quad
+    const bool bad = *A.status != 0u;                                        // as iaf_final_kernel: NaN, never saturated audio
+    if (bad && r == 0 && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(A.status + 1, *A.status);
+    if (k0 >= n) return;
+    const int64_t src = (int64_t)r * A.T + row.keep_from + k0, dst = e0 + k0;
+    const bool full = k0 >= 0 && k0 + 4 <= n;
+    float x0v[4], mv[4], sv[4];
+    if (full && (src & 3) == 0) {
+        const f4 a = *reinterpret_cast<const f4*>(A.x0 + src), m = *reinterpret_cast<const f4*>(A.Mt + src),
+                 s = *reinterpret_cast<const f4*>(A.St + src);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { x0v[e] = a[e]; mv[e] = m[e]; sv[e] = s[e]; }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const bool in = k0 + e >= 0 && k0 + e < n;
+            x0v[e] = in ? A.x0[src + e] : 0.f;
+            mv[e] = in ? A.Mt[src + e] : 0.f;
+            sv[e] = in ? A.St[src + e] : 0.f;
+        }
+    }
+    f4 w, y, m, s, x0o;
+    int q4[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float se = fminf(sv[e], EXP_7);                      // parallel_wavenet.py:327
+        float me = mv[e];
+        float ye = x0v[e] * se + me;                         // :330
+        float we; int qi;
+        clip_quant_one(ye, A.Q, A.mu, we, qi);
+        if (bad) { we = ye = me = se = __builtin_nanf(""); qi = 0; }
+        w[e] = we; y[e] = ye; m[e] = me; s[e] = se; q4[e] = qi; x0o[e] = x0v[e];
+    }
+    if (full && A.vec) {
+        *reinterpret_cast<f4*>(A.wav + dst) = w;
+        if (A.idx) *reinterpret_cast<int4*>(A.idx + dst) = make_int4(q4[0], q4[1], q4[2], q4[3]);
+        if (A.xraw) *reinterpret_cast<f4*>(A.xraw + dst) = y;
+        if (A.mean_tot) *reinterpret_cast<f4*>(A.mean_tot + dst) = m;
+        if (A.scale_tot) *reinterpret_cast<f4*>(A.scale_tot + dst) = s;
+        if (A.rand_out) *reinterpret_cast<f4*>(A.rand_out + dst) = x0o;
+        return;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (k0 + e < 0 || k0 + e >= n) continue;
+        A.wav[dst + e] = w[e];
+        if (A.idx) A.idx[dst + e] = q4[e];
+        if (A.xraw) A.xraw[dst + e] = y[e];
+        if (A.mean_tot) A.mean_tot[dst + e] = m[e];
+        if (A.scale_tot) A.scale_tot[dst + e] = s[e];
+        if (A.rand_out) A.rand_out[dst + e] = x0o[e];
+    }
+}
+
 struct IafLayout {
     int64_t T, TE, RS;
     int XR, c0;
@@ -995,9 +1133,8 @@ struct IafCall {
 };
 
 // prologue: zero left pads + the flow input (drawn on the device, or the caller's noise), one launch
-void iaf_prologue(const IafCall& c, const float* noise, float* x0g, uint64_t seed) {
+void iaf_prologue_args(const IafCall& c, const float* noise, float* x0g, uint64_t seed, PrologueArgs& A) {
     const IafLayout& L = c.L;
-    PrologueArgs A{};
     // G4 layout (f16x3) and the Q4 rows of the hoisted fp32 form: 16 interleaved group rows per batch element, each
     // 4*(LP+T) words; fused fp32 form and the generic student: planar rows, one per channel
     const bool rows16 = c.f16x3 || c.hoist;
@@ -1012,6 +1149,10 @@ void iaf_prologue(const IafCall& c, const float* noise, float* x0g, uint64_t see
     A.npad = A.pgx * A.pgy * 3;
     A.T = L.T; A.XR = L.XR; A.seed = seed; A.gauss = c.h->cfg.loss_type == WN_LOSS_GAUSS ? 1 : 0;
     A.ngx = (int)((L.T / 4 + 255) / 256);
+}
+void iaf_prologue(const IafCall& c, const float* noise, float* x0g, uint64_t seed) {
+    PrologueArgs A{};
+    iaf_prologue_args(c, noise, x0g, seed, A);
     hipLaunchKernelGGL(iaf_prologue_kernel, dim3((unsigned)(A.npad + A.ngx * c.B)), dim3(256), 0, c.st, A);
 }
 
@@ -1320,6 +1461,191 @@ extern "C" int wn_iaf_generate_form(wn_handle* h, int form, const float* mel, in
                            Q, cfg.use_mu_law, wav, idx, x_raw, mean_tot, scale_tot, c.status);
         if (rand_out && rand_out != x0)
             WN_HIP(h, hipMemcpyAsync(rand_out, x0, nn * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+    }
+    if (int rc = c.part(-1)) return rc;
+    if (c.parts_on) {
+        std::lock_guard<std::mutex> g(h->list_mu);
+        ++h->part_calls;
+    }
+    WN_HIP(h, hipGetLastError());
+    return WN_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Windowed generation: R rows of Fw frames run through the skeleton above as a batch of R utterances; what
+// differs is the call's front (noise at absolute positions) and back (only the kept columns leave, at their place in the
+// utterance).  nsynth_wavenet_amd/config.py: iaf_window_geometry is the twin of wn_iaf_window_geometry.
+extern "C" int wn_iaf_window_geometry(const wn_handle* h, int64_t* reach, int* frames_before, int* frames_after, int* period) {
+    if (!h) return wn_fail(nullptr, WN_EINVAL, "wn_iaf_window_geometry: null handle");
+    const wn_config& c = h->cfg;
+    if (c.kind != WN_KIND_STUDENT)
+        return wn_fail(h, WN_EINVAL, "wn_iaf_window_geometry: handle is not a ParallelWavenet student");
+    // a flow's mean and scale at t read x[t - r .. t - 1], r = fl + (fl - 1) sum of its dilations; the flows chain on x
+    int64_t rc = 0;
+    for (int k = 0; k < c.n_flows; ++k) {
+        rc += c.filter_length;
+        for (int i = 0; i < c.iaf_layers[k]; ++i) rc += (int64_t)(c.filter_length - 1) << (i % c.num_stages);
+    }
+    // the input interval one upsampler layer reads for an output interval, last layer first, from one frame far from the edges
+    auto fdiv = [](int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
+    const int64_t f = 1 << 20;
+    int64_t a = f * h->frame_shift, b = (f + 1) * h->frame_shift - 1;
+    for (int j = c.n_deconv - 1; j >= 0; --j) {
+        const int64_t K = c.deconv_filter[j], s = c.deconv_stride[j];
+        if (c.use_resize_conv) {
+            const int64_t pl = (K - 1) / 2;
+            a = fdiv(a - pl, s);
+            b = fdiv(b - pl + K - 1, s);
+        } else {
+            const int64_t pL = std::max<int64_t>(K - s, 0) / 2;
+            a = -fdiv(-(a + pL - K + 1), s);
+            b = fdiv(b + pL, s);
+        }
+    }
+    const int64_t md = (int64_t)1 << (c.num_stages - 1);
+    int64_t x = h->frame_shift, y = md;
+    while (y) { const int64_t t = x % y; x = y; y = t; }     // x = gcd(frame_shift, max dilation)
+    if (reach) *reach = rc;
+    if (frames_before) *frames_before = (int)(f - a);
+    if (frames_after) *frames_after = (int)(b - f);
+    if (period) *period = (int)(md / x);
+    return WN_OK;
+}
+
+static size_t wn_iaf_windows_table_bytes(int R) { return align_up((size_t)R * sizeof(wn_iaf_window_row), 256); }
+
+extern "C" size_t wn_iaf_windows_workspace_bytes(const wn_handle* h, int R, int Fw, int form) {
+    if (!h || h->cfg.kind != WN_KIND_STUDENT || R < 1 || Fw < 1 || form < WN_FORM_DEFAULT || form > WN_FORM_F16X3_FUSED) return 0;
+    return align_up(wn_iaf_workspace_bytes(h, R, Fw, form), 256) + wn_iaf_windows_table_bytes(R);
+}
+
+extern "C" int wn_iaf_generate_windows(wn_handle* h, int form, int form_rows, const float* mel, int R, int Fw,
+                                       const wn_iaf_window_row* rows_host, const float* noise_abs, int B_out, int64_t T_out,
+                                       uint64_t seed, float* wav, int32_t* idx, float* x_raw, float* mean_tot,
+                                       float* scale_tot, float* rand_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!h) return wn_fail(nullptr, WN_EINVAL, "wn_iaf_generate_windows: null handle");
+    if (form < WN_FORM_DEFAULT || form > WN_FORM_F16X3_FUSED)
+        return wn_fail(h, WN_EINVAL, "wn_iaf_generate_windows: unknown form %d", form);
+    if (!h->finalized) return wn_fail(h, WN_ESTATE, "wn_iaf_generate_windows: call wn_finalize first");
+    if (h->cfg.kind != WN_KIND_STUDENT)
+        return wn_fail(h, WN_EINVAL, "wn_iaf_generate_windows: handle is not a ParallelWavenet student");
+    if (R < 1 || Fw < 1) return wn_fail(h, WN_EINVAL, "wn_iaf_generate_windows: R and Fw must be >= 1");
+    if (R > 65535) return wn_fail(h, WN_EINVAL, "wn_iaf_generate_windows: at most 65535 rows per call, got %d", R);
+    if (form_rows < 0) return wn_fail(h, WN_EINVAL, "wn_iaf_generate_windows: form_rows must be >= 0, got %d", form_rows);
+    if (B_out < 1 || T_out < 1) return wn_fail(h, WN_EINVAL, "wn_iaf_generate_windows: B_out and T_out must be >= 1");
+    const WnWork work(h);
+    IafCall c{};
+    c.h = h;
+    c.prof_on = h->prof_on;
+    c.parts_on = h->parts_on;
+    c.pmask = c.parts_on ? h->parts_mask : 0xf;
+    c.no_pair = getenv("WN_NO_PAIR") != nullptr;
+    c.no_headfuse = getenv("WN_NO_HEADFUSE") != nullptr;
+    c.L = iaf_layout(h, R, Fw, form);
+    const IafLayout& L = c.L;
+    if (L.T == 0) return wn_fail(h, WN_EINVAL, "wn_iaf_generate_windows: a window of %d frames is shorter than one max-dilation block", Fw);
+    if (!mel || !wav || !ws || !rows_host) return wn_fail(h, WN_EINVAL, "wn_iaf_generate_windows: null mel/wav/workspace/rows");
+    if (L.TE > 2000000)   // 32-bit buffer offsets inside one row (960 * TE bytes): the limit is the WINDOW's, not the utterance's
+        return wn_fail(h, WN_EINVAL, "wn_iaf_generate_windows: %lld samples per window exceeds the 2,000,000 "
+                       "(125 s) limit of the 32-bit row offsets; plan shorter windows", (long long)L.TE);
+    const size_t tab_off = align_up(L.total, 256), tab_bytes = (size_t)R * sizeof(wn_iaf_window_row);
+    if (ws_bytes < tab_off + tab_bytes)
+        return wn_fail(h, WN_ENOMEM, "wn_iaf_generate_windows: workspace %zu < %zu bytes", ws_bytes, tab_off + tab_bytes);
+    if ((int64_t)R * L.T / 64 > 0x7fffffff) return wn_fail(h, WN_EINVAL, "wn_iaf_generate_windows: batch too large");
+    // the row table: every refusal by name, then one writer per output element
+    int64_t max_keep = 0;
+    std::vector<std::pair<int64_t, int64_t>> spans((size_t)R);
+    for (int r = 0; r < R; ++r) {
+        const wn_iaf_window_row& w = rows_host[r];
+        if (w.b < 0 || w.b >= B_out)
+            return wn_fail(h, WN_EINVAL, "wn_iaf_generate_windows: row %d: b = %d outside [0, B_out = %d)", r, w.b, B_out);
+        if (w.t_origin < 0 || (w.t_origin & 3))
+            return wn_fail(h, WN_EINVAL, "wn_iaf_generate_windows: row %d: t_origin = %lld is not a non-negative multiple of 4 "
+                           "(unaligned t_origin: the noise counter covers four samples)", r, (long long)w.t_origin);
+        if (w.keep_from < 0 || w.keep_to < w.keep_from || w.keep_to > L.T)
+            return wn_fail(h, WN_EINVAL, "wn_iaf_generate_windows: row %d: kept range [%lld, %lld) outside [0, T_w = %lld)", r,
+                           (long long)w.keep_from, (long long)w.keep_to, (long long)L.T);
+        const int64_t n = w.keep_to - w.keep_from;
+        if (w.out_t < 0 || w.out_t + n > T_out)
+            return wn_fail(h, WN_EINVAL, "wn_iaf_generate_windows: row %d: out_t = %lld plus %lld kept samples past T_out = %lld",
+                           r, (long long)w.out_t, (long long)n, (long long)T_out);
+        spans[r] = {(int64_t)w.b * T_out + w.out_t, n};
+        max_keep = std::max(max_keep, n);
+    }
+    std::sort(spans.begin(), spans.end());
+    for (int r = 0; r + 1 < R; ++r)
+        if (spans[r].second > 0 && spans[r].first + spans[r].second > spans[r + 1].first && spans[r + 1].second > 0)
+            return wn_fail(h, WN_EINVAL, "wn_iaf_generate_windows: overlapping kept ranges: two rows write output element %lld",
+                           (long long)spans[r + 1].first);
+    const wn_config& cfg = h->cfg;
+    char* base = reinterpret_cast<char*>(ws);
+    auto at = [base](size_t off) { return reinterpret_cast<float*>(base + off); };
+    c.B = R; c.F = Fw; c.mel = mel;
+    c.st = reinterpret_cast<hipStream_t>(stream);
+    c.enc = at(L.enc); c.lA = at(L.lA); c.lB = at(L.lB); c.Mt = at(L.M); c.St = at(L.S); c.Cc = at(L.C);
+    c.xbuf0 = c.x = at(L.x);
+    c.status = reinterpret_cast<unsigned*>(base + L.status);
+    c.scratch = base + L.scratch;
+    c.prec = h->generic_student ? WN_PREC_F32 : wn_form_precision(h, form);
+    c.f16x3 = c.prec == WN_PREC_F16X3;
+    c.hoist = L.form == WN_COND_HOISTED;
+    // groups or per-layer launches: the one-shot's size policy evaluated for form_rows rows (0: the R of this call).  A caller
+    // that wants a row's bits not to depend on how many rows share its call names a fixed count (a stream runs windows as
+    // they become possible, Engine.iaf_generate_long eight at a time; both must produce the same audio)
+    c.use_groups = c.f16x3 && wn_iaf_use_groups(h, form_rows ? form_rows : R, L.T, L.form);
+    c.tiles_per_row = (int)(L.T / 64);
+    c.ntiles = R * c.tiles_per_row;
+    c.grid = std::min(c.ntiles, h->num_cu);
+    c.rb_floats = (size_t)(L.T / 16) * 1024;
+    const IafRunner run_flow = iaf_runner(c);
+
+    // the table goes up from a copy the handle keeps (the upload is asynchronous), as wn_iaf_set_weights keeps its tables
+    wn_iaf_window_row* d_rows = reinterpret_cast<wn_iaf_window_row*>(base + tab_off);
+    {
+        auto keep = std::make_shared<std::vector<wn_iaf_window_row>>(rows_host, rows_host + R);
+        WN_HIP(h, hipMemcpyAsync(d_rows, keep->data(), tab_bytes, hipMemcpyHostToDevice, c.st));
+        std::lock_guard<std::mutex> g(h->list_mu);
+        h->window_tables[h->window_tables_next++ % h->window_tables.size()] = keep;
+    }
+    if (int rc = c.part(0)) return rc;
+    float* x0g = at(L.x0);
+    {
+        WinPrologueArgs W{};
+        iaf_prologue_args(c, nullptr, x0g, seed, W.P);
+        W.rows = d_rows; W.noise_abs = noise_abs; W.T_out = T_out;
+        hipLaunchKernelGGL(iaf_window_prologue_kernel, dim3((unsigned)(W.P.npad + W.P.ngx * R)), dim3(256), 0, c.st, W);
+    }
+    if (cfg.share_deconv)
+        if (int rc = iaf_upsample_cond(c, 0, 0, h->cond_rows, c.blob_u(c.use_groups ? h->order_all_off : h->order_id_off),
+                                       c.use_groups ? h->n_nat_all : h->cond_rows))
+            return rc;
+    for (int k = 0; k < cfg.n_flows; ++k) {
+        const IafFlowPack* fp = h->generic_student ? nullptr : &h->flows[k];
+        const int rb0 = fp ? fp->rb_base : 0, RB = fp ? (int)fp->layers.size() + 1 : 0;
+        if (!cfg.share_deconv)
+            if (int rc = iaf_upsample_cond(c, fp ? fp->deconv_stack : h->flows_x[k].deconv_stack, rb0, RB,
+                                           c.use_groups ? c.blob_u(h->order_flow_off) + rb0 : c.blob_u(h->order_id_off),
+                                           c.use_groups ? h->n_nat_flow[k] : RB))
+                return rc;
+        if (int rc = c.part(3)) return rc;
+        if (!(c.pmask & 8)) continue;
+        if (int rc = run_flow(c, k, c.Cc + (cfg.share_deconv ? (size_t)rb0 * c.rb_floats : 0))) return rc;
+    }
+    if (int rc = c.part(0)) return rc;
+    if (max_keep > 0) {
+        WinFinalArgs A{};
+        A.rows = d_rows; A.x0 = x0g; A.Mt = c.Mt; A.St = c.St; A.T = L.T; A.T_out = T_out;
+        A.Q = cfg.use_mu_law ? 256 : 65536; A.mu = cfg.use_mu_law;
+        A.wav = wav; A.idx = idx; A.xraw = x_raw; A.mean_tot = mean_tot; A.scale_tot = scale_tot; A.rand_out = rand_out;
+        A.status = c.status;
+        uintptr_t bits = (uintptr_t)(T_out & 3);
+        for (const void* p : {(const void*)wav, (const void*)idx, (const void*)x_raw, (const void*)mean_tot,
+                              (const void*)scale_tot, (const void*)rand_out})
+            bits |= reinterpret_cast<uintptr_t>(p) & 15;
+        A.vec = bits == 0;
+        // a quad per thread; the first quad of a row may start up to three elements before its first kept column
+        const unsigned gx = (unsigned)(((max_keep + 3) / 4 + 1 + 255) / 256);
+        hipLaunchKernelGGL(iaf_window_final_kernel, dim3(gx, (unsigned)R), dim3(256), 0, c.st, A);
     }
     if (int rc = c.part(-1)) return rc;
     if (c.parts_on) {

@@ -1,6 +1,8 @@
 // Internal declarations shared by the translation units of libwnhip.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -179,6 +181,9 @@ struct wn_handle {
     TeacherPack teacher;
     IafTrainPack iaf_train;
     std::shared_ptr<void> repack_keep;        // host tables the last wn_iaf_set_weights uploaded (wn_iaf_repack.hip)
+    // host copies of the row tables the last 64 wn_iaf_generate_windows calls uploaded (asynchronous uploads; under list_mu)
+    std::array<std::shared_ptr<void>, 64> window_tables;
+    size_t window_tables_next = 0;
     // hoisted conditioning (wn_iaf_c.hip): word offsets of the 8-K-step cond fragment arrays of
     // every layer and head ("row block"), flow after flow, stored as uint32 inside the blob
     size_t cond_tab_off = 0;

@@ -205,6 +205,107 @@ class Engine(object):
                 out[k] = v
         return out
 
+    # ---- windowed IAF generation ----
+    ONE_SHOT_MAX_SAMPLES = 2000000         # wn_iaf_generate refuses more upsampled samples per utterance (32-bit row offsets)
+
+    def iaf_needs_windows(self, num_frames):
+        """True when iaf_generate refuses num_frames for its length and iaf_generate_long has to take the call."""
+        return int(num_frames) * self.frame_shift > self.ONE_SHOT_MAX_SAMPLES
+
+    def iaf_window_geometry(self):
+        """wn_iaf_window_geometry: (reach, frames_before, frames_after, period) as the library derives them;
+        config.iaf_window_geometry is the Python twin."""
+        r, fb, fa, p = ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        self._check(self.lib.wn_iaf_window_geometry(self._h, ctypes.byref(r), ctypes.byref(fb), ctypes.byref(fa),
+                                                    ctypes.byref(p)))
+        return int(r.value), int(fb.value), int(fa.value), int(p.value)
+
+    def _window_outputs(self, B, T, want):
+        new = lambda dt=torch.float32: torch.empty((B, T), dtype=dt, device=self.device)
+        return {'wav': new(), 'idx': new(torch.int32) if 'idx' in want else None, 'x': new() if 'x' in want else None,
+                'mean_tot': new() if 'mean_tot' in want else None, 'scale_tot': new() if 'scale_tot' in want else None,
+                'rand_input': new() if 'rand_input' in want else None}
+
+    def iaf_generate_windows(self, mel_rows, rows, out, noise_abs=None, seed=0, form=None, form_rows=1, check_range=True,
+                             ws_rows=None):
+        """One wn_iaf_generate_windows call.  mel_rows [R,Fw,n_mel] on the device; rows: R tuples (b, t_origin, keep_from,
+        keep_to, out_t); out: dict of [B_out,T_out] device tensors wav (required), idx, x, mean_tot, scale_tot, rand_input
+        (or None) that receive the kept samples; noise_abs [B_out,T_out] or None (drawn from `seed` at absolute positions).
+        check_range as in iaf_generate: a call that left the fp16 range is re-run on the fp32 form.  ws_rows: size the
+        workspace for that many rows (a run of calls on one buffer)."""
+        R, Fw = int(mel_rows.shape[0]), int(mel_rows.shape[1])
+        if mel_rows.dim() != 3 or int(mel_rows.shape[2]) != self.n_mel or not mel_rows.is_contiguous():
+            raise ValueError('mel_rows must be contiguous [rows, frames, {}], got {}'.format(self.n_mel, tuple(mel_rows.shape)))
+        if len(rows) != R:
+            raise ValueError('{} row descriptors for {} mel rows'.format(len(rows), R))
+        wav = out['wav']
+        B_out, T_out = int(wav.shape[0]), int(wav.shape[1])
+        for k, v in out.items():
+            if v is not None and (tuple(v.shape) != (B_out, T_out) or not v.is_contiguous()):
+                raise ValueError('output {} must be contiguous [{}, {}]'.format(k, B_out, T_out))
+        if noise_abs is not None and tuple(noise_abs.shape) != (B_out, T_out):
+            raise ValueError('noise must be [{}, {}], got {}'.format(B_out, T_out, tuple(noise_abs.shape)))
+        table = (_lib.WindowRow * R)(*[_lib.WindowRow(*[int(v) for v in r]) for r in rows])
+        form = _lib.FORM_DEFAULT if form is None else form
+        with torch.cuda.device(self.device):
+            ws = self._workspace(self.lib.wn_iaf_windows_workspace_bytes(self._h, max(R, int(ws_rows or 0)), Fw, form))
+
+            def run(f):
+                self._check(self.lib.wn_iaf_generate_windows(
+                    self._h, f, int(form_rows), _ptr(mel_rows), R, Fw, table, _ptr(noise_abs), B_out, T_out,
+                    ctypes.c_uint64(int(seed)), _ptr(wav), _ptr(out.get('idx')), _ptr(out.get('x')), _ptr(out.get('mean_tot')),
+                    _ptr(out.get('scale_tot')), _ptr(out.get('rand_input')), _ptr(ws), ws.numel(), self._stream()))
+            run(form)
+            self._last_ws = ws
+            if check_range and not self.precision.startswith('f32') and form != _lib.FORM_F32:
+                rc = self.lib.wn_iaf_range_status(self._h, _ptr(ws), self._stream())
+                if rc == _lib.WN_ERANGE:
+                    self.range_fallbacks += 1
+                    run(_lib.FORM_F32)
+                    self._check(self.lib.wn_iaf_range_reset(self._h, _ptr(ws), self._stream()))
+                else:
+                    self._check(rc)
+
+    def iaf_generate_long(self, mel, noise=None, seed=0, want=('wav',), window_frames=None, rows_per_call=8, crop='centre',
+                          check_range=True, form=None, out=None):
+        """iaf_generate for any number of frames: the utterance is planned as windows of one frame count
+        (config.iaf_plan_windows), each recomputing the `reach` samples of causal context in front of what it keeps, and
+        the windows run as batches of rows_per_call rows on one workspace, writing into one output set.  Same keys and
+        shapes as iaf_generate.  A plan of ONE row (F <= window_frames; default 384 frames for the shipped configs) returns
+        iaf_generate's bits; otherwise x, mean_tot and scale_tot agree with it to the accuracy two calls of different
+        length agree, and the device noise is the one-shot's noise bit for bit.
+        crop='left' crops the conditioning on the right only (sample t reads upsampled column t) -- what a stream produces;
+        it coincides with the one-shot's centred crop whenever F % period == 0.  form: a _lib.FORM_* (default: the engine's).
+        out: preallocated [B,T] device tensors under iaf_generate_windows' names ('wav' at least), to be written instead of
+        new ones."""
+        mel = self._dev(mel)
+        if mel.dim() != 3 or mel.shape[2] != self.n_mel:
+            raise ValueError('mel must be [batch, frames, {}], got {}'.format(self.n_mel, tuple(mel.shape)))
+        if int(rows_per_call) < 1:
+            raise ValueError('rows_per_call must be >= 1')
+        B, F = int(mel.shape[0]), int(mel.shape[1])
+        T = self.iaf_length(F)
+        noise = self._dev(noise)
+        if noise is not None and tuple(noise.shape) != (B, T):
+            raise ValueError('noise must be [{}, {}], got {}'.format(B, T, tuple(noise.shape)))
+        out = dict(out) if out is not None else self._window_outputs(B, T, want)
+        if T > 0:
+            Fw, plan = cfg.iaf_plan_windows(self.hp, F, window_frames, crop)
+            rows = [(b, f0) + (to, kf, kt, ot) for (f0, to, kf, kt, ot) in plan for b in range(B)]
+            # a single-row plan is the one-shot: its launch form is chosen for the whole batch, as iaf_generate chooses it
+            form_rows = B if len(plan) == 1 else 1
+            n = min(int(rows_per_call), len(rows))
+            for i in range(0, len(rows), n):
+                part = rows[i:i + n]
+                mel_rows = torch.stack([mel[b, f0:f0 + Fw] for b, f0 in (r[:2] for r in part)])
+                self.iaf_generate_windows(mel_rows, [(r[0],) + r[2:] for r in part], out, noise, seed, form, form_rows,
+                                          check_range, ws_rows=n)
+        return {k: v for k, v in out.items() if k in want}
+
+    def iaf_stream(self, batch=1, seed=0, window_frames=None, want=('wav',)):
+        """A streaming generator: see IafStream."""
+        return IafStream(self, batch, seed, window_frames, want)
+
     def check_range(self):
         """Raise if any iaf_generate(check_range=False) call since the last check left the fp16 range (the outputs of
         such a call are NaN); synchronises the stream once."""
@@ -892,6 +993,95 @@ class Engine(object):
         if want_out:
             out['out_params'] = torch.cat([p[5] for p in parts], 0)
         return out
+
+
+class IafStream(object):
+    """Audio while the mel frames are still arriving (Engine.iaf_stream).
+
+    push(mel_frames [B,n,n_mel]) -> dict of the samples that became final ([B,m] per name in `want`, m >= 0), finish() ->
+    the tail, close().  The concatenation of everything returned equals
+    engine.iaf_generate_long(all_mel, seed=seed, crop='left', window_frames=window_frames) bit for bit however the frames
+    were cut into pushes: windows sit on the fixed grid of config.iaf_plan_windows, a grid window runs as soon as more
+    than its last frame has arrived (so it cannot turn out to be the tail), and finish() plans what is left with the frame
+    count then known.  crop='left' is the one-shot's centred crop whenever the total frame count is a multiple of
+    `period`.  A window is window_frames long, so the first samples appear after about that many frames.
+
+    The stream is a caller of its own in the sense of Engine.fork(): it shares the engine's weights, owns its workspace
+    and the trailing mel frames it still needs (on the device), and issues its work on the torch stream current in the
+    calling thread; one stream object belongs to one thread, and the engine must outlive it."""
+
+    def __init__(self, engine, batch=1, seed=0, window_frames=None, want=('wav',)):
+        self.eng = engine.fork()
+        self.B, self.seed, self.want = int(batch), int(seed), tuple(want)
+        if self.B < 1:
+            raise ValueError('iaf_stream: batch must be >= 1')
+        hp = self.eng.hp
+        self.window_frames = int(window_frames) if window_frames is not None else cfg.iaf_default_window_frames(hp)
+        self.Fw, _, self.lo, self.S = cfg.iaf_window_grid(hp, self.window_frames, 0)
+        self._mel = None          # frames self._base .. self.frames of every utterance, [B, n, n_mel] on the device
+        self._base = 0
+        self.frames = 0           # frames pushed so far
+        self._next = 0            # next grid window
+        self.samples = 0          # samples returned so far
+        self._closed = False
+
+    def _run(self, rows, n_out):
+        """rows (f0, t_origin, keep_from, keep_to, out_t) of the utterance plan -> the n_out samples behind self.samples"""
+        eng = self.eng
+        out = eng._window_outputs(self.B, n_out, self.want)
+        if n_out > 0:
+            Fw = rows[0][5]
+            mel_rows = torch.stack([self._mel[b, f0 - self._base:f0 - self._base + Fw] for (f0, *_r) in rows
+                                    for b in range(self.B)])
+            # the noise is absolute (t_origin); only the place in the returned chunk is relative
+            desc = [(b, to, kf, kt, ot - self.samples) for (f0, to, kf, kt, ot, _) in rows for b in range(self.B)]
+            eng.iaf_generate_windows(mel_rows, desc, out, None, self.seed, None, 1, True)
+            self.samples += n_out
+        return {k: v for k, v in out.items() if k in self.want}
+
+    def push(self, mel_frames):
+        if self._closed:
+            raise RuntimeError('iaf_stream: push after finish() / close()')
+        eng = self.eng
+        m = eng._dev(mel_frames)
+        if m.dim() != 3 or int(m.shape[0]) != self.B or int(m.shape[2]) != eng.n_mel:
+            raise ValueError('mel_frames must be [{}, n, {}], got {}'.format(self.B, eng.n_mel, tuple(m.shape)))
+        self._mel = m if self._mel is None else torch.cat([self._mel, m], 1)
+        self.frames += int(m.shape[1])
+        fs, rows, n_out = eng.frame_shift, [], 0
+        while self.frames > self._next * self.S + self.Fw:         # certain to be a grid window of the final plan
+            f0 = self._next * self.S
+            to, kt = f0 * fs, self.lo + self.S * fs
+            kf = self.samples + n_out - to
+            rows.append((f0, to, kf, kt, self.samples + n_out, self.Fw))
+            n_out += kt - kf
+            self._next += 1
+        out = self._run(rows, n_out)
+        # the tail window starts behind the last grid window that ran: frames before that one are not needed again
+        keep_from = max(self._next - 1, 0) * self.S
+        if keep_from > self._base:
+            self._mel = self._mel[:, keep_from - self._base:].contiguous()
+            self._base = keep_from
+        return out
+
+    def finish(self):
+        """The samples not returned yet; the stream is closed afterwards."""
+        if self._closed:
+            raise RuntimeError('iaf_stream: finish after finish() / close()')
+        rows, n_out = [], 0
+        if self.frames > 0 and self.eng.iaf_length(self.frames) > 0:
+            Fw, plan = cfg.iaf_plan_windows(self.eng.hp, self.frames, self.window_frames, 'left')
+            assert self._next == 0 or (Fw == self.Fw and self._next == len(plan) - 1), (Fw, self.Fw, self._next, len(plan))
+            rows = [r + (Fw,) for r in plan[self._next:]]
+            n_out = self.eng.iaf_length(self.frames) - self.samples
+        out = self._run(rows, n_out)
+        self.close()
+        return out
+
+    def close(self):
+        self._closed = True
+        self._mel = None
+        self.eng.close()
 
 
 PRIORITY_FREQ = 384        # auxilaries/mel_extractor.py:27 (bins below 3 kHz)

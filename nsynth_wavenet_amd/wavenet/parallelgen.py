@@ -46,7 +46,9 @@ def generate(hparams, mel, checkpoint_path, noise=None, seed=None):
         mel_d = torch.as_tensor(np.ascontiguousarray(mel), dtype=torch.float32).to(eng.device)
     torch.cuda.synchronize(eng.device)
     start = time.time()
-    out = eng.iaf_generate(mel_d, noise=noise, seed=seed, want=('wav',))
+    # longer than one call may be (125 s): the windowed call -- such a length used to be refused
+    gen = eng.iaf_generate_long if eng.iaf_needs_windows(mel_d.shape[1]) else eng.iaf_generate
+    out = gen(mel_d, noise=noise, seed=seed, want=('wav',))
     audio = out['wav'].cpu().numpy()
     cost = time.time() - start
     wave_length = audio.shape[1] / 16000
@@ -77,7 +79,8 @@ def generate_async(hparams, mel, checkpoint_path, seed=None):
     ev0 = torch.cuda.Event(enable_timing=True)
     ev1 = torch.cuda.Event(enable_timing=True)
     ev0.record()
-    out = eng.iaf_generate(mel_d, seed=seed, want=('wav',), check_range=True)['wav']
+    gen = eng.iaf_generate_long if eng.iaf_needs_windows(mel_d.shape[1]) else eng.iaf_generate
+    out = gen(mel_d, seed=seed, want=('wav',), check_range=True)['wav']
     ev1.record()
     host = torch.empty(out.shape, dtype=torch.float32, pin_memory=True)
     host.copy_(out, non_blocking=True)
