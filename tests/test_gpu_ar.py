@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import load_json
+import ar_cases as A
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
@@ -40,30 +41,11 @@ def test_golden_ar(tag):
     Q = 256 if cfgd['use_mu_law'] else 65536
     assert gi.min() >= -Q // 2 and gi.max() < Q // 2
     fg = O.Fastgen(w, hp, B, np.float32)
-    # Integer parity of the sampling head (loss_func.py:140-206) GIVEN the engine's own network output and
-    # the injected randoms: against float64 arithmetic the index may differ by ONE step, and only where
-    # the pre-floor() quantity sits within float32 rounding of a decision boundary.
+    # Integer parity of the sampling head (loss_func.py:140-206) GIVEN the engine's own network output and the injected
+    # randoms: the rule lives in tests/ar_cases.py (one copy for this file and tests/test_gpu_ar_heads.py)
     gop = _np(out['out_params'])
     mol = hp.loss_type == 'mol'
-    n_bad = n_flip = 0
-    for t in range(Tn):
-        i64, margin, gap = O.sample_margin(gop[:, t], g['rnd'][t], hp)
-        d = gi[:, t].astype(np.int64) - i64
-        flip = d != 0
-        n_flip += int(flip.sum())
-        if hp.loss_type == 'ce':
-            ok = (np.abs(d) <= 1) & (~flip | (margin <= 2e-5))     # 256 fp32 running sums: ~1.5e-5 of the mass
-        else:
-            # |x| <= 1 in fp32 -> x*Q/2 carries <= ~4e-3 index units of rounding at Q = 65536 (libm exp/log 1-2 ulp)
-            tol = 0.02 if Q == 65536 else 1e-3
-            ok = (np.abs(d) <= 1) & (~flip | (margin <= tol))
-            if mol:     # a different mixture component only where the two best scores tie within fp32 noise
-                ok |= gap <= 1e-5
-        n_bad += int((~ok).sum())
-    print('{}: sampler index vs float64: {} of {} differ by one step at a boundary, {} unexplained'.format(
-        tag, n_flip, B * Tn, n_bad))
-    assert n_bad == 0
-    assert n_flip <= max(2, B * Tn // 20)
+    n_flip = A.assert_sampler_parity(tag, hp, gop, g['rnd'], gi)
     # the float32 oracle sampler on the same inputs agrees except at those boundary cases as well
     mism = sum(int((fg.sample_from(gop[:, t], g['rnd'][t]) != gi[:, t]).sum()) for t in range(Tn))
     assert mism <= n_flip + max(2, B * Tn // 20)
