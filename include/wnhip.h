@@ -280,6 +280,29 @@ WN_API int64_t wn_mel_frames(int64_t n_samples);
  * padding, as in numpy.pad). */
 WN_API int wn_mel_spectrogram(const float* wav, int B, int64_t L, float* mel, void* stream);
 
+/* ---- the batch of one training step, cut from a device-resident dataset (replaces the queue of
+ * auxilaries/reader.py:61-108).  Needs no model handle; errors are reported through wn_last_error(NULL). ---- */
+
+/* pool: every utterance back to back (device, float32); utterance i is pool[utt_off[i] .. utt_off[i] + utt_len[i]).
+ * eligible: the indices of the utterances with utt_len >= L (n_eligible of them; all three tables on the device).
+ * Row b of stream s takes the words r of Philox4x32-10 under key (seed lo, seed hi) and counter (step lo, step hi, b, s):
+ *   u = eligible[(r0 * n_eligible) >> 32],  start = (r1 * (utt_len[u] - L + 1)) >> 32    (64-bit products)
+ * -- uniform over the eligible utterances with replacement and over the starts tf.random_crop can return, a function of
+ * (seed, step, b, s) alone.  Stream 0 is the batch: wav [B][L] = the crop, mel = its log-mel as wn_mel_spectrogram
+ * computes it for the crop (bit for bit; reflect padding at the crop's edges, no load outside the crop).  n_streams = 2
+ * adds stream 1, a second unrelated draw of which only the mel is produced (the reference's mel_rand).
+ *   wav   [B][L]                                    stream 0 only
+ *   mel   [n_streams][B][wn_mel_frames(L)][80]
+ *   picks [n_streams][B][2] = (utterance index, start)
+ * One launch, asynchronous on `stream`, no workspace, no allocation after the first call on a device, no host
+ * synchronisation; every output element has one writer.  WN_EINVAL: a null pointer, B < 1, L <= 1024 (as
+ * wn_mel_spectrogram), n_eligible < 1, n_streams not 1 or 2.  The tables are the caller's contract: an `eligible` entry
+ * whose utterance is shorter than L, or an utt_off / utt_len outside the pool, is not detected. */
+WN_API int wn_train_batch(const float* pool, const int64_t* utt_off, const int64_t* utt_len,
+                          const int32_t* eligible, int n_eligible,
+                          int B, int64_t L, uint64_t seed, uint64_t step, int n_streams,
+                          float* wav, float* mel, int64_t* picks, void* stream);
+
 /* ---- autoregressive path (wavenet.py:379-514, fastgen.py:118-169) ---- */
 
 /* Number of injected random values per sample and per batch element:

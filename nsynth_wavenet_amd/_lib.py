@@ -28,7 +28,8 @@ SYMBOLS = ['wn_abi_version', 'wn_create', 'wn_set_weight', 'wn_finalize', 'wn_ia
            'wn_iaf_grad_count', 'wn_iaf_grad_info', 'wn_iaf_grad_floats', 'wn_iaf_train_tape_bytes',
            'wn_iaf_train_workspace_bytes', 'wn_iaf_forward_train_tape', 'wn_iaf_backward_weights_workspace_bytes',
            'wn_iaf_backward_weights', 'wn_iaf_set_weights_workspace_bytes', 'wn_iaf_set_weights',
-           'wn_iaf_window_geometry', 'wn_iaf_generate_windows', 'wn_iaf_windows_workspace_bytes']
+           'wn_iaf_window_geometry', 'wn_iaf_generate_windows', 'wn_iaf_windows_workspace_bytes',
+           'wn_train_batch']
 
 
 class WindowRow(ctypes.Structure):
@@ -181,6 +182,7 @@ def load():
     lib.wn_mel_frames.argtypes = [i64]
     lib.wn_mel_frames.restype = i64
     lib.wn_mel_spectrogram.argtypes = [vp, c.c_int, i64, vp, vp]
+    lib.wn_train_batch.argtypes = [vp, vp, vp, vp, i32, i32, i64, u64, u64, i32, vp, vp, vp, vp]
     lib.wn_last_error.argtypes = [vp]
     lib.wn_last_error.restype = c.c_char_p
     lib.wn_destroy.argtypes = [vp]

@@ -16,12 +16,26 @@ and of the deconv stacks the student owns -- on top of ParallelWavenet.loss_and_
     trainer = StudentTrainer(student, w, lr={0: 2e-4, 90000: 6e-5})
     for batch in batches:                       # {'wav': [B,T'], 'mel': [B,F,80]} (+ 'mel_rand')
         out = trainer.step(batch)               # calculate_loss's entries and 'grad_norm': device tensors
+
+The batches: DeviceDataset keeps the training set on the device and cuts the batch of step k from it in one
+launch, a pure function of (seed, k); trainer.save(logdir) / trainer.restore(logdir) write and read a TF V2 checkpoint with
+the optimiser state, so that a restored trainer continues with the bits of the uninterrupted run.
+
+    ds = DeviceDataset.from_tfrecord(train_path, hparams.wave_length, seed=0)
+    while trainer.global_step < num_iters:
+        out = trainer.step(ds.batch(trainer.global_step, batch_size))
+    trainer.save(logdir)
+
+train_wavenet.py / train_parallel_wavenet.py (train_cli.py) are this loop behind the reference's command lines.
 """
 import math
+import os
 
 import numpy as np
 import torch
 
+from . import _lib
+from . import weights as wts
 from .engine import adam_ema_step, grad_sumsq
 
 
@@ -84,6 +98,146 @@ def dropout_step_seed(base, step):
     (base + step * 0x9E3779B97F4A7C15) mod 2^64.  The multiplier is odd, so for one base the seeds of 2^64 consecutive steps
     are distinct, and a trainer resumed at step n continues the sequence it would have run."""
     return (int(base) + int(step) * 0x9E3779B97F4A7C15) & (2 ** 64 - 1)
+
+
+def batch_picks(seed, step, B, lengths, L, stream=0):
+    """The picks of the device-side batch (wn_train_batch), on the host: int64 [B, 2] = (utterance index,
+    start) of every row.  Row b of stream `stream` takes the words r of Philox4x32-10(key = the 64-bit seed, counter =
+    (step lo, step hi, b, stream)); with `eligible` the indices of the utterances of at least L samples, in order,
+    u = eligible[(r0 * len(eligible)) >> 32] and start = (r1 * (lengths[u] - L + 1)) >> 32.  A function of (seed, step, b,
+    stream) and the lengths alone: a larger B extends the picks without changing them."""
+    lengths = np.asarray(lengths, np.int64).reshape(-1)
+    L = int(L)
+    eligible = np.nonzero(lengths >= L)[0]
+    if eligible.size < 1:
+        raise ValueError('batch_picks: no utterance has {} samples (the longest has {})'.format(L, int(lengths.max()) if lengths.size else 0))
+    seed, step = int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)
+    b = np.arange(int(B), dtype=np.uint64)
+    r = _philox4x32_10(np.uint64(step & 0xFFFFFFFF), np.uint64(step >> 32), b, np.uint64(int(stream)), seed & 0xFFFFFFFF, seed >> 32)
+    r0, r1 = (np.broadcast_to(w, b.shape).astype(np.uint64) for w in r[:2])
+    u = eligible[((r0 * np.uint64(eligible.size)) >> np.uint64(32)).astype(np.int64)]
+    span = (lengths[u] - L + 1).astype(np.uint64)
+    start = ((r1 * span) >> np.uint64(32)).astype(np.int64)
+    return np.stack([u.astype(np.int64), start], axis=1)
+
+
+class DeviceDataset(object):
+    """The training set on the device: every utterance back to back in one float32 pool, and the batch of a step cut from
+    it and featurised by one launch of wn_train_batch (csrc/wn_batch.hip).  Replaces the reference's TFRecord queue, random
+    crop and shuffle_batch (auxilaries/reader.py:61-108): the same marginal distribution -- an utterance uniformly among
+    those of at least `length` samples, a start uniformly among those tf.random_crop can return -- as a function of
+    (seed, step), so a resumed run sees the batches of the uninterrupted one.
+
+    utterances: a list of 1-d float arrays.  length: the crop, hparams.wave_length (more than 1024 samples)."""
+
+    def __init__(self, utterances, length, seed=0, device=None):
+        self.length, self.seed = int(length), int(seed) & (2 ** 64 - 1)
+        self.utterances = [np.ascontiguousarray(np.asarray(u, np.float32).reshape(-1)) for u in utterances]
+        self.lengths = np.array([u.shape[0] for u in self.utterances], np.int64)
+        eligible = np.nonzero(self.lengths >= self.length)[0].astype(np.int32)
+        if eligible.size < 1:
+            raise ValueError('DeviceDataset: none of the {} utterances has {} samples (the longest has {})'.format(
+                len(self.utterances), self.length, int(self.lengths.max()) if self.lengths.size else 0))
+        self.lib = _lib.load()
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        offsets = np.concatenate([[0], np.cumsum(self.lengths)[:-1]]).astype(np.int64)
+        self.pool = torch.from_numpy(np.concatenate(self.utterances)).to(self.device)
+        self.utt_off = torch.from_numpy(offsets).to(self.device)
+        self.utt_len = torch.from_numpy(self.lengths.copy()).to(self.device)
+        self.eligible = torch.from_numpy(eligible).to(self.device)
+        self.frames = int(self.lib.wn_mel_frames(self.length))
+
+    @classmethod
+    def from_tfrecord(cls, path, length, seed=0, device=None):
+        """Every utterance of a TFRecord written by build_dataset.py (auxilaries/reader.py), padded as stored."""
+        from .auxilaries import reader
+        return cls([audio for _, audio, _ in reader.read_tfrecord(path)], length, seed=seed, device=device)
+
+    def batch(self, step, batch_size, mel_rand=False):
+        """{'wav': [B, length], 'mel': [B, frames, 80], 'picks': int64 [n_streams, B, 2]} of step `step`, with mel_rand=True
+        also 'mel_rand' [B, frames, 80] (the mel of a second, unrelated draw): device tensors, enqueued on the current
+        stream without a host synchronisation."""
+        B, ns = int(batch_size), 2 if mel_rand else 1
+        with torch.cuda.device(self.device):
+            wav = torch.empty(B, self.length, dtype=torch.float32, device=self.device)
+            mel = torch.empty(ns, B, self.frames, 80, dtype=torch.float32, device=self.device)
+            picks = torch.empty(ns, B, 2, dtype=torch.int64, device=self.device)
+            _lib.check(self.lib.wn_train_batch(self.pool.data_ptr(), self.utt_off.data_ptr(), self.utt_len.data_ptr(),
+                                               self.eligible.data_ptr(), int(self.eligible.numel()), B, self.length, self.seed,
+                                               int(step) & (2 ** 64 - 1), ns, wav.data_ptr(), mel.data_ptr(), picks.data_ptr(),
+                                               torch.cuda.current_stream(self.device).cuda_stream))
+        out = {'wav': wav, 'mel': mel[0], 'picks': picks}
+        if mel_rand:
+            out['mel_rand'] = mel[1]
+        return out
+
+    def host_batch(self, step, batch_size, mel_rand=False):
+        """The same batch by the host route, as numpy arrays: batch_picks, slices of the utterances and
+        auxilaries.mel_extractor.batch_melspectrogram (float64 FFT) -- what the tests and the benchmark compare with."""
+        from .auxilaries import mel_extractor
+        picks = [batch_picks(self.seed, step, batch_size, self.lengths, self.length, stream=s) for s in range(2 if mel_rand else 1)]
+        crops = [np.stack([self.utterances[u][t:t + self.length] for u, t in p]) for p in picks]
+        out = {'wav': crops[0], 'mel': mel_extractor.batch_melspectrogram(crops[0]), 'picks': np.stack(picks)}
+        if mel_rand:
+            out['mel_rand'] = mel_extractor.batch_melspectrogram(crops[1])
+        return out
+
+
+# ---- checkpoints (DESIGN.md 23): the keys tf.train.Saver writes for the reference's training graph ----
+ADAM_M, ADAM_V = '/Adam', '/Adam_1'
+
+
+def checkpoint_tensors(trained, frozen, global_step, beta1=0.9, beta2=0.999):
+    """{checkpoint key: array} of one training state.  trained: {variable: (value, m, v, shadow)} -> '<var>', '<var>/Adam',
+    '<var>/Adam_1', '<var>/ExponentialMovingAverage'; frozen: {variable: value} under the plain name only; 'global_step'
+    (int32) and the informational 'beta1_power' / 'beta2_power' (float32, beta^global_step)."""
+    out = {}
+    for name, (p, m, v, e) in trained.items():
+        out[name], out[name + ADAM_M], out[name + ADAM_V], out[name + wts.EMA] = (np.asarray(a, np.float32) for a in (p, m, v, e))
+    for name, a in frozen.items():
+        out[name] = np.asarray(a, np.float32)
+    out['global_step'] = np.array(int(global_step), np.int32)
+    out['beta1_power'] = np.array(float(beta1) ** int(global_step), np.float32)
+    out['beta2_power'] = np.array(float(beta2) ** int(global_step), np.float32)
+    return out
+
+
+def write_checkpoint(logdir, tensors):
+    """model.ckpt-<global_step> (a TF V2 bundle) in logdir and the `checkpoint` state file naming it; returns the prefix"""
+    from . import tf_bundle
+    os.makedirs(logdir, exist_ok=True)
+    name = 'model.ckpt-{:d}'.format(int(tensors['global_step']))
+    prefix = tf_bundle.write_bundle(os.path.join(logdir, name), tensors)
+    with open(os.path.join(logdir, 'checkpoint'), 'wt') as f:
+        f.write('model_checkpoint_path: "{0}"\nall_model_checkpoint_paths: "{0}"\n'.format(name))
+    return prefix
+
+
+def resolve_checkpoint(prefix_or_logdir):
+    """a checkpoint prefix as it is, a directory -> its latest checkpoint (weights.latest_checkpoint)"""
+    if os.path.isdir(prefix_or_logdir):
+        prefix = wts.latest_checkpoint(prefix_or_logdir)
+        if prefix is None:
+            raise ValueError('no checkpoint found in {}'.format(prefix_or_logdir))
+        return prefix
+    return prefix_or_logdir
+
+
+def checkpoint_weights(prefix_or_logdir, hp, kind=None):
+    """{variable: value} of a training checkpoint under the PLAIN names -- the weights a run continues from, where
+    weights.load_checkpoint prefers the shadows (what generation wants)."""
+    from . import tf_bundle
+    prefix = resolve_checkpoint(prefix_or_logdir)
+    r = tf_bundle.BundleReader(prefix)
+    out = {}
+    for name, shape in wts.expected_variables(hp, kind):
+        if not r.has_tensor(name):
+            raise KeyError('checkpoint {} lacks {}'.format(prefix, name))
+        a = r.get_tensor(name)
+        if a.size != int(np.prod(shape)):
+            raise ValueError('checkpoint {}: {} has shape {}, the model expects {}'.format(prefix, name, list(a.shape), list(shape)))
+        out[name] = np.asarray(a, np.float32).reshape(shape)
+    return out
 
 
 class _DeviceTrainer(object):
@@ -154,6 +308,49 @@ class _DeviceTrainer(object):
         return self
 
     def use_weights(self):
+        self._repack(self.p)
+        return self
+
+    def save(self, logdir):
+        """Write model.ckpt-<global_step> into logdir as a TF V2 bundle with the keys tf.train.Saver writes for the
+        reference's training graph -- '<var>', '<var>/Adam', '<var>/Adam_1', '<var>/ExponentialMovingAverage' for every
+        trained variable, the plain name alone for a frozen one, 'global_step', 'beta1_power', 'beta2_power' -- and the
+        `checkpoint` state file.  The eval CLIs load the directory as it is (shadows preferred); restore() continues from it.
+        Returns the prefix."""
+        host = [[b.cpu().numpy() for b in bufs] for bufs in (self.p, self.m, self.v, self.ema)]
+        trained = {}
+        for i, tab in enumerate(self.tables):
+            for name, off, shape in tab:
+                n = int(np.prod(shape))
+                trained[name] = tuple(h[i][off:off + n].reshape(shape) for h in host)
+        return write_checkpoint(logdir, checkpoint_tensors(trained, self._frozen, self.global_step, self.beta1, self.beta2))
+
+    def restore(self, prefix_or_logdir):
+        """Refill the weights, both Adam moments, the shadows and global_step from a checkpoint save() wrote (a prefix, or a
+        directory: its latest) and re-pack the handle with the weights.  The next step then has the bits of the run that
+        wrote the checkpoint.  KeyError naming the first missing key, ValueError naming a key whose shape disagrees.  Frozen
+        variables are the handle's: they are not reloaded."""
+        from . import tf_bundle
+        prefix = resolve_checkpoint(prefix_or_logdir)
+        r = tf_bundle.BundleReader(prefix)
+        if not r.has_tensor('global_step'):
+            raise KeyError('checkpoint {} lacks global_step'.format(prefix))
+        host = [[np.zeros(b.numel(), np.float32) for b in self.p] for _ in range(4)]
+        for i, tab in enumerate(self.tables):
+            for name, off, shape in tab:
+                for h, suffix in zip(host, ('', ADAM_M, ADAM_V, wts.EMA)):
+                    key = name + suffix
+                    if not r.has_tensor(key):
+                        raise KeyError('checkpoint {} lacks {}'.format(prefix, key))
+                    if list(r.entries[key]['shape']) != list(shape):
+                        raise ValueError('checkpoint {}: {} has shape {}, the model expects {}'.format(
+                            prefix, key, list(r.entries[key]['shape']), list(shape)))
+                    h[i][off:off + int(np.prod(shape))] = r.get_tensor(key).reshape(-1)
+        for bufs, h in zip((self.p, self.m, self.v, self.ema), host):
+            for b, a in zip(bufs, h):
+                b.copy_(torch.from_numpy(a))
+        self.global_step = int(r.get_tensor('global_step'))
+        self.lr_t, self.lr_history = None, []
         self._repack(self.p)
         return self
 
