@@ -12,7 +12,7 @@
 // draw against a few loads per row, so the kernel is bound by the SIMDs' transcendental issue, not by HBM.
 // Draws: injected [B,S,T] (row b*S + s of the reference's [B*S,T] draw), or Philox4x32-10 keyed by (seed; t, s/4, b) with
 // lane s%4 of the result -- a function of (seed, b, s, t) alone -- through log u - log(1 - u), u ~ U(1e-5, 1 - 1e-5), the
-// transform of iaf_noise_body (wn_iaf.hip).
+// transform of iaf_noise_draw (wn_iaf_call.hip).
 //
 // dx_gauss_kernel -- kl_loss_gauss (:404-429): the closed-form KL(q || p) of two Gaussians per sample and the squared
 // log-scale difference, elementwise.

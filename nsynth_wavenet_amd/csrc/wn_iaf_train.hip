@@ -331,7 +331,7 @@ bool it_supported(const wn_handle* h) {
 bool it_shape_ok(const wn_handle* h, int B, int F, long long T) {
     if (B < 1 || F < 1 || T < 1) return false;
     const long long TE = (long long)F * h->frame_shift, md = 1ll << (h->cfg.num_stages - 1);
-    return T <= TE && T % md == 0 && TE <= 2000000;
+    return T <= TE && T % md == 0 && TE <= WN_MAX_ROW_SAMPLES;
 }
 // ... and by name
 int it_check(wn_handle* h, const char* fn) {
@@ -356,7 +356,7 @@ int it_shape_check(wn_handle* h, const char* fn, int B, int F, int64_t T) {
                                "(wavenet.py:79 assert cond_len >= x_len)", fn, (long long)T, F);
     if (T % md) return wn_fail(h, WN_EINVAL, "%s: length %lld is not a multiple of the largest "
                                "dilation %lld (masked.py:188)", fn, (long long)T, md);
-    if (TE > 2000000) return wn_fail(h, WN_EINVAL, "%s: utterance too long (32-bit row offsets)", fn);
+    if (TE > WN_MAX_ROW_SAMPLES) return wn_fail(h, WN_EINVAL, "%s: utterance too long (32-bit row offsets)", fn);
     return WN_OK;
 }
 

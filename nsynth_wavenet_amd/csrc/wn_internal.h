@@ -290,6 +290,9 @@ constexpr int WN_COND_HOISTED = 2; // one GEMM per deconv stack writes them for 
 constexpr int IAF_LP = 2048;   // zero left pad of activation rows (>= 2 * max dilation; >= 32 * 64: the DL layout of
                                // wn_iaf_g.hip keeps 64 zero columns in front of each of its 32 residue rows)
 constexpr int IAF_XP = 64;     // zero left pad of the flow input x (>= filter_length)
+// Most upsampled samples in one row of a generate or training call: the kernels address a batch element's rows (960 bytes
+// per sample) with 32-bit buffer offsets.  125 s of audio; Engine.ONE_SHOT_MAX_SAMPLES (engine.py) is the Python twin.
+constexpr int64_t WN_MAX_ROW_SAMPLES = 2000000;
 // First bytes of every caller-owned workspace: the range-guard words of the generate calls made on it (status[0] of the
 // current call, status[1] accumulated since wn_iaf_range_reset).  Nothing else -- wn_deconv included -- writes there.
 constexpr size_t WN_WS_HEAD = 256;
@@ -330,6 +333,23 @@ void wn_iaf_x_layer(const wn_handle* h, const IafLayerX& lx, const float* lin, f
                     int64_t TE, int c0, int B, int64_t T, hipStream_t st);
 void wn_iaf_x_head(const wn_handle* h, const IafFlowX& fx, const float* lin, const float* enc, float* x, float* Mt,
                    float* St, int64_t RS, int64_t TE, int c0, int XR, int64_t T, int first, int B, hipStream_t st);
+// ---- fp32 MFMA kernels (wn_iaf.hip).  _c: hoisted conditioning (accumulators start from the C rows, Q4 residual rows; x:
+// the start conv runs in front of the layer); q4: start conv into the Q4 rows of the hoisted form ----
+int wn_iaf_f32_set_attrs(wn_handle* h);
+void wn_iaf_f32_start(const float* x, const float* wb, float* l, int64_t T, int XR, int64_t RS, int B, bool q4, hipStream_t st);
+void wn_iaf_f32_layer(const float* lin, float* lout, const float* enc, const float* wpack, int64_t RS, int64_t TE, int c0,
+                      int d, int B, int64_t T, int num_cu, hipStream_t st);
+void wn_iaf_f32_layer_c(const float* lin, float* lout, const float* C, int64_t c_bstride, const float* wpack, int64_t RS,
+                        int d, int B, int64_t T, int num_cu, hipStream_t st, const float* x = nullptr, int XR = 0,
+                        const float* wstart = nullptr);
+void wn_iaf_f32_layer_head(const float* lin, const float* C, const float* Ch, int64_t c_bstride, const float* wpack,
+                           const float* wpack_head, float* x, float* Mt, float* St, int64_t RS, int XR, int d, int first,
+                           int B, int64_t T, int num_cu, hipStream_t st);
+void wn_iaf_f32_head(const float* lin, const float* enc, const float* wpack, float* x, float* Mt, float* St, int64_t RS,
+                     int64_t TE, int c0, int XR, int64_t T, int first, int B, int num_cu, hipStream_t st);
+void wn_iaf_f32_head_c(const float* lin, const float* C, int64_t c_bstride, const float* wpack, float* x, float* Mt,
+                       float* St, int64_t RS, int XR, int64_t T, int first, int B, int num_cu, hipStream_t st);
+// ---- split-fp16 kernels, conditioning fused (wn_iaf_h.hip) / hoisted (wn_iaf_c.hip) ----
 int wn_iaf_h_set_attrs(wn_handle* h);
 void wn_iaf_h_start(const float* x, const float* wb, float* l, int64_t T, int XR, int64_t RS, int B, hipStream_t st,
                     unsigned* status);

@@ -681,7 +681,7 @@ int tg_forward_check(wn_handle* h, const char* fn, const float* wav, const float
                                "(wavenet.py:79 assert cond_len >= x_len)", fn, (long long)T, F);
     if (T % md) return wn_fail(h, WN_EINVAL, "%s: length %lld is not a multiple of the largest "
                                "dilation %lld (masked.py:188)", fn, (long long)T, md);
-    if (TE > 2000000) return wn_fail(h, WN_EINVAL, "%s: utterance too long (32-bit row offsets)", fn);
+    if (TE > WN_MAX_ROW_SAMPLES) return wn_fail(h, WN_EINVAL, "%s: utterance too long (32-bit row offsets)", fn);
     return WN_OK;
 }
 

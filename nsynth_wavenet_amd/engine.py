@@ -164,14 +164,7 @@ class Engine(object):
         noise = self._dev(noise)
         if noise is not None and tuple(noise.shape) != (B, T):
             raise ValueError('noise must be [{}, {}], got {}'.format(B, T, tuple(noise.shape)))
-        out = {}
-        new = lambda dt=torch.float32: torch.empty((B, T), dtype=dt, device=self.device)
-        wav = new()
-        idx = new(torch.int32) if 'idx' in want else None
-        xr = new() if 'x' in want else None
-        mt = new() if 'mean_tot' in want else None
-        st = new() if 'scale_tot' in want else None
-        ro = new() if 'rand_input' in want else None
+        out = self._window_outputs(B, T, want)
         with torch.cuda.device(self.device):
             form = _lib.FORM_DEFAULT
             try:
@@ -186,27 +179,37 @@ class Engine(object):
 
             def run(f):
                 self._check(self.lib.wn_iaf_generate_form(
-                    self._h, f, _ptr(mel), B, F, _ptr(noise), ctypes.c_uint64(int(seed)), _ptr(wav), _ptr(idx),
-                    _ptr(xr), _ptr(mt), _ptr(st), _ptr(ro), _ptr(ws), ws.numel(), self._stream()))
-            run(form)
-            self._last_ws = ws
-            if check_range and not self.precision.startswith('f32') and T > 0:
-                rc = self.lib.wn_iaf_range_status(self._h, _ptr(ws), self._stream())
-                if rc == _lib.WN_ERANGE:
-                    self.range_fallbacks += 1
-                    run(_lib.FORM_F32)      # same seed -> the same Philox draws when the noise is device-drawn
-                    # handled here: not to be reported again by a later check_range()
-                    self._check(self.lib.wn_iaf_range_reset(self._h, _ptr(ws), self._stream()))
-                else:
-                    self._check(rc)
-        for k, v in (('wav', wav), ('idx', idx), ('x', xr), ('mean_tot', mt), ('scale_tot', st),
-                     ('rand_input', ro)):
-            if k in want:
-                out[k] = v
-        return out
+                    self._h, f, _ptr(mel), B, F, _ptr(noise), ctypes.c_uint64(int(seed)), _ptr(out['wav']), _ptr(out['idx']),
+                    _ptr(out['x']), _ptr(out['mean_tot']), _ptr(out['scale_tot']), _ptr(out['rand_input']), _ptr(ws),
+                    ws.numel(), self._stream()))
+            self._run_ranged(run, form, ws, check_range and not self.precision.startswith('f32') and T > 0)
+        return {k: v for k, v in out.items() if k in want}
+
+    def _window_outputs(self, B, T, want):
+        """The output set of a generate call: wav always, the others where `want` names them, else None."""
+        new = lambda dt=torch.float32: torch.empty((B, T), dtype=dt, device=self.device)
+        return {'wav': new(), 'idx': new(torch.int32) if 'idx' in want else None, 'x': new() if 'x' in want else None,
+                'mean_tot': new() if 'mean_tot' in want else None, 'scale_tot': new() if 'scale_tot' in want else None,
+                'rand_input': new() if 'rand_input' in want else None}
+
+    def _run_ranged(self, run, form, ws, read_status):
+        """run(form) on workspace ws; where read_status, read the call's range word (one 4-byte read-back, which synchronises
+        the stream) and re-run a call that left the fp16 range on the fp32 form."""
+        run(form)
+        self._last_ws = ws
+        if not read_status:
+            return
+        rc = self.lib.wn_iaf_range_status(self._h, _ptr(ws), self._stream())
+        if rc == _lib.WN_ERANGE:
+            self.range_fallbacks += 1
+            run(_lib.FORM_F32)      # same seed -> the same Philox draws when the noise is device-drawn
+            # handled here: not to be reported again by a later check_range()
+            self._check(self.lib.wn_iaf_range_reset(self._h, _ptr(ws), self._stream()))
+        else:
+            self._check(rc)
 
     # ---- windowed IAF generation (DESIGN.md 21) ----
-    ONE_SHOT_MAX_SAMPLES = 2000000         # wn_iaf_generate refuses more upsampled samples per utterance (32-bit row offsets)
+    ONE_SHOT_MAX_SAMPLES = 2000000         # twin of WN_MAX_ROW_SAMPLES (csrc/wn_internal.h): wn_iaf_generate refuses longer utterances
 
     def iaf_needs_windows(self, num_frames):
         """True when iaf_generate refuses num_frames for its length and iaf_generate_long has to take the call."""
@@ -219,12 +222,6 @@ class Engine(object):
         self._check(self.lib.wn_iaf_window_geometry(self._h, ctypes.byref(r), ctypes.byref(fb), ctypes.byref(fa),
                                                     ctypes.byref(p)))
         return int(r.value), int(fb.value), int(fa.value), int(p.value)
-
-    def _window_outputs(self, B, T, want):
-        new = lambda dt=torch.float32: torch.empty((B, T), dtype=dt, device=self.device)
-        return {'wav': new(), 'idx': new(torch.int32) if 'idx' in want else None, 'x': new() if 'x' in want else None,
-                'mean_tot': new() if 'mean_tot' in want else None, 'scale_tot': new() if 'scale_tot' in want else None,
-                'rand_input': new() if 'rand_input' in want else None}
 
     def iaf_generate_windows(self, mel_rows, rows, out, noise_abs=None, seed=0, form=None, form_rows=1, check_range=True,
                              ws_rows=None):
@@ -255,16 +252,7 @@ class Engine(object):
                     self._h, f, int(form_rows), _ptr(mel_rows), R, Fw, table, _ptr(noise_abs), B_out, T_out,
                     ctypes.c_uint64(int(seed)), _ptr(wav), _ptr(out.get('idx')), _ptr(out.get('x')), _ptr(out.get('mean_tot')),
                     _ptr(out.get('scale_tot')), _ptr(out.get('rand_input')), _ptr(ws), ws.numel(), self._stream()))
-            run(form)
-            self._last_ws = ws
-            if check_range and not self.precision.startswith('f32') and form != _lib.FORM_F32:
-                rc = self.lib.wn_iaf_range_status(self._h, _ptr(ws), self._stream())
-                if rc == _lib.WN_ERANGE:
-                    self.range_fallbacks += 1
-                    run(_lib.FORM_F32)
-                    self._check(self.lib.wn_iaf_range_reset(self._h, _ptr(ws), self._stream()))
-                else:
-                    self._check(rc)
+            self._run_ranged(run, form, ws, check_range and not self.precision.startswith('f32') and form != _lib.FORM_F32)
 
     def iaf_generate_long(self, mel, noise=None, seed=0, want=('wav',), window_frames=None, rows_per_call=8, crop='centre',
                           check_range=True, form=None, out=None):

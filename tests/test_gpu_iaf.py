@@ -304,7 +304,7 @@ def test_split_fp16_is_as_accurate_as_fp32():
 
 def test_conditioning_placement_policy():
     """The default 'f16x3' engine hoists the per-layer conditioning 1x1s into one GEMM per deconv
-    stack (wn_iaf.hip wn_iaf_hoisted); 'f16x3-fused' keeps them inside the layer kernels.  Both
+    stack (wn_iaf_call.hip wn_iaf_hoisted); 'f16x3-fused' keeps them inside the layer kernels.  Both
     forms are the same arithmetic up to fp32 summation order; the forced engine reproduces the
     default bit for bit."""
     from oracle import wavenet_np as O
