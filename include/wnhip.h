@@ -33,7 +33,7 @@
  *     available from wn_last_error().
  *   - Concurrency (SURVEY 8(b) "Threading / streams"; tests/test_gpu_threads.py drives one handle from two
  *     host threads on two streams).  After wn_finalize() the weights and every table of a handle are read-only.
- *     The WORK calls -- wn_deconv, wn_iaf_generate*, wn_iaf_range_*, wn_clip_quant, wn_ar_reset / wn_ar_step /
+ *     The WORK calls -- wn_deconv, wn_iaf_generate*, wn_iaf_encode, wn_iaf_latent_log_prob, wn_iaf_range_*, wn_clip_quant, wn_ar_reset / wn_ar_step /
  *     wn_ar_generate / wn_ar_cond_vars, wn_teacher_forward / wn_teacher_log_prob / wn_teacher_log_prob_grad, wn_distill_mol_xent /
  *     wn_distill_gauss_kl -- keep all per-call state (the
  *     range-guard word, the autoregressive queues and step counter) in the caller's workspace / state buffer:
@@ -260,6 +260,45 @@ WN_API int wn_iaf_generate_windows(wn_handle* h, int form, int form_rows, const 
                             void* ws, size_t ws_bytes, void* stream);
 /* wn_iaf_workspace_bytes_form(h, form, R, Fw) plus the row table (0 for a bad argument) */
 WN_API size_t wn_iaf_windows_workspace_bytes(const wn_handle* h, int R, int Fw, int form);
+
+/* The inverse of the student: the latent z with feed_forward(noise = z)['x'] == x, by fixed-point sweeps.
+ * feed_forward returns x = z scale_tot(z) + mean_tot(z) where scale_tot[t], mean_tot[t] depend on z[< t] only, so
+ * z <- (x - mean_tot(z)) / scale_tot(z) is exact on the first k samples after k sweeps.  One call enqueues n_sweeps sweeps on
+ * `stream` without a host synchronisation; a sweep is the prologue with noise = z, the residual stack of the generate
+ * call, and a back kernel: z' = (x - mean_tot) / min(scale_tot, e^7), a non-finite z' becomes 0, then z' is clamped to
+ * +-z_max; z [B,T] is read and written in place.
+ *   x, z                 [B,T]  T = wn_iaf_length(h, F); z holds the starting iterate on entry
+ *   tol                  front[b] = the smallest t with |z' - z| > tol in the LAST sweep of the call, T if none (int32 [B]);
+ *                        tol = 0 compares the bits
+ *   mean_tot, scale_tot  [B,T] of the last sweep's input iterate -- the converged z's own once front == T   (optional)
+ *   counts               int32 [4]: [0] elements clamped in the last sweep; [1] the OR of the range words of the call's
+ *                        sweeps (non-zero: a split-fp16 operand left the fp16 range; such a sweep leaves z as it was and
+ *                        writes NaN to mean_tot / scale_tot -- go on from the same z with WN_FORM_F32 and first = 1);
+ *                        [2] the first sweep of this call, counted from 1, after which every front was T and nothing was
+ *                        clamped, 0 if none -- the call's later sweeps then change nothing, so z, the totals and front
+ *                        are that sweep's; [3] 0.  The workspace's accumulated status word is left alone.
+ *   first                1: the call computes the upsampler and the conditioning term (a fresh encode, a new mel, another
+ *                        form, another workspace).  0: CALLER CONTRACT -- the previous call on this workspace was a
+ *                        wn_iaf_encode of the same handle, form, mel contents, B and F, and nothing has written the
+ *                        workspace since; a student with a shared deconv stack then reuses the encoding and the
+ *                        conditioning term that call left there and runs neither the upsampler nor the conditioning GEMM.
+ *                        Within one call only the first sweep runs them in any case.  Students with private stacks run
+ *                        both in every sweep whatever `first` says.
+ * Refused with WN_EINVAL: a teacher handle; a mu-law student (its x is not the flow's output); n_sweeps < 1; z_max <= 0 or
+ * NaN; tol < 0 or NaN; a null mel / x / z / front / counts / workspace; what wn_iaf_generate_form refuses.  WN_ENOMEM: a
+ * workspace below wn_iaf_encode_workspace_bytes, which is 0 for whatever the call would refuse. */
+WN_API size_t wn_iaf_encode_workspace_bytes(const wn_handle* h, int form, int B, int F);
+WN_API int wn_iaf_encode(wn_handle* h, int form, const float* mel, int B, int F, const float* x, float* z,
+                  int n_sweeps, float z_max, float tol, int first, float* mean_tot, float* scale_tot,
+                  int32_t* front, int32_t* counts, void* ws, size_t ws_bytes, void* stream);
+/* log p(x[t]) = log f(z[t]) - log scale_tot[t] of the student's density at x = z scale_tot + mean_tot: f is Logistic(0,1),
+ * log f(z) = -z - 2 softplus(-z), for loss_type logistic and Normal(0,1) for gauss.  The untruncated density: the
+ * reference draws u ~ U(1e-5, 1 - 1e-5), which cuts the logistic off at |z| = 11.5; that clip is ignored here.
+ * log_prob [B,T] float32 (optional), row_sums [B] float64 (optional): each row summed in double in a fixed order, so
+ * repeated calls give the same bits.  Evaluated in double, rounded once.  Refused: a teacher handle, a null z or
+ * scale_tot, B < 1 or T < 1. */
+WN_API int wn_iaf_latent_log_prob(wn_handle* h, const float* z, const float* scale_tot, int B, int64_t T,
+                           float* log_prob, double* row_sums, void* stream);
 
 /* _clip_quant_scale on its own (parallel_wavenet.py:347-359 with
  * utils.cast_quantize / inv_cast_quantize / inv_mu_law, utils.py:108-159):

@@ -29,6 +29,7 @@ SYMBOLS = ['wn_abi_version', 'wn_create', 'wn_set_weight', 'wn_finalize', 'wn_ia
            'wn_iaf_train_workspace_bytes', 'wn_iaf_forward_train_tape', 'wn_iaf_backward_weights_workspace_bytes',
            'wn_iaf_backward_weights', 'wn_iaf_set_weights_workspace_bytes', 'wn_iaf_set_weights',
            'wn_iaf_window_geometry', 'wn_iaf_generate_windows', 'wn_iaf_windows_workspace_bytes',
+           'wn_iaf_encode_workspace_bytes', 'wn_iaf_encode', 'wn_iaf_latent_log_prob',
            'wn_train_batch']
 
 
@@ -96,6 +97,10 @@ def load():
     lib.wn_iaf_windows_workspace_bytes.argtypes = [vp, i32, i32, i32]
     lib.wn_iaf_windows_workspace_bytes.restype = sz
     lib.wn_clip_quant.argtypes = [vp, vp, i64, vp, vp, vp]
+    lib.wn_iaf_encode_workspace_bytes.argtypes = [vp, i32, i32, i32]
+    lib.wn_iaf_encode_workspace_bytes.restype = sz
+    lib.wn_iaf_encode.argtypes = [vp, i32, vp, i32, i32, vp, vp, i32, c.c_float, c.c_float, i32, vp, vp, vp, vp, vp, sz, vp]
+    lib.wn_iaf_latent_log_prob.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp]
     lib.wn_ar_n_rand.argtypes = [vp]
     lib.wn_ar_state_bytes.argtypes = [vp, i32]
     lib.wn_ar_state_bytes.restype = sz

@@ -147,6 +147,168 @@ __global__ void clip_quant_kernel(const float* __restrict__ x, int64_t n, int Q,
     if (idx) idx[i] = qi;
 }
 
+// ---------------- the back of an encode sweep (wn_iaf_encode) ----------------
+// iaf_final_kernel's counterpart for the inverse direction: z' = (x - Mt) / min(St, e^7), non-finite -> 0, clamped to
+// +-z_max, written over z.  A thread owns one quad of a row (16-byte accesses where T and the pointers allow, vec), a
+// workgroup 1024 samples.  The row's front -- the first sample the sweep changed by more than tol -- is a per-block minimum
+// here (a wave butterfly, then the waves in order) into part[0][b][bx], the clamp count likewise into part[1][b][bx];
+// iaf_encode_reduce_kernel folds them.  No atomics but the range flag, no initialisation between sweeps.
+constexpr int ENC_BLOCK = 1024;      // samples of a row per workgroup of iaf_encode_back_kernel
+
+struct EncBackArgs {
+    const float *x, *Mt, *St;                                // [B][T]
+    float *z, *mean_tot, *scale_tot;                         // [B][T]; z read and written
+    int64_t T;
+    float z_max, tol;
+    int vec, nblk;
+    int* part;                                               // [2][B][nblk]
+    const unsigned* status;                                  // the sweep's range word (wn_codec.h)
+    int* counts;                                             // counts[1]: OR of the range words of the call's sweeps
+};
+
+__global__ __launch_bounds__(256) void iaf_encode_back_kernel(const EncBackArgs A) {
+    // an earlier sweep of this call met the stop condition (iaf_encode_reduce_kernel): z, the totals and the partials stay
+    // those of that sweep, so what the call hands out belongs to the sweep counts[2] names -- with tol > 0 a later sweep
+    // could move a sample by more than tol again
+    if (A.counts[2] != 0) return;
+    const int b = blockIdx.y;
+    const int64_t t0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4, row = (int64_t)b * A.T;
+    // a split-fp16 operand left the fp16 range in this sweep: Mt and St are not the reference's.  z stays as it is (the
+    // caller goes on from it on the fp32 form), nothing counts as converged, and the totals handed out are NaN
+    const bool bad = *A.status != 0u;
+    if (bad && b == 0 && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(reinterpret_cast<unsigned*>(A.counts) + 1, *A.status);
+    int fr = 0x7fffffff, nc = 0;
+    if (t0 < A.T) {
+        const int n = (int)(A.T - t0 < 4 ? A.T - t0 : 4);
+        float xv[4], mv[4], sv[4], zo[4], zn[4];
+        if (A.vec) {
+            const f4 a = *reinterpret_cast<const f4*>(A.x + row + t0), m = *reinterpret_cast<const f4*>(A.Mt + row + t0),
+                     s = *reinterpret_cast<const f4*>(A.St + row + t0), z = *reinterpret_cast<const f4*>(A.z + row + t0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { xv[e] = a[e]; mv[e] = m[e]; sv[e] = s[e]; zo[e] = z[e]; }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const bool in = e < n;
+                xv[e] = in ? A.x[row + t0 + e] : 0.f;
+                mv[e] = in ? A.Mt[row + t0 + e] : 0.f;
+                sv[e] = in ? A.St[row + t0 + e] : 1.f;
+                zo[e] = in ? A.z[row + t0 + e] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            sv[e] = fminf(sv[e], EXP_7);                     // parallel_wavenet.py:327
+            float v = (xv[e] - mv[e]) / sv[e];
+            if (!(fabsf(v) <= 3.0e38f)) v = 0.f;             // NaN or +-inf
+            if (e < n && fabsf(v) > A.z_max) { v = copysignf(A.z_max, v); ++nc; }
+            const bool moved = A.tol == 0.f ? __float_as_uint(v) != __float_as_uint(zo[e]) : !(fabsf(v - zo[e]) <= A.tol);
+            if (e < n && (moved || bad)) fr = min(fr, (int)(t0 + e));
+            zn[e] = v;
+            if (bad) mv[e] = sv[e] = __builtin_nanf("");
+        }
+        if (bad) nc = 0;
+        if (A.vec) {
+            if (!bad) *reinterpret_cast<f4*>(A.z + row + t0) = (f4){zn[0], zn[1], zn[2], zn[3]};
+            if (A.mean_tot) *reinterpret_cast<f4*>(A.mean_tot + row + t0) = (f4){mv[0], mv[1], mv[2], mv[3]};
+            if (A.scale_tot) *reinterpret_cast<f4*>(A.scale_tot + row + t0) = (f4){sv[0], sv[1], sv[2], sv[3]};
+        } else {
+            for (int e = 0; e < n; ++e) {
+                if (!bad) A.z[row + t0 + e] = zn[e];
+                if (A.mean_tot) A.mean_tot[row + t0 + e] = mv[e];
+                if (A.scale_tot) A.scale_tot[row + t0 + e] = sv[e];
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        fr = min(fr, __shfl_xor(fr, o));
+        nc += __shfl_xor(nc, o);
+    }
+    __shared__ int sh[2][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { sh[0][wave] = fr; sh[1][wave] = nc; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const size_t i = (size_t)b * A.nblk + blockIdx.x;
+        A.part[i] = min(min(sh[0][0], sh[0][1]), min(sh[0][2], sh[0][3]));
+        A.part[(size_t)gridDim.y * A.nblk + i] = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3];
+    }
+}
+
+// One workgroup: front[b] = min over the row's block minima (T where nothing moved), counts[0] = the sweep's clamp count,
+// counts[2] = the first sweep of the call (from 1) after which every front was T and nothing was clamped.  Wave w takes the
+// rows w, w + 4, ...; its lanes stride the row's partials.
+__global__ __launch_bounds__(256) void iaf_encode_reduce_kernel(const int* __restrict__ part, int B, int nblk, int T, int sweep,
+                                                                int* __restrict__ front, int* __restrict__ counts) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int nc = 0, open = 0;                                    // clamped elements / rows whose front is not T, of this wave's rows
+    for (int b = wave; b < B; b += 4) {
+        int fr = T;
+        for (int i = lane; i < nblk; i += 64) {
+            fr = min(fr, part[(size_t)b * nblk + i]);
+            nc += part[(size_t)B * nblk + (size_t)b * nblk + i];
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) fr = min(fr, __shfl_xor(fr, o));
+        if (lane == 0) front[b] = fr;
+        open += fr != T;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) nc += __shfl_xor(nc, o);
+    __shared__ int sh[2][4];
+    if (lane == 0) { sh[0][wave] = nc; sh[1][wave] = open; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int c = sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3];
+        counts[0] = c;
+        if (c == 0 && sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3] == 0 && counts[2] == 0) counts[2] = sweep + 1;
+    }
+}
+
+// log p(x) = log f(z) - log scale_tot (wn_iaf_latent_log_prob), one workgroup per row.  Evaluated in double and rounded
+// once; the row sum is taken as the distillation kernels take theirs (wn_distill.hip): double, each thread its quads in
+// order, a wave butterfly, then the waves in order.
+__global__ __launch_bounds__(256) void iaf_latent_log_prob_kernel(const float* __restrict__ z, const float* __restrict__ st,
+                                                                  int64_t T, int gauss, int vec, float* __restrict__ lp,
+                                                                  double* __restrict__ row_sums) {
+    const int64_t row = (int64_t)blockIdx.x * T;
+    double acc = 0.0;
+    for (int64_t t0 = (int64_t)threadIdx.x * 4; t0 < T; t0 += 1024) {
+        const int n = (int)(T - t0 < 4 ? T - t0 : 4);
+        float zv[4], sv[4], out[4];
+        if (vec) {
+            const f4 a = *reinterpret_cast<const f4*>(z + row + t0), s = *reinterpret_cast<const f4*>(st + row + t0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { zv[e] = a[e]; sv[e] = s[e]; }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                zv[e] = e < n ? z[row + t0 + e] : 0.f;
+                sv[e] = e < n ? st[row + t0 + e] : 1.f;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const double zd = (double)zv[e];
+            // Logistic(0,1): -z - 2 softplus(-z), softplus(y) = max(y, 0) + log1p(exp(-|y|)); Normal(0,1)
+            const double lf = gauss ? -0.5 * zd * zd - 0.9189385332046727 : -zd - 2.0 * (fmax(-zd, 0.0) + log1p(exp(-fabs(zd))));
+            out[e] = (float)(lf - log((double)sv[e]));
+            if (e < n) acc += (double)out[e];
+        }
+        if (lp) {
+            if (vec) *reinterpret_cast<f4*>(lp + row + t0) = (f4){out[0], out[1], out[2], out[3]};
+            else for (int e = 0; e < n; ++e) lp[row + t0 + e] = out[e];
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    __shared__ double sh[4];
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0 && row_sums) row_sums[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
 // ---------------- windowed generation (wn_iaf_generate_windows) ----------------
 // Row r of a window call is an ordinary row of T samples whose local sample t is sample t_origin + t of utterance b.
 // Prologue: iaf_prologue_kernel's two jobs with the noise taken at ABSOLUTE positions -- Philox counter (t_origin / 4 + i4, b),
@@ -332,6 +494,9 @@ struct IafCall {
     bool prof_on, parts_on;
     int pmask;                         // parts the call runs: a restriction exists only inside a parts session (wn_profile_parts_only)
     bool no_pair, no_headfuse;         // WN_NO_PAIR / WN_NO_HEADFUSE (cross-form tests): no two-layer launches / no head in a last layer
+    // wn_iaf_encode: the body leaves out the upsampler and the conditioning GEMM of a SHARED deconv stack -- enc and C in the
+    // workspace are those of an earlier sweep of the same encode.  Generate calls never set it.
+    bool skip_front;
     // measurement state
     int part_now = -2;
     bool prof_open = false;
@@ -631,7 +796,7 @@ IafCall iaf_call_fill(wn_handle* h, int form, int rows, int frames, int form_row
 int iaf_call_body(IafCall& c) {
     wn_handle* h = c.h;
     const wn_config& cfg = h->cfg;
-    if (cfg.share_deconv)
+    if (cfg.share_deconv && !c.skip_front)
         if (int rc = iaf_upsample_cond(c, 0, 0, h->cond_rows, c.blob_u(c.use_groups ? h->order_all_off : h->order_id_off),
                                        c.use_groups ? h->n_nat_all : h->cond_rows))
             return rc;
@@ -710,6 +875,86 @@ extern "C" int wn_iaf_generate_form(wn_handle* h, int form, const float* mel, in
             WN_HIP(h, hipMemcpyAsync(rand_out, x0, nn * sizeof(float), hipMemcpyDeviceToDevice, c.st));
     }
     return iaf_call_close(c);
+}
+
+// ---------------------------------------------------------------------------
+// The inverse by fixed-point sweeps: a sweep is a generate call's prologue with noise = z and its body,
+// with iaf_encode_back_kernel as the back.  Behind the generate workspace of the call's form: the back kernel's partials.
+static int enc_blocks(int64_t T) { return (int)((T + ENC_BLOCK - 1) / ENC_BLOCK); }
+
+static const char* const ENC_NOT_FINALIZED = "call wn_finalize first";
+
+static const char* iaf_encode_refusal(const wn_handle* h, int form, int B, int F) {
+    if (!h) return "null handle";
+    if (form < WN_FORM_DEFAULT || form > WN_FORM_F16X3_FUSED) return "unknown form";
+    if (h->cfg.kind != WN_KIND_STUDENT) return "handle is not a ParallelWavenet student (a teacher has no latent to encode to)";
+    if (h->cfg.use_mu_law) return "mu-law students are not supported (their audio is not the flow's output x)";
+    if (!h->finalized) return ENC_NOT_FINALIZED;
+    if (B < 1 || F < 1) return "B and F must be >= 1";
+    if (B > 65535) return "at most 65535 rows per call";
+    if (wn_iaf_length(h, F) == 0) return "fewer frames than one max-dilation block";
+    if ((int64_t)F * h->frame_shift > WN_MAX_ROW_SAMPLES)
+        return "more than 2,000,000 samples (125 s) per row: the limit of the 32-bit row offsets";
+    if ((int64_t)B * wn_iaf_length(h, F) / 64 > 0x7fffffff) return "batch too large";
+    return nullptr;
+}
+
+extern "C" size_t wn_iaf_encode_workspace_bytes(const wn_handle* h, int form, int B, int F) {
+    if (iaf_encode_refusal(h, form, B, F)) return 0;
+    return align_up(wn_iaf_workspace_bytes(h, B, F, form), 256) +
+           align_up((size_t)2 * B * enc_blocks(wn_iaf_length(h, F)) * sizeof(int), 256);
+}
+
+extern "C" int wn_iaf_encode(wn_handle* h, int form, const float* mel, int B, int F, const float* x, float* z, int n_sweeps,
+                             float z_max, float tol, int first, float* mean_tot, float* scale_tot, int32_t* front,
+                             int32_t* counts, void* ws, size_t ws_bytes, void* stream) {
+    if (const char* why = iaf_encode_refusal(h, form, B, F))
+        return wn_fail(h, why == ENC_NOT_FINALIZED ? WN_ESTATE : WN_EINVAL, "wn_iaf_encode: %s", why);
+    if (n_sweeps < 1) return wn_fail(h, WN_EINVAL, "wn_iaf_encode: n_sweeps must be >= 1, got %d", n_sweeps);
+    if (!(z_max > 0.f)) return wn_fail(h, WN_EINVAL, "wn_iaf_encode: z_max must be > 0, got %g", (double)z_max);
+    if (!(tol >= 0.f)) return wn_fail(h, WN_EINVAL, "wn_iaf_encode: tol must be >= 0, got %g", (double)tol);
+    if (!mel || !x || !z || !front || !counts || !ws)
+        return wn_fail(h, WN_EINVAL, "wn_iaf_encode: null mel/x/z/front/counts/workspace");
+    const size_t need = wn_iaf_encode_workspace_bytes(h, form, B, F);
+    if (ws_bytes < need) return wn_fail(h, WN_ENOMEM, "wn_iaf_encode: workspace %zu < %zu bytes", ws_bytes, need);
+    const WnWork work(h);
+    IafCall c = iaf_call_fill(h, form, B, F, B, mel, ws, stream);
+    const IafLayout& L = c.L;
+    EncBackArgs A{};
+    A.x = x; A.Mt = c.Mt; A.St = c.St; A.z = z; A.mean_tot = mean_tot; A.scale_tot = scale_tot;
+    A.T = L.T; A.z_max = z_max; A.tol = tol; A.nblk = enc_blocks(L.T);
+    A.part = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + align_up(wn_iaf_workspace_bytes(h, B, F, form), 256));
+    A.status = c.status; A.counts = counts;
+    uintptr_t bits = (uintptr_t)(L.T & 3);
+    for (const void* p : {(const void*)x, (const void*)z, (const void*)mean_tot, (const void*)scale_tot})
+        bits |= reinterpret_cast<uintptr_t>(p) & 15;
+    A.vec = bits == 0;
+    WN_HIP(h, hipMemsetAsync(counts, 0, 4 * sizeof(int32_t), c.st));
+    for (int s = 0; s < n_sweeps; ++s) {
+        c.skip_front = h->cfg.share_deconv && (s > 0 || !first);
+        c.x = c.xbuf0;                                      // run_groups may have left the other copy in force
+        if (int rc = c.part(0)) return rc;
+        iaf_prologue(c, z, 0);
+        if (int rc = iaf_call_body(c)) return rc;
+        hipLaunchKernelGGL(iaf_encode_back_kernel, dim3((unsigned)A.nblk, (unsigned)B), dim3(256), 0, c.st, A);
+        hipLaunchKernelGGL(iaf_encode_reduce_kernel, dim3(1), dim3(256), 0, c.st, A.part, B, A.nblk, (int)L.T, s, front, counts);
+    }
+    return iaf_call_close(c);
+}
+
+extern "C" int wn_iaf_latent_log_prob(wn_handle* h, const float* z, const float* scale_tot, int B, int64_t T, float* log_prob,
+                                      double* row_sums, void* stream) {
+    if (!h) return wn_fail(nullptr, WN_EINVAL, "wn_iaf_latent_log_prob: null handle");
+    if (h->cfg.kind != WN_KIND_STUDENT)
+        return wn_fail(h, WN_EINVAL, "wn_iaf_latent_log_prob: handle is not a ParallelWavenet student");
+    if (B < 1 || T < 1) return wn_fail(h, WN_EINVAL, "wn_iaf_latent_log_prob: B and T must be >= 1");
+    if (!z || !scale_tot) return wn_fail(h, WN_EINVAL, "wn_iaf_latent_log_prob: null z/scale_tot");
+    uintptr_t bits = (uintptr_t)(T & 3);
+    for (const void* p : {(const void*)z, (const void*)scale_tot, (const void*)log_prob}) bits |= reinterpret_cast<uintptr_t>(p) & 15;
+    hipLaunchKernelGGL(iaf_latent_log_prob_kernel, dim3((unsigned)B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), z,
+                       scale_tot, T, h->cfg.loss_type == WN_LOSS_GAUSS ? 1 : 0, bits == 0 ? 1 : 0, log_prob, row_sums);
+    WN_HIP(h, hipGetLastError());
+    return WN_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -38,6 +38,7 @@ class Engine(object):
         self._ar_stream = None
         self._ar_groups = None              # per-group streams / queue states of ar_generate(streams=G)
         self._last_ws = None
+        self._enc_ws = None               # iaf_encode's own workspace: the conditioning term lives there between its C calls
         self._train_frames = {}           # tape address -> mel frames of the training tapes written through this handle
         self.range_fallbacks = 0          # calls re-run on the fp32 form because they left the fp16 range
         self._finalized = False
@@ -55,7 +56,7 @@ class Engine(object):
     # ---- lifecycle ----
     def close(self):
         """Destroy the C handle (the owner) / drop this caller's workspace (a fork: the handle belongs to its parent)."""
-        self._ws = self._last_ws = None
+        self._ws = self._last_ws = self._enc_ws = None
         if self._is_fork:
             return
         if self._h:
@@ -74,7 +75,7 @@ class Engine(object):
             raise RuntimeError('fork() needs a finalized engine (load_weights first)')
         f = copy.copy(self)                 # same _hbox / _shared objects, same hparams
         f._is_fork = True
-        f._ws = f._last_ws = f._ar_stream = None
+        f._ws = f._last_ws = f._enc_ws = f._ar_stream = None
         f._ar_groups = None
         f.range_fallbacks = 0
         return f
@@ -143,7 +144,7 @@ class Engine(object):
         return torch.as_tensor(np.ascontiguousarray(x), dtype=dtype).to(self.device)
 
     # ---- IAF path ----
-    def iaf_generate(self, mel, noise=None, seed=0, want=('wav',), check_range=True):
+    def iaf_generate(self, mel, noise=None, seed=0, want=('wav',), check_range=True, form=None):
         """ParallelWavenet.feed_forward + _clip_quant_scale.  mel [B,F,n_mel].
         Returns a dict of device tensors for the names in `want` out of
         wav, idx, x, mean_tot, scale_tot, rand_input.
@@ -155,7 +156,8 @@ class Engine(object):
         reference's fp32 behaviour; `self.range_fallbacks` counts those re-runs.  check_range=False keeps the call
         asynchronous (serving / timing loops): call check_range() afterwards -- it raises if ANY call since the last
         check overflowed (the library accumulates the status words in the workspace; each such call NaN-poisoned its
-        own outputs)."""
+        own outputs).  form: one of _lib.FORM_* to name the arithmetic of the call (None: the engine's default), e.g. the
+        form an iaf_encode reports."""
         mel = self._dev(mel)
         if mel.dim() != 3 or mel.shape[2] != self.n_mel:
             raise ValueError('mel must be [batch, frames, {}], got {}'.format(self.n_mel, tuple(mel.shape)))
@@ -166,7 +168,7 @@ class Engine(object):
             raise ValueError('noise must be [{}, {}], got {}'.format(B, T, tuple(noise.shape)))
         out = self._window_outputs(B, T, want)
         with torch.cuda.device(self.device):
-            form = _lib.FORM_DEFAULT
+            form = _lib.FORM_DEFAULT if form is None else int(form)
             try:
                 ws = self._workspace(self.lib.wn_workspace_bytes(self._h, B, F))
             except MemoryError:
@@ -182,7 +184,7 @@ class Engine(object):
                     self._h, f, _ptr(mel), B, F, _ptr(noise), ctypes.c_uint64(int(seed)), _ptr(out['wav']), _ptr(out['idx']),
                     _ptr(out['x']), _ptr(out['mean_tot']), _ptr(out['scale_tot']), _ptr(out['rand_input']), _ptr(ws),
                     ws.numel(), self._stream()))
-            self._run_ranged(run, form, ws, check_range and not self.precision.startswith('f32') and T > 0)
+            self._run_ranged(run, form, ws, check_range and not self.precision.startswith('f32') and form != _lib.FORM_F32 and T > 0)
         return {k: v for k, v in out.items() if k in want}
 
     def _window_outputs(self, B, T, want):
@@ -207,6 +209,90 @@ class Engine(object):
             self._check(self.lib.wn_iaf_range_reset(self._h, _ptr(ws), self._stream()))
         else:
             self._check(rc)
+
+    # ---- the inverse of the student ----
+    def iaf_encode(self, x, mel, z_init=None, max_sweeps=None, tol=0.0, check_every=8, z_max=64.0, want=('z',)):
+        """The latent z with iaf_generate(mel, noise=z)['x'] == x, by fixed-point sweeps z <- (x - mean_tot(z)) / scale_tot(z)
+        (wn_iaf_encode): scale_tot[t] and mean_tot[t] depend on z[<t] only, so k sweeps make the first k samples exact and T
+        sweeps the whole row.  x [B,T], mel [B,F,n_mel]; starts from z_init, or from zeros.
+
+        `check_every` sweeps are enqueued per C call; after each call front, the clamp count and the range word come back in
+        ONE read-back.  The encode stops when every row's front is T (the last sweep changed no sample by more than tol;
+        tol = 0: no bit) with nothing clamped to +-z_max, or at max_sweeps (default T).  All sweeps run in one arithmetic
+        form: when a sweep leaves the fp16 range the encode restarts from the current iterate on the fp32 form, stays
+        there, and counts into `range_fallbacks`.  The workspace is the encode's own, so the conditioning term of a shared
+        deconv stack is computed once per encode.
+
+        Returns the names in `want` out of z, mean_tot, scale_tot, log_prob (log p(x[t]), with 'log_prob_sums', float64
+        [B]), plus 'sweeps' (int: sweeps until the stop condition held, or all that ran), 'front' ([B] int32), 'converged'
+        ([B] bool, front == T), 'clamped' (int, of the last sweep) and 'form' (the _lib.FORM_* the sweeps ran in).
+        mean_tot / scale_tot belong to the last sweep's input iterate: to z itself once it has converged.  Sweeps a C call
+        has enqueued past the one where the stop condition held change nothing: z, the totals and front are that sweep's."""
+        mel = self._dev(mel)
+        if mel.dim() != 3 or mel.shape[2] != self.n_mel:
+            raise ValueError('mel must be [batch, frames, {}], got {}'.format(self.n_mel, tuple(mel.shape)))
+        B, F = int(mel.shape[0]), int(mel.shape[1])
+        f32 = self.precision.startswith('f32')
+        form = _lib.FORM_F32 if f32 else _lib.FORM_DEFAULT
+        with torch.cuda.device(self.device):
+            nbytes = int(self.lib.wn_iaf_encode_workspace_bytes(self._h, form, B, F))
+            if nbytes == 0:                # a handle or a shape the call refuses: the call itself says why
+                self._check(self.lib.wn_iaf_encode(self._h, form, None, B, F, None, None, 1, 1.0, 0.0, 1, None, None, None, None,
+                                                   None, 0, self._stream()))
+        T = self.iaf_length(F)
+        x = self._dev(x)
+        if tuple(x.shape) != (B, T):
+            raise ValueError('x must be [{}, {}], got {}'.format(B, T, tuple(x.shape)))
+        if z_init is not None and tuple(z_init.shape) != (B, T):
+            raise ValueError('z_init must be [{}, {}], got {}'.format(B, T, tuple(z_init.shape)))
+        if check_every < 1:
+            raise ValueError('check_every must be >= 1, got {}'.format(check_every))
+        max_sweeps = T if max_sweeps is None else int(max_sweeps)
+        z = torch.zeros((B, T), dtype=torch.float32, device=self.device) if z_init is None else self._dev(z_init).clone()
+        new = lambda: torch.empty((B, T), dtype=torch.float32, device=self.device)
+        mean_tot = new() if 'mean_tot' in want else None
+        scale_tot = new() if ('scale_tot' in want or 'log_prob' in want) else None
+        meta = torch.zeros(B + 4, dtype=torch.int32, device=self.device)          # front [B], then counts [4]
+        sweeps, first = 0, 1
+        with torch.cuda.device(self.device):
+            if self._enc_ws is None or self._enc_ws.numel() < nbytes:
+                self._enc_ws = None
+                self._enc_ws = torch.empty(max(nbytes, 64), dtype=torch.uint8, device=self.device)
+            ws = self._enc_ws
+            while True:
+                n = min(int(check_every), max_sweeps - sweeps)
+                self._check(self.lib.wn_iaf_encode(
+                    self._h, form, _ptr(mel), B, F, _ptr(x), _ptr(z), n, float(z_max), float(tol), first, _ptr(mean_tot),
+                    _ptr(scale_tot), _ptr(meta), ctypes.c_void_p(meta.data_ptr() + 4 * B), _ptr(ws), ws.numel(), self._stream()))
+                first = 0
+                m = meta.cpu()
+                front, clamped, flag, done_at = m[:B], int(m[B]), int(m[B + 1]), int(m[B + 2])
+                if flag and form != _lib.FORM_F32:
+                    self.range_fallbacks += 1
+                    form, first = _lib.FORM_F32, 1           # z is the iterate the faulted sweep started from
+                    continue
+                sweeps += done_at if done_at else n
+                if done_at or sweeps >= max_sweeps:
+                    break
+            out = {'z': z, 'mean_tot': mean_tot, 'scale_tot': scale_tot}
+            if 'log_prob' in want:
+                out['log_prob'], out['log_prob_sums'] = self.iaf_latent_log_prob(z, scale_tot)
+        ret = {k: v for k, v in out.items() if k in want or (k == 'log_prob_sums' and 'log_prob' in want)}
+        ret.update({'sweeps': sweeps, 'front': meta[:B].clone(), 'converged': meta[:B] == T, 'clamped': clamped, 'form': form})
+        return ret
+
+    def iaf_latent_log_prob(self, z, scale_tot):
+        """wn_iaf_latent_log_prob: log p(x[t]) = log f(z[t]) - log scale_tot[t] of the student's (untruncated) density,
+        [B,T] float32, and its row sums, [B] float64 summed in a fixed order."""
+        z, scale_tot = self._dev(z), self._dev(scale_tot)
+        if z.dim() != 2 or z.shape != scale_tot.shape:
+            raise ValueError('z and scale_tot must be [batch, T] alike, got {} and {}'.format(tuple(z.shape), tuple(scale_tot.shape)))
+        lp = torch.empty_like(z)
+        sums = torch.empty(z.shape[0], dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.wn_iaf_latent_log_prob(self._h, _ptr(z), _ptr(scale_tot), int(z.shape[0]), int(z.shape[1]),
+                                                        _ptr(lp), _ptr(sums), self._stream()))
+        return lp, sums
 
     # ---- windowed IAF generation (DESIGN.md 21) ----
     ONE_SHOT_MAX_SAMPLES = 2000000         # twin of WN_MAX_ROW_SAMPLES (csrc/wn_internal.h): wn_iaf_generate refuses longer utterances

@@ -82,6 +82,24 @@ class ParallelWavenet(object):
         out['log_scale_tot'] = torch.log(out['scale_tot'])
         return {k: out[k] for k in ('x', 'mean_tot', 'scale_tot', 'log_scale_tot', 'rand_input')}
 
+    def encode(self, inputs, **kw):
+        """The inverse of feed_forward.  inputs: 'mel' [B,F,80] and the audio as 'x' (feed_forward's key)
+        or 'wav' [B,T], T = the student's length for F frames.  Returns z with feed_forward(noise=z)['x'] == x,
+        log_scale_tot, log_probs (log p(x[t]) under the student), sweeps and converged ([B] bool).  Keyword arguments go
+        to Engine.iaf_encode (z_init, max_sweeps, tol, check_every, z_max)."""
+        x = inputs['x'] if 'x' in inputs else inputs['wav']
+        r = self.engine.iaf_encode(x, inputs['mel'], want=('z', 'scale_tot', 'log_prob'), **kw)
+        return {'z': r['z'], 'log_scale_tot': torch.log(r['scale_tot']), 'log_probs': r['log_prob'],
+                'log_prob_sums': r['log_prob_sums'], 'sweeps': r['sweeps'], 'converged': r['converged']}
+
+    def log_prob(self, inputs, **kw):
+        """The student's log-likelihood of real audio: {'log_probs': [B,T], 'loss': -mean log p} (a 0-d float64 device
+        tensor, from the kernel's float64 row sums).  Needs no teacher.  Raises when a row did not converge."""
+        r = self.encode(inputs, **kw)
+        if not bool(r['converged'].all()):
+            raise RuntimeError('log_prob: the inverse did not converge in {} sweeps'.format(r['sweeps']))
+        return {'log_probs': r['log_probs'], 'loss': -(r['log_prob_sums'].sum() / r['log_probs'].numel())}
+
     def _clip_quant_scale(self, x, quant_chann=None, use_mu_law=None):
         wav, _ = self.engine.clip_quant(x)
         return wav
