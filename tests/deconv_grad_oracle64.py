@@ -3,7 +3,9 @@ conv_transpose1d with padding = (K - S) / 2, then the activation, so that torch.
 trans_conv_j/kernel and trans_conv_j/bias.  tests/test_deconv_grad_oracle.py pins it on the CPU (forward against
 oracle.wavenet_np.deconv_stack, gradients against central differences); tests/test_gpu_deconv_backward.py holds the engine
 to it.  Also the tie handling of leaky-relu, which works on this oracle alone: row seeds whose hidden pre-activations keep
-clear of zero, and a mask of the last layer's near-zero pre-activations.
+clear of zero, and a mask of the last layer's near-zero pre-activations.  relu (masked.get_upsample_act's third name) goes
+by the same tie rules on its pre-activations; an unknown name raises.  Stacks of any number of layers are served, except by
+the projection of hidden ties, which stays two-layer.
 
 pick_rows searches until it finds a clear seed.  One shape of the GPU tests has none in practice: a hidden tensor of 256
 channels x 270 frames has 69 120 values, and a band of 1e-4 of the largest magnitude around zero catches 15 to 28 of them
@@ -37,8 +39,20 @@ def weights64(w, n_layers, prefix=''):
     return {k: torch.as_tensor(np.asarray(w[k], np.float64)) for k in names(n_layers, prefix)}
 
 
+def activation(z, act):
+    """masked.get_upsample_act on a float64 tensor; torch.relu has no gradient at exactly 0"""
+    if act == 'leaky_relu':
+        return TF.leaky_relu(z, 0.4)
+    if act == 'relu':
+        return torch.relu(z)
+    if act == 'tanh':
+        return torch.tanh(z)
+    raise ValueError('Unsupported activation function for upsample layer: {!r}'.format(act))
+
+
 def stack_ff(mel, w, deconv_config, act, prefix=''):
-    """mel [B,F,n_mel] float64, w {name: float64 tensor, TF shapes} -> ([pre-activation z_j [B,C,T_j]], enc [B,TE,Cd])"""
+    """mel [B,F,n_mel] float64, w {name: float64 tensor, TF shapes} -> ([pre-activation z_j [B,C,T_j]], enc [B,TE,Cd]);
+    a stack of any number of layers"""
     p = prefix + '/' if prefix else ''
     h = torch.as_tensor(mel, dtype=torch.float64).transpose(1, 2)
     pre = []
@@ -47,7 +61,7 @@ def stack_ff(mel, w, deconv_config, act, prefix=''):
         assert W.shape[1] == fl and (fl - s) % 2 == 0
         z = TF.conv_transpose1d(h, W[0].permute(2, 1, 0).contiguous(), b, stride=s, padding=(fl - s) // 2)
         pre.append(z)
-        h = TF.leaky_relu(z, 0.4) if act == 'leaky_relu' else torch.tanh(z)
+        h = activation(z, act)
     return pre, h.transpose(1, 2)
 
 
@@ -65,8 +79,9 @@ def near(z):
     return z.abs() <= BAND * z.abs().amax(dim=(1, 2), keepdim=True)
 
 
-def hidden_ties(mels, w, deconv_config, prefix=''):
-    """per row of mels [n,F,n_mel]: the number of near ties in the hidden layers (every layer but the last)"""
+def hidden_ties(mels, w, deconv_config, prefix='', act='leaky_relu'):
+    """per row of mels [n,F,n_mel]: the number of near ties in the hidden layers (every layer but the last; none in a stack
+    of one layer) under the activation `act` between them"""
     p = prefix + '/' if prefix else ''
     h = torch.as_tensor(mels, dtype=torch.float64).transpose(1, 2)
     n = torch.zeros(h.shape[0], dtype=torch.int64)
@@ -74,7 +89,7 @@ def hidden_ties(mels, w, deconv_config, prefix=''):
         W, b = w['{}trans_conv_{:d}/kernel'.format(p, j + 1)], w['{}trans_conv_{:d}/bias'.format(p, j + 1)]
         z = TF.conv_transpose1d(h, W[0].permute(2, 1, 0).contiguous(), b, stride=s, padding=(fl - s) // 2)
         n += near(z).sum(dim=(1, 2))
-        h = TF.leaky_relu(z, 0.4)
+        h = activation(z, act)
     return n.tolist()
 
 
@@ -85,8 +100,9 @@ def _mel_row(seed, F, n_mel):
 def pick_rows(B, F, w, deconv_config, act, prefix='', n_mel=80):
     """(mel [B,F,n_mel] float32, seeds): row i is np.random.RandomState(seed).uniform(0, 1, [F, n_mel]) of the first seed from
     FIRST_SEED upward (after row i - 1's) whose hidden pre-activations have no near tie.  The search goes on until it finds
-    one (SEARCH_LIMIT seeds at the most, then it fails).  tanh has no ties: consecutive seeds"""
-    if act != 'leaky_relu':
+    one (SEARCH_LIMIT seeds at the most, then it fails).  leaky_relu and relu search; tanh has no ties: consecutive seeds"""
+    activation(torch.zeros(1, dtype=torch.float64), act)          # raises on an unknown name
+    if act == 'tanh':
         seeds = tuple(range(FIRST_SEED, FIRST_SEED + B))
         return np.stack([_mel_row(s, F, n_mel) for s in seeds]), seeds
     rows, seeds, seed = [], [], FIRST_SEED
@@ -94,7 +110,7 @@ def pick_rows(B, F, w, deconv_config, act, prefix='', n_mel=80):
         assert seed < FIRST_SEED + SEARCH_LIMIT, 'no seed without a hidden near tie'
         cand = list(range(seed, seed + BATCH))
         mels = np.stack([_mel_row(s, F, n_mel) for s in cand])
-        ties = hidden_ties(mels, w, deconv_config, prefix)
+        ties = hidden_ties(mels, w, deconv_config, prefix, act)
         clear = [i for i, n in enumerate(ties) if n == 0]
         if not clear:
             seed += BATCH
@@ -155,8 +171,9 @@ def mask_last(g, mel, w, deconv_config, act, prefix='', project=False):
     """g [B,TE,Cd] with the elements at near ties of the LAST layer's pre-activation set to zero -> (g float32, number zeroed,
     hidden ties).  Asserts that the zeroed share is within MAX_ZEROED and that no hidden layer has a near tie -- unless
     project=True (rows of pick_rows_fewest): then g also loses its component that reaches a hidden near tie"""
-    if act != 'leaky_relu':
+    if act == 'tanh':
         return g, 0, 0
+    assert act == 'leaky_relu' or not project, 'hidden ties are projected out under leaky-relu only'
     pre, _ = stack_ff(mel, w, deconv_config, act, prefix)
     m = near(pre[-1]).transpose(1, 2)
     n = int(m.sum())
