@@ -181,6 +181,16 @@ WN_API size_t wn_workspace_bytes(const wn_handle* h, int B, int F);
 WN_API int wn_deconv(wn_handle* h, const char* scope, const float* mel, int B, int F,
               float* enc, void* ws, size_t ws_bytes, void* stream);
 
+/* Which kernels the upsampler stack `scope` runs for batch B and F frames, one entry per layer in order, joined by ", ":
+ * the GEMM form -- front (deconv_front_kernel), pg (deconv_pg_kernel), hs<T> (deconv_mfma_hs_kernel<TAPS>), h<false|true>
+ * (deconv_mfma_h_kernel<G4IN>), fa (the frame-axis fp32 GEMM), mfma (deconv_mfma_kernel) -- then, where a weave launch
+ * follows it, il (deconv_interleave_kernel) or g4<S> (deconv_interleave_g4_kernel<S>): "front, pg", "h<false> g4<10>, hs<4> il".
+ * split_out 0: fp32 rows out, as wn_deconv; 1: G4 words out, as the generate, teacher and training calls ask for.
+ * precision: -1 = the handle's, else a value of wn_config.precision (the arithmetic of one call, as WN_FORM_F32 selects it).
+ * Launches nothing and needs no workspace.  WN_ESTATE / WN_ENOENT as wn_deconv; WN_EINVAL for a null or short buffer. */
+WN_API int wn_deconv_forms(const wn_handle* h, const char* scope, int B, int F, int split_out, int precision, char* buf,
+                           size_t cap);
+
 /* The single sess.run of parallelgen.synthesis (parallelgen.py:43-45):
  * ParallelWavenet.feed_forward (parallel_wavenet.py:289-345) followed by
  * _clip_quant_scale (:347-359).

@@ -18,7 +18,7 @@ FORM_DEFAULT, FORM_F16X3, FORM_F32, FORM_F16X3_FUSED = -1, 0, 1, 2
 
 # every symbol include/wnhip.h declares
 SYMBOLS = ['wn_abi_version', 'wn_create', 'wn_set_weight', 'wn_finalize', 'wn_iaf_length',
-           'wn_ar_length', 'wn_workspace_bytes', 'wn_deconv', 'wn_iaf_generate', 'wn_iaf_generate_form',
+           'wn_ar_length', 'wn_workspace_bytes', 'wn_deconv', 'wn_deconv_forms', 'wn_iaf_generate', 'wn_iaf_generate_form',
            'wn_iaf_workspace_bytes_form', 'wn_iaf_range_status', 'wn_iaf_range_reset',
            'wn_iaf_range_status_since_reset', 'wn_clip_quant',
            'wn_ar_n_rand', 'wn_ar_state_bytes', 'wn_ar_reset', 'wn_ar_step', 'wn_ar_generate', 'wn_ar_set_graph', 'wn_ar_cond_vars', 'wn_ar_cond_vars_floats',
@@ -84,6 +84,7 @@ def load():
     lib.wn_workspace_bytes.argtypes = [vp, i32, i32]
     lib.wn_workspace_bytes.restype = sz
     lib.wn_deconv.argtypes = [vp, c.c_char_p, vp, i32, i32, vp, vp, sz, vp]
+    lib.wn_deconv_forms.argtypes = [vp, c.c_char_p, i32, i32, i32, i32, c.c_char_p, sz]
     lib.wn_iaf_generate.argtypes = [vp, vp, i32, i32, vp, u64, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.wn_iaf_generate_form.argtypes = [vp, i32, vp, i32, i32, vp, u64, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.wn_iaf_workspace_bytes_form.argtypes = [vp, i32, i32, i32]

@@ -1031,206 +1031,232 @@ int wn_deconv_set_attrs(wn_handle* h) {
     return wn_iaf_f_set_attrs(h);       // the fp32 GEMMs with the activation tile in LDS (students and fp32 teachers' upsampler)
 }
 
-// phase-major GEMM output of the largest layer: [B][S][cout][Qp]
-static size_t dc_phase_floats(const wn_handle* h, int B, int F) {
+// The scratch area of one call: channel-major mel, every hidden layer's output rows, then the phase-major GEMM output of
+// the largest layer [B][S][cout][Qp], which ENDS at the (256-byte aligned) end of the area
+static DeconvLayout dc_layout(const wn_handle* h, int B, int F) {
     const wn_config& c = h->cfg;
-    size_t mx = 0;
+    DeconvLayout at{};
+    size_t fl = (size_t)B * c.n_mel * dc_row_stride(F), phase = 0;
     int64_t L = F;
     for (int j = 0; j < c.n_deconv; ++j) {
         const size_t Qp = (size_t)((L + 5 + DC_QW - 1) / DC_QW) * DC_QW;   // Q <= L + 5 for <= 8 taps
-        mx = std::max(mx, (size_t)B * c.deconv_stride[j] * c.deconv_width * Qp);
+        phase = std::max(phase, (size_t)B * c.deconv_stride[j] * c.deconv_width * Qp);
         L *= c.deconv_stride[j];
+        if (j + 1 < c.n_deconv) {
+            at.hidden[j] = fl;
+            fl += (size_t)B * c.deconv_width * dc_row_stride((int)L);
+        }
     }
-    return mx;
+    at.bytes = align_up((fl + phase) * sizeof(float), 256);
+    at.phase = at.bytes / sizeof(float) - phase;
+    return at;
 }
 
-// scratch: channel-major mel + every intermediate layer output + the phase-major buffer
-size_t wn_deconv_scratch_bytes(const wn_handle* h, int B, int F) {
-    const wn_config& c = h->cfg;
-    size_t fl = (size_t)B * c.n_mel * dc_row_stride(F);
-    int64_t L = F;
-    for (int j = 0; j + 1 < c.n_deconv; ++j) {
-        L *= c.deconv_stride[j];
-        fl += (size_t)B * c.deconv_width * dc_row_stride((int)L);
-    }
-    fl += dc_phase_floats(h, B, F);
-    return align_up(fl * sizeof(float), 256);
-}
+size_t wn_deconv_scratch_bytes(const wn_handle* h, int B, int F) { return dc_layout(h, B, F).bytes; }
 
 const void* wn_deconv_hidden(const wn_handle* h, int B, int F, int j, const void* scratch, int64_t* ys, int* yoff) {
-    const wn_config& c = h->cfg;
-    const float* at = reinterpret_cast<const float*>(scratch) + (size_t)B * c.n_mel * dc_row_stride(F);
     int L = F;
-    for (int i = 0; i < j; ++i) {
-        L *= c.deconv_stride[i];
-        at += (size_t)B * c.deconv_width * dc_row_stride(L);
-    }
-    *ys = dc_row_stride(L * c.deconv_stride[j]);
+    for (int i = 0; i <= j; ++i) L *= h->cfg.deconv_stride[i];
+    *ys = dc_row_stride(L);
     *yoff = DC_XOFF;
-    return at;
+    return reinterpret_cast<const float*>(scratch) + dc_layout(h, B, F).hidden[j];
+}
+
+// Which kernels one call of stack `si` launches, layer by layer, and where every layer reads and writes.  Every choice among
+// the GEMM and weave forms is made here: wn_run_deconv launches what the plan says and wn_deconv_forms prints it.
+// split_out: the caller consumes the last layer as G4 words; prec: WN_PREC_* of this call, -1 = the handle's
+static DeconvPlan dc_plan(const wn_handle* h, int si, int B, int F, bool split_out, int prec) {
+    const wn_config& c = h->cfg;
+    const DeconvStackPack& sp = h->stacks[si];
+    DeconvPlan P{};
+    P.at = dc_layout(h, B, F);
+    P.n = c.n_deconv;
+    // split-fp16 GEMMs when the call runs in f16x3 mode and every layer's shape supports them
+    bool h_gemm = (prec < 0 ? c.precision : prec) == WN_PREC_F16X3;
+    for (const DeconvLayerPack& lp : sp.layers) h_gemm = h_gemm && lp.w_off_h != 0;
+    const DeconvLayerPack& l0 = sp.layers.front();
+    const DeconvLayerPack& ll = sp.layers.back();
+    // deconv_pg_kernel: the last layer in one launch, from the G4 words of a split-fp16 layer in front of it to G4 words
+    // (h->dc_no_pg: WN_DC_NO_PG=1 at wn_create keeps the phase-major GEMM + interleave of rounds 1-4: A/B runs, cross-form test)
+    const bool pg_last = h_gemm && c.n_deconv >= 2 && split_out && ll.w_off_pg && !h->dc_no_pg;
+    // deconv_front_kernel: the first layer in one launch where it is 4 taps x 80 mel channels -> 256 channels and the stack
+    // ends in deconv_pg_kernel; every other stack keeps the three launches
+    const bool front = pg_last && l0.taps == 4 && l0.cin == DF_CIN && l0.cout == 256 &&
+                       (int64_t)64 * 16 * dc_row_stride(F * l0.S) < ((int64_t)1 << 31);      // (32-bit store offsets)
+    P.entry = front ? DC_ENTRY_NONE : h_gemm ? DC_ENTRY_SPLIT : DC_ENTRY_CM;
+    int L = F;
+    for (int j = 0; j < P.n; ++j) {
+        const DeconvLayerPack& lp = sp.layers[j];
+        DeconvPlanLayer& pl = P.layer[j];
+        const bool last = (j + 1 == P.n);
+        pl.L = L;
+        pl.Lout = L * lp.S;
+        pl.x_off = j ? P.at.hidden[j - 1] : P.at.mel;
+        pl.xs = dc_row_stride(L);
+        // the fp16 GEMM of a layer behind another reads G4 words (deconv_width is a multiple of 64: validate, wn_host.cpp)
+        pl.x_g4 = h_gemm && j > 0;
+        pl.y_enc = last;
+        if (!last) {
+            pl.y_off = P.at.hidden[j];
+            pl.ys = dc_row_stride(pl.Lout);
+            pl.yoff = DC_XOFF;
+        }
+        // intermediate outputs feed the next GEMM; the last one is split (G4) only when the caller consumes the split layout
+        const bool y_g4 = last ? split_out : h_gemm;
+        // zero pads of an intermediate output: the G4 forms write them themselves, the fp32 rows get a memset
+        pl.zero_pads = !last && !y_g4;
+        const int Q = L + (lp.pL + lp.S - 1) / lp.S + 1;      // phase columns q = (t + pL) / S
+        pl.cols = ((Q + DC_QW - 1) / DC_QW) * DC_QW;
+        pl.weave_pL = lp.pL;
+        if (front && j == 0) {
+            pl.gemm = DC_FRONT;
+        } else if (pg_last && last) {
+            pl.gemm = DC_PG;
+        } else if (h_gemm) {
+            // G4 input: every column is loaded once per channel block and shifted in registers for the
+            // other taps (instantiated for the tap counts of the supported configs)
+            pl.gemm = !pl.x_g4 ? DC_H_PLANAR : lp.taps == 4 ? DC_HS4 : lp.taps == 5 ? DC_HS5 : lp.taps == 6 ? DC_HS6 : DC_H_G4;
+        } else if (lp.tab_f_off && !h->dc_no_pg) {
+            // fp32, 256 input channels: the frame-axis GEMM with the input tile in LDS (wn_iaf_f.hip); its phase-major output
+            // is indexed by (output phase, frame), so the weave runs with pL = 0
+            pl.gemm = DC_FA;
+            pl.cols = (L + 63) / 64 * 64;
+            pl.weave_pL = 0;
+        } else {
+            pl.gemm = DC_MFMA;
+        }
+        if (pl.gemm == DC_FRONT || pl.gemm == DC_PG) {
+            pl.weave = DC_WEAVE_NONE;      // G4 words straight from the launch
+            pl.cols = 0;
+        } else if (y_g4) {
+            // also behind the fp32 GEMMs (a teacher handle created with precision f32; a split-fp16 handle whose stack has a
+            // layer without a split-fp16 pack): the same weave, split in its epilogue
+            pl.weave = lp.S == 20 ? DC_WEAVE_G4_20 : lp.S == 10 ? DC_WEAVE_G4_10 : DC_WEAVE_G4_0;
+            pl.weave_hidden = last ? 0 : 1;
+        } else {
+            // fp32 rows: the last layer of Engine.deconv, every layer of the fp32 GEMMs
+            pl.weave = DC_WEAVE_IL;
+        }
+        L = pl.Lout;
+    }
+    return P;
+}
+
+// ---- one launch helper per form.  x / y: the layer's input and output rows, phase: the phase-major buffer ----
+static void dc_launch_front(const wn_handle* h, const DeconvLayerPack& lp, const float* mel, int B, int F, float* y, int64_t ys,
+                            unsigned* status, hipStream_t st) {
+    FrontArgs A{};
+    A.mel = mel; A.B = B; A.F = F;
+    A.wp = reinterpret_cast<const unsigned*>(h->d_blob + lp.w_off_h);
+    A.bias = h->d_blob + lp.b_off;
+    A.inv_scale = lp.inv_scale_h;
+    A.y = reinterpret_cast<unsigned*>(y);
+    A.ys = (int)ys;
+    A.S = lp.S; A.pL = lp.pL; A.act = h->cfg.upsample_act;
+    A.ncb = (F + 15) / 16;
+    A.nunits = lp.S * B * A.ncb;
+    A.status = status;
+    hipLaunchKernelGGL(deconv_front_kernel, dim3((A.nunits + 7) / 8 * 8), dim3(DF_WAVES * 64), 0, st, A);
+}
+
+static void dc_launch_pg(const wn_handle* h, const DeconvLayerPack& lp, const DeconvPlanLayer& pl, const float* x, int B, float* y,
+                         int64_t ys, int yoff, unsigned* status, hipStream_t st) {
+    PgArgs A{};
+    A.x = reinterpret_cast<const unsigned*>(x);
+    A.cin = lp.cin; A.xs = pl.xs; A.L = pl.L;
+    A.wp = reinterpret_cast<const unsigned*>(h->d_blob + lp.w_off_pg);
+    A.bias = h->d_blob + lp.b_off;
+    A.inv_scale = lp.inv_scale_h;
+    A.y = reinterpret_cast<unsigned*>(y);
+    A.cout = lp.cout; A.S = lp.S; A.act = h->cfg.upsample_act;
+    A.ys = ys; A.yoff = yoff; A.status = status;
+    A.ngroups = lp.pg_n; A.nrg = lp.pg_nrg;
+    for (int g = 0; g < lp.pg_n; ++g) {
+        A.g_p0[g] = lp.pg_p0[g]; A.g_nph[g] = lp.pg_nph[g]; A.g_d[g] = lp.pg_d[g]; A.g_rg0[g] = lp.pg_rg0[g];
+    }
+    A.ntiles = (pl.L + PG_FRAMES - 1) / PG_FRAMES;
+    hipLaunchKernelGGL(deconv_pg_kernel, dim3(lp.pg_nrg * A.ntiles, B), dim3(PG_WAVES * 64), PG_LDS_BYTES, st, A);
+}
+
+template <int TAPS>
+static void dc_launch_hs(const wn_handle* h, const DeconvLayerPack& lp, const DeconvPlanLayer& pl, const float* x, int B,
+                         float* phase, hipStream_t st) {
+    hipLaunchKernelGGL(deconv_mfma_hs_kernel<TAPS>, dim3(pl.cols / DC_QW, lp.S, B * (lp.cout / 64)), dim3(256), 0, st,
+                       reinterpret_cast<const unsigned*>(x), lp.cin, pl.xs, reinterpret_cast<const unsigned*>(h->d_blob + lp.w_off_h),
+                       phase, lp.cout, pl.cols, lp.S, lp.inv_scale_h);
+}
+
+template <bool G4IN>
+static void dc_launch_h(const wn_handle* h, const DeconvLayerPack& lp, const DeconvPlanLayer& pl, const float* x, int B,
+                        float* phase, hipStream_t st) {
+    hipLaunchKernelGGL(deconv_mfma_h_kernel<G4IN>, dim3(pl.cols / DC_QW, lp.S, B * (lp.cout / 64)), dim3(256), 0, st,
+                       reinterpret_cast<const unsigned*>(x), lp.cin, pl.xs, reinterpret_cast<const unsigned*>(h->d_blob + lp.w_off_h),
+                       phase, lp.cout, pl.cols, lp.S, lp.taps, lp.inv_scale_h);
+}
+
+static void dc_launch_fa(wn_handle* h, const DeconvLayerPack& lp, const DeconvPlanLayer& pl, const float* x, int B, float* phase,
+                         hipStream_t st) {
+    wn_deconv_f_gemm(h, x, pl.xs, DC_XOFF, reinterpret_cast<const unsigned*>(h->d_blob + lp.tab_f_off), lp.tab_f_R, lp.taps,
+                     (lp.cout / 16) * 256, phase, lp.S, lp.cout, pl.L, pl.cols, B, st);
+}
+
+static void dc_launch_mfma(const wn_handle* h, const DeconvLayerPack& lp, const DeconvPlanLayer& pl, const float* x, int B,
+                           float* phase, hipStream_t st) {
+    const int zc = (lp.cout + 255) / 256;
+    hipLaunchKernelGGL(deconv_mfma_kernel, dim3(pl.cols / DC_QT, lp.S, B * zc), dim3(256), 0, st, x, lp.cin, pl.xs,
+                       h->d_blob + lp.w_off, phase, lp.cout, pl.cols, lp.S, lp.taps, zc);
+}
+
+// phase-major rows -> time order, bias and activation: fp32 rows, or G4 words split in the epilogue
+static void dc_launch_weave(const wn_handle* h, const DeconvLayerPack& lp, const DeconvPlanLayer& pl, const float* phase, int B,
+                            float* y, int64_t ys, int yoff, unsigned* status, hipStream_t st) {
+    const float* bias = h->d_blob + lp.b_off;
+    if (pl.weave == DC_WEAVE_IL) {
+        hipLaunchKernelGGL(deconv_interleave_kernel, dim3(pl.cols / DC_QT, lp.cout, B), dim3(256), 0, st, phase, bias, y, lp.cout,
+                           pl.cols, ys, yoff, pl.L, lp.S, pl.weave_pL, h->cfg.upsample_act);
+    } else if (pl.weave != DC_WEAVE_NONE) {
+        auto ik = pl.weave == DC_WEAVE_G4_20 ? deconv_interleave_g4_kernel<20>
+                : pl.weave == DC_WEAVE_G4_10 ? deconv_interleave_g4_kernel<10> : deconv_interleave_g4_kernel<0>;
+        hipLaunchKernelGGL(ik, dim3(pl.cols / DG_Q, lp.cout / 8, B), dim3(256), 0, st, phase, bias, reinterpret_cast<unsigned*>(y),
+                           lp.cout, pl.cols, ys, yoff, pl.L, lp.S, pl.weave_pL, h->cfg.upsample_act, status, pl.weave_hidden);
+    }
 }
 
 int wn_run_deconv(wn_handle* h, int si, const float* mel, int B, int F, float* enc_cm,
                   int64_t enc_stride, void* scratch, hipStream_t st, bool split_out, unsigned* status, int prec) {
     const wn_config& c = h->cfg;
     const DeconvStackPack& sp = h->stacks[si];
-    // split-fp16 GEMMs when the call runs in f16x3 mode and every layer's shape supports them
-    bool h_gemm = (prec < 0 ? c.precision : prec) == WN_PREC_F16X3;
-    for (const DeconvLayerPack& lp : sp.layers) h_gemm = h_gemm && lp.w_off_h != 0;
+    const DeconvPlan P = dc_plan(h, si, B, F, split_out, prec);
     float* buf = reinterpret_cast<float*>(scratch);
-    int xs = dc_row_stride(F);
-    // deconv_front_kernel: the first layer in one launch where it is 4 taps x 80 mel channels -> 256 channels and the stack
-    // ends in deconv_pg_kernel (the condition of that branch below); every other stack keeps the three launches
-    const DeconvLayerPack& l0 = sp.layers.front();
-    const DeconvLayerPack& ll = sp.layers.back();
-    const bool front = h_gemm && c.n_deconv >= 2 && split_out && ll.w_off_pg && !h->dc_no_pg && l0.taps == 4 &&
-                       l0.cin == DF_CIN && l0.cout == 256 &&
-                       (int64_t)64 * 16 * dc_row_stride(F * l0.S) < ((int64_t)1 << 31);      // (32-bit store offsets)
-    if (front) {
-        // mel is split inside the launch
-    } else if (h_gemm) {
-        dim3 g((xs + 255) / 256, c.n_mel / 2, B);
-        hipLaunchKernelGGL(mel_to_split_kernel, g, dim3(256), 0, st, mel, reinterpret_cast<unsigned*>(buf), F,
-                           c.n_mel, xs, status);
-    } else {
-        dim3 g((xs + 255) / 256, c.n_mel, B);
-        hipLaunchKernelGGL(mel_to_cm_kernel, g, dim3(256), 0, st, mel, buf, F, c.n_mel, xs);
+    const int xs0 = dc_row_stride(F);
+    if (P.entry == DC_ENTRY_SPLIT) {
+        dim3 g((xs0 + 255) / 256, c.n_mel / 2, B);
+        hipLaunchKernelGGL(mel_to_split_kernel, g, dim3(256), 0, st, mel, reinterpret_cast<unsigned*>(buf + P.at.mel), F,
+                           c.n_mel, xs0, status);
+    } else if (P.entry == DC_ENTRY_CM) {
+        dim3 g((xs0 + 255) / 256, c.n_mel, B);
+        hipLaunchKernelGGL(mel_to_cm_kernel, g, dim3(256), 0, st, mel, buf + P.at.mel, F, c.n_mel, xs0);
     }
-    const float* x = buf;
-    float* next = buf + (size_t)B * c.n_mel * xs;
-    // the phase-major buffer sits at the end of the scratch area
-    float* phase = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + wn_deconv_scratch_bytes(h, B, F)) -
-                   dc_phase_floats(h, B, F);
-    int L = F;
-    bool in_g4 = false;
-    for (int j = 0; j < c.n_deconv; ++j) {
+    float* phase = buf + P.at.phase;
+    for (int j = 0; j < P.n; ++j) {
         const DeconvLayerPack& lp = sp.layers[j];
-        const bool last = (j + 1 == c.n_deconv);
-        const int Lout = L * lp.S;
-        float* y;
-        int64_t ys;
-        int yoff;
-        if (last) {
-            y = enc_cm; ys = enc_stride; yoff = 0;
-        } else {
-            y = next; ys = dc_row_stride(Lout); yoff = DC_XOFF;
+        const DeconvPlanLayer& pl = P.layer[j];
+        const float* x = buf + pl.x_off;
+        float* y = pl.y_enc ? enc_cm : buf + pl.y_off;
+        const int64_t ys = pl.y_enc ? enc_stride : pl.ys;
+        if (pl.zero_pads) WN_HIP(h, hipMemsetAsync(y, 0, (size_t)B * lp.cout * ys * sizeof(float), st));
+        switch (pl.gemm) {
+        case DC_FRONT: dc_launch_front(h, lp, mel, B, F, y, ys, status, st); break;
+        case DC_PG: dc_launch_pg(h, lp, pl, x, B, y, ys, pl.yoff, status, st); break;
+        case DC_HS4: dc_launch_hs<4>(h, lp, pl, x, B, phase, st); break;
+        case DC_HS5: dc_launch_hs<5>(h, lp, pl, x, B, phase, st); break;
+        case DC_HS6: dc_launch_hs<6>(h, lp, pl, x, B, phase, st); break;
+        case DC_H_PLANAR: dc_launch_h<false>(h, lp, pl, x, B, phase, st); break;
+        case DC_H_G4: dc_launch_h<true>(h, lp, pl, x, B, phase, st); break;
+        case DC_FA: dc_launch_fa(h, lp, pl, x, B, phase, st); break;
+        case DC_MFMA: dc_launch_mfma(h, lp, pl, x, B, phase, st); break;
         }
-        const int Q = L + (lp.pL + lp.S - 1) / lp.S + 1;      // phase columns q = (t + pL) / S
-        const int Qp = ((Q + DC_QW - 1) / DC_QW) * DC_QW;
-        // the fp16 GEMM of the NEXT layer reads G4 words (deconv_width is a multiple of 64: validate, wn_host.cpp)
-        const bool next_g4 = h_gemm && !last;
-        // zero pads of an intermediate output: the G4 interleave writes them itself, the other forms get a memset
-        if (!last && !next_g4) WN_HIP(h, hipMemsetAsync(y, 0, (size_t)B * lp.cout * ys * sizeof(float), st));
-        if (front && j == 0) {
-            FrontArgs A{};
-            A.mel = mel; A.B = B; A.F = F;
-            A.wp = reinterpret_cast<const unsigned*>(h->d_blob + lp.w_off_h);
-            A.bias = h->d_blob + lp.b_off;
-            A.inv_scale = lp.inv_scale_h;
-            A.y = reinterpret_cast<unsigned*>(y);
-            A.ys = (int)ys;
-            A.S = lp.S; A.pL = lp.pL; A.act = c.upsample_act;
-            A.ncb = (F + 15) / 16;
-            A.nunits = lp.S * B * A.ncb;
-            A.status = status;
-            hipLaunchKernelGGL(deconv_front_kernel, dim3((A.nunits + 7) / 8 * 8), dim3(DF_WAVES * 64), 0, st, A);
-            in_g4 = true;
-            x = y; xs = (int)ys; next = y + (size_t)B * lp.cout * ys; L = Lout;
-            continue;
-        }
-        // (h->dc_no_pg: WN_DC_NO_PG=1 at wn_create keeps the phase-major GEMM + interleave of rounds 1-4: A/B runs, cross-form test)
-        if (h_gemm && in_g4 && last && split_out && lp.w_off_pg && !h->dc_no_pg) {
-            PgArgs A{};
-            A.x = reinterpret_cast<const unsigned*>(x);
-            A.cin = lp.cin; A.xs = xs; A.L = L;
-            A.wp = reinterpret_cast<const unsigned*>(h->d_blob + lp.w_off_pg);
-            A.bias = h->d_blob + lp.b_off;
-            A.inv_scale = lp.inv_scale_h;
-            A.y = reinterpret_cast<unsigned*>(y);
-            A.cout = lp.cout; A.S = lp.S; A.act = c.upsample_act;
-            A.ys = ys; A.yoff = yoff; A.status = status;
-            A.ngroups = lp.pg_n; A.nrg = lp.pg_nrg;
-            for (int g = 0; g < lp.pg_n; ++g) {
-                A.g_p0[g] = lp.pg_p0[g]; A.g_nph[g] = lp.pg_nph[g]; A.g_d[g] = lp.pg_d[g]; A.g_rg0[g] = lp.pg_rg0[g];
-            }
-            A.ntiles = (L + PG_FRAMES - 1) / PG_FRAMES;
-            hipLaunchKernelGGL(deconv_pg_kernel, dim3(lp.pg_nrg * A.ntiles, B), dim3(PG_WAVES * 64), PG_LDS_BYTES, st, A);
-            in_g4 = false;
-            x = y; xs = (int)ys; next = y + (size_t)B * lp.cout * ys; L = Lout;
-            continue;
-        }
-        if (h_gemm) {
-            dim3 g(Qp / DC_QW, lp.S, B * (lp.cout / 64));
-            const unsigned* xin = reinterpret_cast<const unsigned*>(x);
-            const unsigned* wfr = reinterpret_cast<const unsigned*>(h->d_blob + lp.w_off_h);
-            // G4 input: every column is loaded once per channel block and shifted in registers for the
-            // other taps (instantiated for the tap counts of the supported configs)
-            if (in_g4 && lp.taps == 4)
-                hipLaunchKernelGGL(deconv_mfma_hs_kernel<4>, g, dim3(256), 0, st, xin, lp.cin, xs, wfr, phase, lp.cout,
-                                   Qp, lp.S, lp.inv_scale_h);
-            else if (in_g4 && lp.taps == 5)
-                hipLaunchKernelGGL(deconv_mfma_hs_kernel<5>, g, dim3(256), 0, st, xin, lp.cin, xs, wfr, phase, lp.cout,
-                                   Qp, lp.S, lp.inv_scale_h);
-            else if (in_g4 && lp.taps == 6)
-                hipLaunchKernelGGL(deconv_mfma_hs_kernel<6>, g, dim3(256), 0, st, xin, lp.cin, xs, wfr, phase, lp.cout,
-                                   Qp, lp.S, lp.inv_scale_h);
-            else {
-                auto kern = in_g4 ? deconv_mfma_h_kernel<true> : deconv_mfma_h_kernel<false>;
-                hipLaunchKernelGGL(kern, g, dim3(256), 0, st, xin, lp.cin, xs, wfr, phase, lp.cout, Qp, lp.S, lp.taps,
-                                   lp.inv_scale_h);
-            }
-        } else if (lp.tab_f_off && !h->dc_no_pg) {
-            // fp32, 256 input channels: the frame-axis GEMM with the input tile in LDS (wn_iaf_f.hip); its phase-major output
-            // is indexed by (output phase, frame), so the interleave below runs with pL = 0
-            const int Lp = (L + 63) / 64 * 64;
-            wn_deconv_f_gemm(h, x, xs, DC_XOFF, reinterpret_cast<const unsigned*>(h->d_blob + lp.tab_f_off), lp.tab_f_R, lp.taps,
-                             (lp.cout / 16) * 256, phase, lp.S, lp.cout, L, Lp, B, st);
-            if (last && split_out) {
-                // a consumer of G4 words behind fp32 GEMMs (a teacher handle created with precision f32; a split-fp16 handle
-                // whose stack has a layer without a split-fp16 pack): the same weave, split in its epilogue
-                dim3 gi(Lp / DG_Q, lp.cout / 8, B);
-                auto ik = lp.S == 20 ? deconv_interleave_g4_kernel<20> : lp.S == 10 ? deconv_interleave_g4_kernel<10>
-                                                                                     : deconv_interleave_g4_kernel<0>;
-                hipLaunchKernelGGL(ik, gi, dim3(256), 0, st, phase, h->d_blob + lp.b_off, reinterpret_cast<unsigned*>(y),
-                                   lp.cout, Lp, ys, yoff, L, lp.S, 0, c.upsample_act, status, 0);
-            } else {
-                dim3 gi(Lp / DC_QT, lp.cout, B);
-                hipLaunchKernelGGL(deconv_interleave_kernel, gi, dim3(256), 0, st, phase, h->d_blob + lp.b_off, y,
-                                   lp.cout, Lp, ys, yoff, L, lp.S, 0, c.upsample_act);
-            }
-            in_g4 = false;
-            x = y;
-            xs = (int)ys;
-            next = y + (size_t)B * lp.cout * ys;
-            L = Lout;
-            continue;
-        } else {
-            const int zc = (lp.cout + 255) / 256;
-            dim3 g(Qp / DC_QT, lp.S, B * zc);
-            hipLaunchKernelGGL(deconv_mfma_kernel, g, dim3(256), 0, st, x, lp.cin, xs, h->d_blob + lp.w_off, phase,
-                               lp.cout, Qp, lp.S, lp.taps, zc);
-        }
-        // intermediate outputs feed the next GEMM; the last one is split (G4) only when the caller
-        // consumes the split layout
-        if ((last && split_out) || next_g4) {
-            dim3 gi(Qp / DG_Q, lp.cout / 8, B);
-            auto ik = lp.S == 20 ? deconv_interleave_g4_kernel<20> : lp.S == 10 ? deconv_interleave_g4_kernel<10>
-                                                                                 : deconv_interleave_g4_kernel<0>;
-            hipLaunchKernelGGL(ik, gi, dim3(256), 0, st, phase, h->d_blob + lp.b_off,
-                               reinterpret_cast<unsigned*>(y), lp.cout, Qp, ys, yoff, L, lp.S, lp.pL, c.upsample_act,
-                               status, last ? 0 : 1);
-        } else {
-            // fp32 rows: the last layer of Engine.deconv, every layer of the fp32 GEMMs (a hidden layer of the split-fp16
-            // GEMMs always takes the G4 branch above: wn_create admits only deconv_width % 64 == 0)
-            dim3 gi(Qp / DC_QT, lp.cout, B);
-            hipLaunchKernelGGL(deconv_interleave_kernel, gi, dim3(256), 0, st, phase, h->d_blob + lp.b_off, y,
-                               lp.cout, Qp, ys, yoff, L, lp.S, lp.pL, c.upsample_act);
-        }
-        in_g4 = next_g4;
-        x = y;
-        xs = (int)ys;
-        next = y + (size_t)B * lp.cout * ys;
-        L = Lout;
+        dc_launch_weave(h, lp, pl, phase, B, y, ys, pl.yoff, status, st);
     }
     WN_HIP(h, hipGetLastError());
     return WN_OK;
@@ -1260,5 +1286,50 @@ extern "C" int wn_deconv(wn_handle* h, const char* scope, const float* mel, int 
     dim3 g((unsigned)((Tn + 31) / 32), (h->cfg.deconv_width + 31) / 32, B);
     hipLaunchKernelGGL(cm_to_tm_kernel, g, dim3(256), 0, st, cm, enc, h->cfg.deconv_width, Tn, Tn);
     WN_HIP(h, hipGetLastError());
+    return WN_OK;
+}
+
+static const char* dc_gemm_name(DcGemm g) {
+    switch (g) {
+    case DC_FRONT: return "front";
+    case DC_PG: return "pg";
+    case DC_HS4: return "hs<4>";
+    case DC_HS5: return "hs<5>";
+    case DC_HS6: return "hs<6>";
+    case DC_H_PLANAR: return "h<false>";
+    case DC_H_G4: return "h<true>";
+    case DC_FA: return "fa";
+    case DC_MFMA: return "mfma";
+    }
+    return "?";
+}
+
+static const char* dc_weave_name(DcWeave w) {
+    switch (w) {
+    case DC_WEAVE_NONE: return "";
+    case DC_WEAVE_IL: return " il";
+    case DC_WEAVE_G4_0: return " g4<0>";
+    case DC_WEAVE_G4_10: return " g4<10>";
+    case DC_WEAVE_G4_20: return " g4<20>";
+    }
+    return " ?";
+}
+
+extern "C" int wn_deconv_forms(const wn_handle* h, const char* scope, int B, int F, int split_out, int precision, char* buf,
+                               size_t cap) {
+    if (!h) return wn_fail(nullptr, WN_EINVAL, "wn_deconv_forms: null handle");
+    if (!h->finalized) return wn_fail(h, WN_ESTATE, "wn_deconv_forms: call wn_finalize first");
+    if (!buf || B < 1 || F < 1 || precision < -1 || precision > WN_PREC_F32)
+        return wn_fail(h, WN_EINVAL, "wn_deconv_forms: bad argument");
+    int si = -1;
+    for (size_t i = 0; i < h->stacks.size(); ++i)
+        if (h->stacks[i].prefix == (scope ? scope : "")) si = (int)i;
+    if (si < 0) return wn_fail(h, WN_ENOENT, "wn_deconv_forms: no deconv stack with scope '%s'", scope ? scope : "");
+    const DeconvPlan P = dc_plan(h, si, B, F, split_out != 0, precision);
+    std::string s;
+    for (int j = 0; j < P.n; ++j)
+        s += std::string(j ? ", " : "") + dc_gemm_name(P.layer[j].gemm) + dc_weave_name(P.layer[j].weave);
+    if (s.size() + 1 > cap) return wn_fail(h, WN_EINVAL, "wn_deconv_forms: buffer of %zu bytes, %zu needed", cap, s.size() + 1);
+    memcpy(buf, s.c_str(), s.size() + 1);
     return WN_OK;
 }

@@ -304,11 +304,49 @@ int wn_pack_ar(wn_handle* h, std::vector<float>& blob);
 int wn_pack_teacher(wn_handle* h, std::vector<float>& blob);   // after wn_pack_ar (reuses its matrices)
 int wn_pack_iaf_train(wn_handle* h, std::vector<float>& blob);  // students the training calls accept (wn_iaf_train.hip)
 
-// Runs stack `si` on mel [B,F,n_mel]; writes channel-major enc [B][cout][enc_stride]
-// (first valid sample at column 0).  Scratch carved from ws.
-struct DeconvScratch {
+// What one wn_run_deconv call launches and where every layer's rows sit (dc_plan, wn_deconv.hip).  Fixed size, no heap: it
+// is filled inside every generate call.  Offsets are floats from the start of the scratch area.
+enum DcEntry { DC_ENTRY_NONE, DC_ENTRY_SPLIT, DC_ENTRY_CM };   // nothing (deconv_front_kernel splits the mel itself) | mel_to_split_kernel | mel_to_cm_kernel
+enum DcGemm {
+    DC_FRONT,                  // deconv_front_kernel
+    DC_PG,                     // deconv_pg_kernel
+    DC_HS4, DC_HS5, DC_HS6,    // deconv_mfma_hs_kernel<TAPS>
+    DC_H_PLANAR, DC_H_G4,      // deconv_mfma_h_kernel<G4IN = false | true>
+    DC_FA,                     // the frame-axis fp32 GEMM (wn_iaf_f.hip)
+    DC_MFMA                    // deconv_mfma_kernel
+};
+enum DcWeave { DC_WEAVE_NONE, DC_WEAVE_IL, DC_WEAVE_G4_0, DC_WEAVE_G4_10, DC_WEAVE_G4_20 };   // deconv_interleave_kernel | deconv_interleave_g4_kernel<S>
+struct DeconvLayout {
+    size_t mel;                        // channel-major mel image (fp32, or split words)
+    size_t hidden[WN_MAX_DECONV];      // output rows of layer j < n_deconv - 1
+    size_t phase;                      // phase-major GEMM output of the largest layer; it ends where the scratch area ends
     size_t bytes;
 };
+struct DeconvPlanLayer {
+    DcGemm gemm;
+    DcWeave weave;
+    int L, Lout;                       // frames in, samples out per row
+    int cols;                          // columns of a phase-major row: Qp, or Lp behind the frame-axis GEMM (front, pg: none)
+    int weave_pL;                      // the weave's left pad: the layer's pL, or 0 behind the frame-axis GEMM
+    int weave_hidden;                  // the G4 weave's hidden-layer flag
+    size_t x_off;                      // input rows
+    int xs;
+    bool x_g4;                         // ... are G4 words (else planar: fp32, or split pair planes of the mel)
+    bool y_enc;                        // output rows: the caller's enc_cm with its enc_stride, else y_off / ys
+    size_t y_off;
+    int64_t ys;
+    int yoff;                          // column of sample 0
+    bool zero_pads;                    // hipMemsetAsync of the output rows first (the forms that do not write their pads)
+};
+struct DeconvPlan {
+    DcEntry entry;
+    DeconvLayout at;
+    int n;
+    DeconvPlanLayer layer[WN_MAX_DECONV];
+};
+
+// Runs stack `si` on mel [B,F,n_mel]; writes channel-major enc [B][cout][enc_stride]
+// (first valid sample at column 0).  Scratch carved from ws.
 size_t wn_deconv_scratch_bytes(const wn_handle* h, int B, int F);
 // split_out: write the LAST layer's output as split-fp16 words in the G4 layout (wn_iaf_h.hip)
 // instead of fp32 rows

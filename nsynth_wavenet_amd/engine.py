@@ -396,14 +396,29 @@ class Engine(object):
             self._check(self.lib.wn_clip_quant(self._h, _ptr(x), x.numel(), _ptr(wav), _ptr(idx), self._stream()))
         return wav, idx
 
+    def _deconv_scope(self, scope):
+        if scope is not None:
+            return scope
+        return '' if self.kind == 'teacher' else \
+            ('iaf_share' if (getattr(self.hp, 'use_share_deconv', False) or
+                             getattr(self.hp, 'use_teacher_deconv', False)) else 'iaf_1')
+
+    def deconv_forms(self, batch, num_frames, scope=None, split_out=False, precision=None):
+        """The kernels the upsampler stack `scope` runs for (batch, num_frames), one string per layer ('front', 'pg',
+        'hs<4> il', 'h<false> g4<10>', 'fa g4<0>', 'mfma il' ...: wn_deconv_forms).  split_out: G4 words out, as the generate,
+        teacher and training calls ask for, instead of deconv()'s fp32 rows; precision: None = the engine's, else 'f16x3' or
+        'f32' for the arithmetic of one call.  Launches nothing."""
+        prec = -1 if precision is None else cfg.PRECISIONS[precision][0]
+        buf = ctypes.create_string_buffer(256)
+        self._check(self.lib.wn_deconv_forms(self._h, self._deconv_scope(scope).encode(), int(batch), int(num_frames),
+                                             int(bool(split_out)), prec, buf, len(buf)))
+        return buf.value.decode().split(', ')
+
     def deconv(self, mel, scope=None):
         """Wavenet.deconv_stack: mel [B,F,n_mel] -> [B, F*frame_shift, deconv_width]."""
         mel = self._dev(mel)
         B, F = int(mel.shape[0]), int(mel.shape[1])
-        if scope is None:
-            scope = '' if self.kind == 'teacher' else \
-                ('iaf_share' if (getattr(self.hp, 'use_share_deconv', False) or
-                                 getattr(self.hp, 'use_teacher_deconv', False)) else 'iaf_1')
+        scope = self._deconv_scope(scope)
         enc = torch.empty((B, F * self.frame_shift, self.hp.deconv_width), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             ws = self._workspace(self.lib.wn_workspace_bytes(self._h, B, F))

@@ -7,11 +7,15 @@ use_share_deconv) with num_iaf_layers [10]; the teacher handles a 64-channel wav
 pL = (K - S) / 2 (resize-conv: taps = ceil((K - 1) / S) + 1, rounded up where taps x cin / 16 would be odd, pL = K - 1 - (K - 1) // 2).
 "pg" = the phase groups of deconv_pg_kernel (phases per group) and its row groups at 256 channels.
 
-The kernel columns are what wn_run_deconv dispatches per layer, confirmed by a kernel trace on an MI355X:
-  rows   Engine.deconv, split-fp16 GEMMs, fp32 rows out           G4   the same stack writing G4 words for a consumer
-  f32    Engine(precision='f32'): fp32 GEMMs, fp32 rows out
-h<..> = deconv_mfma_h_kernel<G4IN>, hs<T> = deconv_mfma_hs_kernel<TAPS>, pg = deconv_pg_kernel, mfma = deconv_mfma_kernel,
-fa = gemm_f32_kernel<4, true> (the frame-axis GEMM), il = deconv_interleave_kernel, g4<S> = deconv_interleave_g4_kernel<S>.
+The kernel columns are what wn_run_deconv launches per layer.  tests/test_gpu_deconv_geometries.py asserts every cell against
+Engine.deconv_forms, which prints the plan the runner launches from (dc_plan, csrc/wn_deconv.hip):
+  rows   Engine.deconv, split-fp16 GEMMs, fp32 rows out           g4   the same stack writing G4 words for a consumer
+  f32    Engine(precision='f32'): fp32 GEMMs, fp32 rows out       no_pg   g4 on a handle created under WN_DC_NO_PG=1
+  no_pg_rows   rows on such a handle, where they differ from rows (the switch also keeps the frame-axis GEMM out)
+TEACHER_KERNELS: the 64-channel teachers (and the 256-channel one of hop256), default handle and precision='f32'.
+front = deconv_front_kernel, pg = deconv_pg_kernel (one launch each, no weave behind them), h<..> = deconv_mfma_h_kernel<G4IN>,
+hs<T> = deconv_mfma_hs_kernel<TAPS>, mfma = deconv_mfma_kernel, fa = gemm_f32_kernel<4, true> (the frame-axis GEMM),
+il = deconv_interleave_kernel, g4<S> = deconv_interleave_g4_kernel<S>.
 """
 import json
 import os
@@ -24,37 +28,58 @@ DC_QW = 256          # q columns per workgroup of the split-fp16 GEMMs (csrc/wn_
 PG_FRAMES = 640      # frames per workgroup of deconv_pg_kernel
 
 # tag: deconv_config, hop, (taps, pL) per layer, pg phase groups of the last layer (None: no pack), frame-axis table on the
-# last layer, and the kernels per layer: (rows, G4, f32)
+# last layer, and the kernels per layer: (rows, G4, f32, G4 under WN_DC_NO_PG)
 GEOMETRIES = {
     'hop256': dict(deconv_config=[[64, 16], [64, 16]], hop=256, layers=[(4, 24), (4, 24)], pg=[4, 4, 4, 4], pg_rg=32, fa=True,
-                   kernels=dict(rows=['h<false> g4<0>', 'hs<4> il'], g4=['h<false> g4<0>', 'pg'], f32=['mfma il', 'fa il'])),
+                   kernels=dict(rows=['h<false> g4<0>', 'hs<4> il'], g4=['front', 'pg'], f32=['mfma il', 'fa il'],
+                                no_pg=['h<false> g4<0>', 'hs<4> g4<0>'])),
     'taps6': dict(deconv_config=[[40, 10], [48, 8]], hop=80, layers=[(4, 15), (6, 20)], pg=None, pg_rg=0, fa=False,
                   kernels=dict(rows=['h<false> g4<10>', 'hs<6> il'], g4=['h<false> g4<10>', 'hs<6> g4<0>'],
-                               f32=['mfma il', 'mfma il'])),
+                               f32=['mfma il', 'mfma il'], no_pg=['h<false> g4<10>', 'hs<6> g4<0>'])),
     'three': dict(deconv_config=[[8, 2], [20, 4], [16, 4]], hop=32, layers=[(4, 3), (5, 8), (4, 6)], pg=[2, 2], pg_rg=8, fa=True,
-                  kernels=dict(rows=['h<false> g4<0>', 'hs<5> g4<0>', 'hs<4> il'], g4=['h<false> g4<0>', 'hs<5> g4<0>', 'pg'],
-                               f32=['mfma il', 'fa il', 'fa il'])),
+                  kernels=dict(rows=['h<false> g4<0>', 'hs<5> g4<0>', 'hs<4> il'], g4=['front', 'hs<5> g4<0>', 'pg'],
+                               f32=['mfma il', 'fa il', 'fa il'], no_pg=['h<false> g4<0>', 'hs<5> g4<0>', 'hs<4> g4<0>'])),
     # layer 1: 3 taps x 5 blocks of 16 mel channels is odd -> no split-fp16 pack -> the whole stack on the fp32 GEMMs
     'oddtap': dict(deconv_config=[[24, 8], [16, 8]], hop=64, layers=[(3, 8), (2, 4)], pg=None, pg_rg=0, fa=True,
-                   kernels=dict(rows=['mfma il', 'fa il'], g4=['mfma il', 'fa g4<0>'], f32=['mfma il', 'fa il'])),
+                   kernels=dict(rows=['mfma il', 'fa il'], g4=['mfma il', 'fa g4<0>'], f32=['mfma il', 'fa il'],
+                                no_pg=['mfma il', 'mfma g4<0>'], no_pg_rows=['mfma il', 'mfma il'])),
     'one': dict(deconv_config=[[64, 32]], hop=32, layers=[(2, 16)], pg=None, pg_rg=0, fa=False,
-                kernels=dict(rows=['h<false> il'], g4=['h<false> g4<0>'], f32=['mfma il'])),
+                kernels=dict(rows=['h<false> il'], g4=['h<false> g4<0>'], f32=['mfma il'], no_pg=['h<false> g4<0>'])),
     'taps8': dict(deconv_config=[[40, 10], [160, 20]], hop=200, layers=[(4, 15), (8, 70)], pg=None, pg_rg=0, fa=False,
                   kernels=dict(rows=['h<false> g4<10>', 'h<true> il'], g4=['h<false> g4<10>', 'h<true> g4<20>'],
-                               f32=['mfma il', 'mfma il'])),
+                               f32=['mfma il', 'mfma il'], no_pg=['h<false> g4<10>', 'h<true> g4<20>'])),
     's12': dict(deconv_config=[[40, 10], [48, 12]], hop=120, layers=[(4, 15), (4, 18)], pg=[4, 2, 4, 2], pg_rg=24, fa=True,
-                kernels=dict(rows=['h<false> g4<10>', 'hs<4> il'], g4=['h<false> g4<10>', 'pg'], f32=['mfma il', 'fa il'])),
+                kernels=dict(rows=['h<false> g4<10>', 'hs<4> il'], g4=['front', 'pg'], f32=['mfma il', 'fa il'],
+                             no_pg=['h<false> g4<10>', 'hs<4> g4<0>'])),
     # stride 6, pL 9: three phases per input shift d -> the pack refuses the phase groups
     's6': dict(deconv_config=[[40, 10], [24, 6]], hop=60, layers=[(4, 15), (4, 9)], pg=None, pg_rg=0, fa=True,
-               kernels=dict(rows=['h<false> g4<10>', 'hs<4> il'], g4=['h<false> g4<10>', 'hs<4> g4<0>'], f32=['mfma il', 'fa il'])),
+               kernels=dict(rows=['h<false> g4<10>', 'hs<4> il'], g4=['h<false> g4<10>', 'hs<4> g4<0>'], f32=['mfma il', 'fa il'],
+                            no_pg=['h<false> g4<10>', 'hs<4> g4<0>'])),
     's32': dict(deconv_config=[[40, 10], [128, 32]], hop=320, layers=[(4, 15), (4, 48)], pg=[4] * 8, pg_rg=64, fa=True,
-                kernels=dict(rows=['h<false> g4<10>', 'hs<4> il'], g4=['h<false> g4<10>', 'pg'], f32=['mfma il', 'fa il'])),
+                kernels=dict(rows=['h<false> g4<10>', 'hs<4> il'], g4=['front', 'pg'], f32=['mfma il', 'fa il'],
+                             no_pg=['h<false> g4<10>', 'hs<4> g4<0>'])),
     'resize': dict(deconv_config=[[9, 4], [5, 2]], hop=8, layers=[(4, 4), (3, 2)], pg=None, pg_rg=0, fa=False, resize=True,
                    kernels=dict(rows=['h<false> g4<0>', 'h<true> il'], g4=['h<false> g4<0>', 'h<true> g4<0>'],
-                                f32=['mfma il', 'mfma il'])),
+                                f32=['mfma il', 'mfma il'], no_pg=['h<false> g4<0>', 'h<true> g4<0>'])),
 }
 TAGS = list(GEOMETRIES)
 TEACHER_TAGS = ['hop256', 'three', 's12', 'oddtap']
+# teacher_cfg(tag) (64 channels: no deconv_front_kernel, which needs 256, and no frame-axis table, which needs 256 input
+# channels), default handle and precision='f32': fp32 rows and G4 words (what teacher_forward asks for)
+TEACHER_KERNELS = {
+    'hop256': dict(rows=['h<false> g4<0>', 'hs<4> il'], g4=['h<false> g4<0>', 'pg'],
+                   f32_rows=['mfma il', 'mfma il'], f32_g4=['mfma il', 'mfma g4<0>']),
+    'three': dict(rows=['h<false> g4<0>', 'hs<5> g4<0>', 'hs<4> il'], g4=['h<false> g4<0>', 'hs<5> g4<0>', 'pg'],
+                  f32_rows=['mfma il', 'mfma il', 'mfma il'], f32_g4=['mfma il', 'mfma il', 'mfma g4<0>']),
+    's12': dict(rows=['h<false> g4<10>', 'hs<4> il'], g4=['h<false> g4<10>', 'pg'],
+                f32_rows=['mfma il', 'mfma il'], f32_g4=['mfma il', 'mfma g4<0>']),
+    'oddtap': dict(rows=['mfma il', 'mfma il'], g4=['mfma il', 'mfma g4<0>'],
+                   f32_rows=['mfma il', 'mfma il'], f32_g4=['mfma il', 'mfma g4<0>']),
+}
+# ... and hop256 with deconv_width 256: the first layer is the front launch, the fp32 last layer the frame-axis GEMM
+TEACHER_256_KERNELS = dict(rows=['h<false> g4<0>', 'hs<4> il'], g4=['front', 'pg'],
+                           f32_rows=['mfma il', 'fa il'], f32_g4=['mfma il', 'fa g4<0>'])
+DF_STORE_LIMIT = 1 << 31     # deconv_front_kernel addresses its output with 32-bit byte offsets: 64 x 16 x row stride below this
 
 
 def load_json(name):
@@ -122,6 +147,20 @@ def f_b(tag):
     """... past one PG_FRAMES tile, where the last layer has a phase-group pack or a frame-axis table (else None)"""
     g = GEOMETRIES[tag]
     return f_over(tag, PG_FRAMES) if (g['pg'] or g['fa']) else None
+
+
+def row_stride(L):
+    """dc_row_stride (csrc/wn_deconv.hip): DC_XOFF zero columns, the q columns of L frames in whole workgroups, 8 more"""
+    return 8 + (L + 5 + DC_QW - 1) // DC_QW * DC_QW + 8
+
+
+def f_past_front(tag):
+    """smallest F at which the first layer's G4 rows are too long for deconv_front_kernel's 32-bit store offsets"""
+    S = GEOMETRIES[tag]['deconv_config'][0][1]
+    F = (DF_STORE_LIMIT // (64 * 16) - 16 - 5) // S - DC_QW
+    while 64 * 16 * row_stride(F * S) < DF_STORE_LIMIT:
+        F += 1
+    return F
 
 
 def f_crop(tag, num_stages=10):

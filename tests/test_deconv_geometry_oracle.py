@@ -39,6 +39,11 @@ def test_table_states_what_the_pack_derives(tag):
     assert (layers, pg, rg, fa) == (g['layers'], g['pg'], g['pg_rg'], g['fa'])
     assert G.hop(tag) == g['hop']
     assert len(g['kernels']['rows']) == len(g['kernels']['g4']) == len(g['kernels']['f32']) == len(g['deconv_config'])
+    assert len(g['kernels']['no_pg']) == len(g['kernels'].get('no_pg_rows', g['kernels']['rows'])) == len(g['deconv_config'])
+    assert set(g['kernels']) <= {'rows', 'g4', 'f32', 'no_pg', 'no_pg_rows'}
+    for column in G.TEACHER_KERNELS.get(tag, {}).values():
+        assert len(column) == len(g['deconv_config'])
+    assert set(G.TEACHER_KERNELS) == set(G.TEACHER_TAGS)
 
 
 def test_frame_counts_and_narrow_row_groups():

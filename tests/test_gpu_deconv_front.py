@@ -81,6 +81,9 @@ class Models(object):
         """rows, student and teacher on one set of inputs against the float64 oracle; returns the three device results"""
         O = self.O
         B, F = mel.shape[:2]
+        # the two consumers take the front launch, Engine.deconv the three launches (no kernel runs for these questions)
+        assert self.student.deconv_forms(B, F, split_out=True) == self.teacher.deconv_forms(B, F, split_out=True) == ['front', 'pg']
+        assert self.student.deconv_forms(B, F) == ['h<false> g4<10>', 'hs<4> il']
         rows64 = O.deconv_stack(mel, self.s_w, self.s_hp, 'iaf_share', np.float64)
         rows = _np(self.student.deconv(mel))
         assert rows.shape == rows64.shape == (B, F * HOP, 256)
@@ -160,17 +163,44 @@ def test_a_short_call_behind_a_long_one_finds_no_stale_margin(models):
         fresh_t.close()
 
 
+def test_what_the_forms_query_refuses(models):
+    """wn_deconv_forms: WN_ENOENT for an unknown scope and WN_ESTATE before wn_finalize, as wn_deconv; WN_EINVAL for a null
+    or short buffer, a shape below 1 and a precision wn_config.precision does not take."""
+    import ctypes
+    from nsynth_wavenet_amd.engine import Engine
+    eng = models.student
+    assert eng.deconv_forms(1, 3, split_out=True) == ['front', 'pg']
+    with pytest.raises(KeyError):
+        eng.deconv_forms(1, 3, scope='iaf_9')
+    with pytest.raises(ValueError):
+        eng.deconv_forms(0, 3)
+    buf = ctypes.create_string_buffer(64)
+    call = eng.lib.wn_deconv_forms
+    assert call(eng._h, b'iaf_share', 1, 3, 1, -1, buf, len(buf)) == 0 and buf.value == b'front, pg'
+    assert call(eng._h, b'iaf_share', 1, 3, 1, -1, buf, len(b'front, pg')) == -22        # no room for the terminator
+    assert call(eng._h, b'iaf_share', 1, 3, 1, -1, None, 64) == -22
+    assert call(eng._h, b'iaf_share', 1, 3, 1, 2, buf, len(buf)) == -22
+    raw = Engine(models.s_cfg, precision='f16x3')
+    try:
+        with pytest.raises(RuntimeError):
+            raw.deconv_forms(1, 3)
+    finally:
+        raw.close()
+
+
 @pytest.mark.parametrize('tag', ('taps6', 'oddtap'))
 def test_geometries_that_keep_the_three_launches(tag):
     """taps6: the first entry of tests/deconv_geometries.py with a layer of taps != 4 (its last layer has six, so no
-    deconv_pg_kernel behind the first layer); oddtap: the first whose FIRST layer has (three).  The library has no view of
-    which kernel ran, so what is held is the result."""
+    deconv_pg_kernel behind the first layer); oddtap: the first whose FIRST layer has (three).  Engine.deconv_forms says
+    which kernels run; the result is held as well."""
     from oracle import wavenet_np as O
     cfgd, w = G.student_weights(tag)
     hp = O.HP(cfgd)
     eng = _engine(cfgd, w, 'f16x3')
     try:
         B, F = 2, G.f_crop(tag)
+        forms = eng.deconv_forms(B, F, split_out=True)
+        assert forms == G.GEOMETRIES[tag]['kernels']['g4'] and 'front' not in forms, (tag, forms)
         mel, noise, T = G.student_inputs(tag, B, F)
         ref = O.iaf_feed_forward(mel, noise, w, hp, np.float64)
         x = _np(eng.iaf_generate(mel, noise, want=('x',))['x'])

@@ -1,7 +1,8 @@
 """Upsampler forward (csrc/wn_deconv.hip and the frame-axis GEMM of csrc/wn_iaf_f.hip) off the two deconv_configs the rest
-of the suite runs: the ten geometries of tests/deconv_geometries.py (its table names the kernels every row runs; DESIGN.md 18
-has the kernel trace that confirms it), each at shapes (B, F) that put almost every tap on a zero pad (1, 1), have an odd
-batch (3, 2), cross one DC_QW = 256 workgroup of q columns on the last layer (2, F_a) and one PG_FRAMES = 640 tile (1, F_b).
+of the suite runs: the ten geometries of tests/deconv_geometries.py (its table names the kernels every row runs, and tests B
+and C hold every cell of it against Engine.deconv_forms, the plan the runner launches from), each at shapes
+(B, F) that put almost every tap on a zero pad (1, 1), have an odd batch (3, 2), cross one DC_QW = 256 workgroup of q columns
+on the last layer (2, F_a) and one PG_FRAMES = 640 tile (1, F_b).
 
   A  Engine.deconv -- fp32 rows -- against the float64 oracle, every element, split-fp16 and fp32 GEMMs, tf-init and unit
      weights:  max |got - ref| <= 2e-5 max(1, max |ref|)  (the bar of tests/test_gpu_iaf.py for this comparison), the split-fp16
@@ -64,6 +65,13 @@ def students():
         e.close()
 
 
+def _assert_forms(e, B, F, rows, g4, who):
+    """what the engine's upsampler launches for fp32 rows and (g4 not None) for G4 words, against the table; no launch"""
+    assert e.deconv_forms(B, F) == rows, (who, B, F, 'rows')
+    if g4 is not None:
+        assert e.deconv_forms(B, F, split_out=True) == g4, (who, B, F, 'G4')
+
+
 def _rows_case(tag, engs, w, hp, label):
     """test A on one set of weights: engs = {'f16x3': ..., 'f32': ...}"""
     from oracle import wavenet_np as O
@@ -117,6 +125,19 @@ def test_g4_words_through_the_student(tag, students, monkeypatch):
     engs['f16x3, phase-major'] = _engine(cfgd, w, 'f16x3')
     monkeypatch.delenv('WN_DC_NO_PG', raising=False)
     try:
+        # the kernels column of the table is what these handles launch.  An fp32 student never asks for G4 words; a
+        # split-fp16 one runs the fp32 column in the one call that re-runs a range-guard fallback
+        k = G.GEOMETRIES[tag]['kernels']
+        B, F = G.student_shapes(tag)[0]
+        _assert_forms(engs['f16x3'], B, F, k['rows'], k['g4'], (tag, 'f16x3'))
+        _assert_forms(engs['f16x3, phase-major'], B, F, k.get('no_pg_rows', k['rows']), k['no_pg'], (tag, 'WN_DC_NO_PG'))
+        _assert_forms(engs['f32'], B, F, k['f32'], None, (tag, 'f32'))
+        assert engs['f16x3'].deconv_forms(B, F, precision='f32') == k['f32'], tag
+        if k['g4'][0] == 'front':
+            # past the 32-bit store offsets of deconv_front_kernel the first layer is three launches again
+            Fp = G.f_past_front(tag)
+            assert engs['f16x3'].deconv_forms(1, Fp - 1, split_out=True) == k['g4'], tag
+            assert engs['f16x3'].deconv_forms(1, Fp, split_out=True) == k['rows'][:1] + k['g4'][1:], tag
         for B, F in G.student_shapes(tag):
             mel, noise, T = G.student_inputs(tag, B, F)
             assert T == O.iaf_length(F, hp) > 0
@@ -146,11 +167,14 @@ def test_g4_words_through_the_student(tag, students, monkeypatch):
         engs['f16x3, phase-major'].close()
 
 
-def _teacher_case(tag, cfgd, w, precisions, shapes, label):
+def _teacher_case(tag, cfgd, w, precisions, shapes, label, kernels):
     from oracle import wavenet_np as O
     hp = O.HP(cfgd)
     engs = {p: _engine(cfgd, w, p) for p in precisions}
     try:
+        for p, e in engs.items():
+            pre = 'f32_' if p == 'f32' else ''
+            _assert_forms(e, *shapes[-1], kernels[pre + 'rows'], kernels[pre + 'g4'], (tag, label, p))
         for B, F in shapes:
             mel, wav = G.teacher_inputs(tag, B, F)
             enc64 = O.deconv_stack(mel, w, hp, '', np.float64)
@@ -172,7 +196,7 @@ def _teacher_case(tag, cfgd, w, precisions, shapes, label):
 def test_g4_words_of_64_channels_through_the_teacher(tag):
     """Test C."""
     cfgd, w = G.teacher_weights(tag)
-    _teacher_case(tag, cfgd, w, (None, 'f32'), ((2, 3), (1, G.f_a(tag))), '64 channels')
+    _teacher_case(tag, cfgd, w, (None, 'f32'), ((2, 3), (1, G.f_a(tag))), '64 channels', G.TEACHER_KERNELS[tag])
 
 
 def test_fp32_upsampler_of_256_channels_hands_a_teacher_g4_words():
@@ -182,7 +206,7 @@ def test_fp32_upsampler_of_256_channels_hands_a_teacher_g4_words():
     from oracle import wavenet_np as O
     cfgd = dict(G.teacher_cfg('hop256'), deconv_width=256)
     w = O.synth_weights(O.HP(cfgd), 'teacher', seed=G.TEACHER_SEED, init=G.TEACHER_INIT)
-    _teacher_case('hop256', cfgd, w, ('f32', None), ((2, 3),), '256 channels')
+    _teacher_case('hop256', cfgd, w, ('f32', None), ((2, 3),), '256 channels', G.TEACHER_256_KERNELS)
 
 
 REFUSED = [('filter not a multiple of the stride', [[40, 12], [80, 20]]),
