@@ -614,6 +614,15 @@ WN_API size_t wn_iaf_backward_weights_workspace_bytes(const wn_handle* h, int B,
 WN_API int wn_iaf_backward_weights(wn_handle* h, const void* tape, size_t tape_bytes, const float* d_x,
                                    const float* d_mean_tot, const float* d_scale_tot, int B, int F, int64_t T, float* grads,
                                    size_t grads_floats, float* d_encoding, void* ws, size_t ws_bytes, void* stream);
+/* The same reverse pass over the same tape without the weight products: the gradient of the student's inputs.
+ * d_noise [B,T], every element overwritten: the total derivative of sum(x d_x + mean_tot d_mean_tot + scale_tot d_scale_tot)
+ * with the noise as a leaf, of the function wn_iaf_forward_train_tape evaluates -- the chain through every flow down to the
+ * first flow's start conv, plus d_x scale_tot for x = noise scale_tot + mean_tot.  d_encoding as above, and bit-equal to what
+ * wn_iaf_backward_weights returns for the same tape and cotangents.  Same checks, ties and refusals; a smaller workspace. */
+WN_API size_t wn_iaf_backward_input_workspace_bytes(const wn_handle* h, int B, int F, int64_t T);
+WN_API int wn_iaf_backward_input(wn_handle* h, const void* tape, size_t tape_bytes, const float* d_x, const float* d_mean_tot,
+                                 const float* d_scale_tot, int B, int F, int64_t T, float* d_noise, float* d_encoding, void* ws,
+                                 size_t ws_bytes, void* stream);
 
 /* ---- reverse pass of the upsampler: the gradients of trans_conv_j/kernel and trans_conv_j/bias of the deconv
  * stack `scope` ("" for a teacher; "iaf_share", "iaf_1" ... for a student, as in wn_deconv) from mel [B,F,n_mel] and a
@@ -636,9 +645,19 @@ WN_API int wn_deconv_grad_info(const wn_handle* h, const char* scope, int i, cha
                                int64_t* shape4, int* ndim);
 WN_API size_t wn_deconv_grad_floats(const wn_handle* h, const char* scope);
 WN_API size_t wn_deconv_backward_workspace_bytes(const wn_handle* h, const char* scope, int B, int F);
-/* grads: every element of the first wn_deconv_grad_floats floats is overwritten.  d mel is not computed. */
+/* grads: every element of the first wn_deconv_grad_floats floats is overwritten.  d mel is not computed here: see
+ * wn_deconv_backward_input. */
 WN_API int wn_deconv_backward(wn_handle* h, const char* scope, const float* mel, const float* d_enc, int B, int F, float* grads,
                               size_t grads_floats, void* ws, size_t ws_bytes, void* stream);
+/* d mel of the stack: d_mel [B,F,n_mel], every element overwritten, from the same mel and d_enc.  The contract
+ * of wn_deconv_backward: the forward is rerun in split fp16 into the call's own workspace, each layer's cotangent enters scaled
+ * by a power of two (a cotangent scaled by 2^k gives d_mel scaled bit for bit), no atomics, one writer per element, the same
+ * refusals; the size query returns 0 for what the work call refuses.  Only the data-gradient chain runs -- no weight or bias
+ * gradient.  Cost for every handle: wn_finalize packs one more transposed split-fp16 copy, the first layer's kernel with its
+ * input channels padded to a multiple of 64 (5.2 MB for the shipped 40 x 80 x 256 layer), behind every other pack. */
+WN_API size_t wn_deconv_backward_input_workspace_bytes(const wn_handle* h, const char* scope, int B, int F);
+WN_API int wn_deconv_backward_input(wn_handle* h, const char* scope, const float* mel, const float* d_enc, int B, int F,
+                                    float* d_mel, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- Teacher training step on the device ----
  *

@@ -30,7 +30,9 @@ SYMBOLS = ['wn_abi_version', 'wn_create', 'wn_set_weight', 'wn_finalize', 'wn_ia
            'wn_iaf_backward_weights', 'wn_iaf_set_weights_workspace_bytes', 'wn_iaf_set_weights',
            'wn_iaf_window_geometry', 'wn_iaf_generate_windows', 'wn_iaf_windows_workspace_bytes',
            'wn_iaf_encode_workspace_bytes', 'wn_iaf_encode', 'wn_iaf_latent_log_prob',
-           'wn_train_batch']
+           'wn_train_batch',
+           'wn_deconv_backward_input_workspace_bytes', 'wn_deconv_backward_input',
+           'wn_iaf_backward_input_workspace_bytes', 'wn_iaf_backward_input']
 
 
 class WindowRow(ctypes.Structure):
@@ -151,11 +153,13 @@ def load():
     lib.wn_iaf_grad_info.argtypes = [vp, i32, c.c_char_p, sz, c.POINTER(i64), c.POINTER(i64), c.POINTER(i32)]
     lib.wn_iaf_grad_floats.argtypes = [vp]
     lib.wn_iaf_grad_floats.restype = sz
-    for name in ('wn_iaf_train_tape_bytes', 'wn_iaf_train_workspace_bytes', 'wn_iaf_backward_weights_workspace_bytes'):
+    for name in ('wn_iaf_train_tape_bytes', 'wn_iaf_train_workspace_bytes', 'wn_iaf_backward_weights_workspace_bytes',
+                 'wn_iaf_backward_input_workspace_bytes'):
         getattr(lib, name).argtypes = [vp, i32, i32, i64]
         getattr(lib, name).restype = sz
     lib.wn_iaf_forward_train_tape.argtypes = [vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, sz, vp, sz, vp]
     lib.wn_iaf_backward_weights.argtypes = [vp, vp, sz, vp, vp, vp, i32, i32, i64, vp, sz, vp, vp, sz, vp]
+    lib.wn_iaf_backward_input.argtypes = [vp, vp, sz, vp, vp, vp, i32, i32, i64, vp, vp, vp, sz, vp]
     lib.wn_deconv_grad_count.argtypes = [vp, c.c_char_p]
     lib.wn_deconv_grad_info.argtypes = [vp, c.c_char_p, i32, c.c_char_p, sz, c.POINTER(i64), c.POINTER(i64), c.POINTER(i32)]
     lib.wn_deconv_grad_floats.argtypes = [vp, c.c_char_p]
@@ -163,6 +167,9 @@ def load():
     lib.wn_deconv_backward_workspace_bytes.argtypes = [vp, c.c_char_p, i32, i32]
     lib.wn_deconv_backward_workspace_bytes.restype = sz
     lib.wn_deconv_backward.argtypes = [vp, c.c_char_p, vp, vp, i32, i32, vp, sz, vp, sz, vp]
+    lib.wn_deconv_backward_input_workspace_bytes.argtypes = [vp, c.c_char_p, i32, i32]
+    lib.wn_deconv_backward_input_workspace_bytes.restype = sz
+    lib.wn_deconv_backward_input.argtypes = [vp, c.c_char_p, vp, vp, i32, i32, vp, vp, sz, vp]
     lib.wn_teacher_set_weights_workspace_bytes.argtypes = [vp]
     lib.wn_teacher_set_weights_workspace_bytes.restype = sz
     lib.wn_teacher_set_weights.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp]

@@ -14,6 +14,8 @@
 //       every 16-byte operand load is aligned), result rows co, columns ci = the TF order [1,K,Cout,Cin];
 //   dx: A = W^T rows [k][ci][co] (packed at wn_finalize), B = DZ_p rows in FRAME-major order [f][co] (the tap shift is a
 //       row offset), result rows ci, columns f'.
+// wn_deconv_backward_input runs the dx chain alone, down to d mel: the first layer's W^T is packed with its rows
+// padded to cinp, and db_dmel_kernel drops the padding columns.
 // The forward is recomputed by wn_run_deconv into the call's workspace; nothing is taped.  Every output element has one
 // writer, partial sums are added in a fixed order, no float atomics: repeated calls give identical bits.
 #include <algorithm>
@@ -52,7 +54,7 @@ LayerDims layer_dims(const DeconvLayerPack& lp, int B, int L) {
     d.N = (long long)B * d.Lp;
     d.nslab = (int)((d.N + DB_SLAB - 1) / DB_SLAB);
     // enough phase chunks for about DB_WGS workgroups, from B and the frame count alone
-    const long long tiles = (long long)(d.cin / 64) * ((L + 63) / 64) * B;
+    const long long tiles = (long long)(d.cinp / 64) * ((L + 63) / 64) * B;      // cinp = cin for every layer but the first
     const int want = (int)std::min<long long>(lp.S, std::max<long long>(1, (DB_WGS + tiles - 1) / std::max<long long>(tiles, 1)));
     d.pchunk = (lp.S + want - 1) / want;
     d.npc = (lp.S + d.pchunk - 1) / d.pchunk;
@@ -88,6 +90,36 @@ BwdLayout bwd_layout(const wn_handle* h, const DeconvStackPack& sp, int B, int F
     o.dzc = take(dzc);
     o.dzt = take(dzt);
     o.xs = take(xs);
+    o.dx = take(dx);
+    o.part = take(part);
+    o.total = p;
+    return o;
+}
+
+// wn_deconv_backward_input: no weight-gradient operands (dzc, xs, slabs); dzt and the phase chunks for the first layer too,
+// whose chunks hold cinp columns per frame
+struct BwdInLayout {
+    size_t scal, part_amax, enc, fwd, dzt, dx, part, total;
+};
+
+BwdInLayout bwd_in_layout(const wn_handle* h, const DeconvStackPack& sp, int B, int F) {
+    BwdInLayout o{};
+    size_t dzt = 0, dx = 0, part = 0;
+    int L = F;
+    for (size_t j = 0; j < sp.layers.size(); ++j) {
+        const LayerDims d = layer_dims(sp.layers[j], B, L);
+        part = std::max<size_t>(part, (size_t)d.npc * B * d.L * d.cinp * sizeof(float));
+        dzt = std::max<size_t>(dzt, (size_t)2 * d.S * B * d.R * d.C * sizeof(hf));
+        if (j > 0) dx = std::max<size_t>(dx, (size_t)B * d.L * d.cin * sizeof(float));
+        L *= d.S;
+    }
+    size_t p = 0;
+    auto take = [&](size_t bytes) { const size_t at = p; p += align_up(std::max<size_t>(bytes, 16), 256); return at; };
+    o.scal = take(sp.layers.size() * 4 * sizeof(float));
+    o.part_amax = take(WN_NPART * sizeof(float));
+    o.enc = take((size_t)B * h->cfg.deconv_width * (size_t)L * sizeof(float));
+    o.fwd = take(wn_deconv_scratch_bytes(h, B, F));
+    o.dzt = take(dzt);
     o.dx = take(dx);
     o.part = take(part);
     o.total = p;
@@ -154,7 +186,7 @@ __device__ inline float db_act_grad(float y, int act) {
 }
 
 // ---- de-interleave: cotangent [B][S L][C] (time-major) x act'(y) -> the phase rows DZ_p, split fp16 ----
-//   dzc[plane][p][co][b Lp + f]            channel-major, for the weight-gradient GEMMs (zeros for f >= L)
+//   dzc[plane][p][co][b Lp + f]            channel-major, for the weight-gradient GEMMs (zeros for f >= L; null: not wanted)
 //   dzt[plane][p][b][dmax + f][co]         frame-major, for the data-gradient GEMM (null: not wanted; the rows outside
 //                                          [dmax, dmax + Lp) are zeroed by the caller)
 // One workgroup = DB_FT frames x DB_CT channels of one batch row = S DB_FT consecutive samples, through LDS; every store is
@@ -198,7 +230,7 @@ __global__ __launch_bounds__(256) void db_deint_kernel(const float* __restrict__
     __syncthreads();
     const long long N = (long long)B * Lp;
     // channel-major rows: (plane, p, c, run of 8 frames)
-    for (int i = threadIdx.x; i < 2 * S * DB_CT * (DB_FT / 8); i += 256) {
+    for (int i = threadIdx.x; dzc && i < 2 * S * DB_CT * (DB_FT / 8); i += 256) {      // (skipped without dzc)
         const int fr = i % (DB_FT / 8), c = (i / (DB_FT / 8)) % DB_CT, p = (i / (DB_FT / 8 * DB_CT)) % S,
                   plane = i / (DB_FT / 8 * DB_CT * S);
         wn_u4 w;
@@ -339,6 +371,28 @@ __global__ __launch_bounds__(256) void db_dxsum_kernel(const float* __restrict__
     reinterpret_cast<f4*>(dx)[i] = s;
 }
 
+// d mel: the first layer's phase chunks [chunk][B F][cinp] summed in order, the padding columns cin .. cinp - 1 dropped, times
+// scal[1] (what undoes every scale applied so far) -> float32 [B F][cin].  One thread = four columns of one frame; VEC: cin is
+// a multiple of 4 and d_mel 16-byte aligned, one 16-byte store
+template <bool VEC>
+__global__ __launch_bounds__(256) void db_dmel_kernel(const float* __restrict__ part, size_t rows, int cin, int cinp, int nchunk,
+                                                      const float* __restrict__ scal, float* __restrict__ d_mel) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const int q = cinp / 4;
+    if (i >= rows * q) return;
+    const size_t row = i / q;
+    const int c0 = 4 * (int)(i - row * q);
+    if (c0 >= cin) return;
+    f4 s = reinterpret_cast<const f4*>(part)[i];
+    for (int k = 1; k < nchunk; ++k) s += reinterpret_cast<const f4*>(part)[(size_t)k * rows * q + i];
+    s = s * scal[1];
+    float* o = d_mel + row * cin + c0;
+    if (VEC) *reinterpret_cast<f4*>(o) = s;
+    else
+        for (int e = 0; e < 4; ++e)
+            if (c0 + e < cin) o[e] = s[e];
+}
+
 // grads[i] = (sum over the slabs, in order) * scal[1]
 __global__ __launch_bounds__(256) void db_reduce_kernel(const float* __restrict__ part, size_t n, int nslab, const float* __restrict__ scal,
                                                         float* __restrict__ out) {
@@ -412,33 +466,43 @@ std::vector<WnGradEntry> dgrad_table(const wn_handle* h, int si) {
 }  // namespace
 
 // W^T of every layer but the first as two planes of halves [k][ci][co], prescaled like the forward's packs; called by
-// wn_finalize after every other pack, so that no existing offset moves
+// wn_finalize after every other pack, so that no existing offset moves.  Behind those, the first layer's W^T with its rows
+// padded to cinp (zero rows behind cin) for wn_deconv_backward_input.
 int wn_pack_deconv_bwd(wn_handle* h, std::vector<float>& blob) {
     const wn_config& c = h->cfg;
     if (c.use_resize_conv || c.use_weight_norm || c.deconv_width % 64) return WN_OK;
+    // rows: the row count of the packed planes (cin, or cinp for the first layer); returns the pack's offset and 1 / scale
+    auto pack_t = [&](const DeconvStackPack& sp, size_t j, int rows, size_t* off, float* inv_scale) {
+        const DeconvLayerPack& lp = sp.layers[j];
+        const std::string scope = (sp.prefix.empty() ? std::string() : sp.prefix + "/") + "trans_conv_" + std::to_string(j + 1);
+        const std::vector<float> W = wn_get_kernel(h, scope, "kernel", true);              // [K][cout][cin]
+        const float sc = pick_scale(W.data(), W.size());
+        const size_t n = (size_t)lp.K * rows * lp.cout;
+        blob.resize(align_up(blob.size(), 64));
+        *off = blob.size();
+        *inv_scale = 1.0f / sc;
+        blob.resize(blob.size() + n);                                                      // 2 planes of n halves, zero
+        uint16_t* P = reinterpret_cast<uint16_t*>(blob.data() + *off);
+        for (int k = 0; k < lp.K; ++k)
+            for (int co = 0; co < lp.cout; ++co)
+                for (int ci = 0; ci < lp.cin; ++ci) {
+                    const float v = sc * W[((size_t)k * lp.cout + co) * lp.cin + ci];
+                    const uint16_t hi = f2h(v);
+                    const size_t at = ((size_t)k * rows + ci) * lp.cout + co;
+                    P[at] = hi;
+                    P[n + at] = f2h(v - h2f(hi));
+                }
+    };
     for (auto& sp : h->stacks)
         for (size_t j = 1; j < sp.layers.size(); ++j) {
             DeconvLayerPack& lp = sp.layers[j];
-            if (!lp.w_off_h) continue;
-            const std::string scope = (sp.prefix.empty() ? std::string() : sp.prefix + "/") + "trans_conv_" + std::to_string(j + 1);
-            const std::vector<float> W = wn_get_kernel(h, scope, "kernel", true);          // [K][cout][cin]
-            const float sc = pick_scale(W.data(), W.size());
-            const size_t n = (size_t)lp.K * lp.cin * lp.cout;
-            blob.resize(align_up(blob.size(), 64));
-            lp.wt_off = blob.size();
-            lp.wt_inv_scale = 1.0f / sc;
-            blob.resize(blob.size() + n);                                                  // 2 planes of n halves
-            uint16_t* P = reinterpret_cast<uint16_t*>(blob.data() + lp.wt_off);
-            for (int k = 0; k < lp.K; ++k)
-                for (int co = 0; co < lp.cout; ++co)
-                    for (int ci = 0; ci < lp.cin; ++ci) {
-                        const float v = sc * W[((size_t)k * lp.cout + co) * lp.cin + ci];
-                        const uint16_t hi = f2h(v);
-                        const size_t at = ((size_t)k * lp.cin + ci) * lp.cout + co;
-                        P[at] = hi;
-                        P[n + at] = f2h(v - h2f(hi));
-                    }
+            if (lp.w_off_h) pack_t(sp, j, lp.cin, &lp.wt_off, &lp.wt_inv_scale);
         }
+    for (auto& sp : h->stacks) {
+        if (sp.layers.empty() || !sp.layers[0].w_off_h) continue;
+        DeconvLayerPack& lp = sp.layers[0];
+        pack_t(sp, 0, (lp.cin + 63) / 64 * 64, &lp.wt_in_off, &lp.wt_in_inv_scale);
+    }
     return WN_OK;
 }
 
@@ -559,6 +623,88 @@ extern "C" int wn_deconv_backward(wn_handle* h, const char* scope, const float* 
             const size_t n4 = (size_t)B * d.L * d.cin / 4;
             hipLaunchKernelGGL(db_dxsum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, part, n4, d.npc, dx);
             g = dx;
+        }
+    }
+    WN_HIP(h, hipGetLastError());
+    return WN_OK;
+}
+
+// ---- d mel: the data-gradient chain alone, down to the first layer ----
+extern "C" size_t wn_deconv_backward_input_workspace_bytes(const wn_handle* h, const char* scope, int B, int F) {
+    int si;
+    if (B < 1 || F < 1 || bwd_check(h, "wn_deconv_backward_input_workspace_bytes", scope, &si, true)) return 0;
+    if (!h->stacks[si].layers[0].wt_in_off) return 0;
+    return bwd_in_layout(h, h->stacks[si], B, F).total;
+}
+
+extern "C" int wn_deconv_backward_input(wn_handle* h, const char* scope, const float* mel, const float* d_enc, int B, int F,
+                                        float* d_mel, void* ws, size_t ws_bytes, void* stream) {
+    const char* fn = "wn_deconv_backward_input";
+    int si;
+    if (int rc = bwd_check(h, fn, scope, &si, false)) return rc;
+    if (!mel || !d_enc || !d_mel || !ws || B < 1 || F < 1) return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
+    if (B > 65535) return wn_fail(h, WN_EINVAL, "%s: B = %d above 65535", fn, B);
+    const DeconvStackPack& sp = h->stacks[si];
+    const int nl = (int)sp.layers.size();
+    std::vector<int> Lin(nl);
+    {
+        int L = F;
+        for (int j = 0; j < nl; ++j) {
+            const LayerDims d = layer_dims(sp.layers[j], B, L);
+            if (d.N > (1ll << 30) || d.nslab > 65535 || (long long)d.S * d.L > (1ll << 30))
+                return wn_fail(h, WN_EINVAL, "%s: B = %d, F = %d is too long for one call", fn, B, F);
+            if (!(j ? sp.layers[j].wt_off : sp.layers[j].wt_in_off))
+                return wn_fail(h, WN_EINVAL, "%s: a layer of the stack has no split-fp16 pack", fn);
+            Lin[j] = L;
+            L *= d.S;
+        }
+    }
+    const BwdInLayout BL = bwd_in_layout(h, sp, B, F);
+    if (ws_bytes < BL.total) return wn_fail(h, WN_EINVAL, "%s: workspace %zu < %zu bytes", fn, ws_bytes, BL.total);
+    const WnWork work(h);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char* base = reinterpret_cast<char*>(ws);
+    float* scal = reinterpret_cast<float*>(base + BL.scal);
+    float* pamax = reinterpret_cast<float*>(base + BL.part_amax);
+    float* enc = reinterpret_cast<float*>(base + BL.enc);
+    void* fwd = base + BL.fwd;
+    hf* dzt = reinterpret_cast<hf*>(base + BL.dzt);
+    float* dx = reinterpret_cast<float*>(base + BL.dx);
+    float* part = reinterpret_cast<float*>(base + BL.part);
+    const int64_t Tn = (int64_t)F * h->frame_shift;
+    // the forward as wn_deconv_backward recomputes it: split-fp16 whatever the handle's precision
+    if (int rc = wn_run_deconv(h, si, mel, B, F, enc, Tn, fwd, st, true, nullptr, WN_PREC_F16X3)) return rc;
+    const float* g = d_enc;
+    for (int j = nl - 1; j >= 0; --j) {
+        const DeconvLayerPack& lp = sp.layers[j];
+        const LayerDims d = layer_dims(lp, B, Lin[j]);
+        float* sj = scal + 4 * j;
+        wn_pow2_scale(g, (long long)B * d.S * d.L * d.C, pamax, sj, j + 1 < nl ? sj + 4 : nullptr, st);
+        WN_HIP(h, hipMemsetAsync(dzt, 0, (size_t)2 * d.S * B * d.R * d.C * sizeof(hf), st));
+        {
+            int64_t ys = Tn; int yoff = 0;
+            const void* y = enc;
+            if (j + 1 < nl) y = wn_deconv_hidden(h, B, F, j, fwd, &ys, &yoff);
+            hipLaunchKernelGGL(db_deint_kernel, dim3(d.Lp / DB_FT, d.C / DB_CT, B), dim3(256), 0, st, g, sj,
+                               reinterpret_cast<const unsigned*>(y), ys, yoff, d.C, d.L, d.Lp, d.S, B, d.R, d.dmax, h->cfg.upsample_act,
+                               (hf*)nullptr, dzt);
+        }
+        // rows of the result: cin, or for the first layer cinp -- the rows behind cin are the pack's zero rows
+        const int rows = j ? d.cin : d.cinp;
+        hipLaunchKernelGGL(db_dgrad_kernel, dim3((rows / 64) * ((d.L + 63) / 64), B, d.npc), dim3(256), 0, st,
+                           reinterpret_cast<const hf*>(h->d_blob + (j ? lp.wt_off : lp.wt_in_off)), dzt, d.C, rows, d.K, d.S, d.taps,
+                           d.pL, d.dmax, d.L, d.R, B, d.pchunk, j ? lp.wt_inv_scale : lp.wt_in_inv_scale, part);
+        if (j > 0) {
+            const size_t n4 = (size_t)B * d.L * d.cin / 4;
+            hipLaunchKernelGGL(db_dxsum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, part, n4, d.npc, dx);
+            g = dx;
+        } else {
+            const size_t nrow = (size_t)B * d.L, items = nrow * (d.cinp / 4);
+            const dim3 gd((unsigned)((items + 255) / 256));
+            if (d.cin % 4 == 0 && (reinterpret_cast<uintptr_t>(d_mel) & 15) == 0)
+                hipLaunchKernelGGL(db_dmel_kernel<true>, gd, dim3(256), 0, st, part, nrow, d.cin, d.cinp, d.npc, sj, d_mel);
+            else
+                hipLaunchKernelGGL(db_dmel_kernel<false>, gd, dim3(256), 0, st, part, nrow, d.cin, d.cinp, d.npc, sj, d_mel);
         }
     }
     WN_HIP(h, hipGetLastError());

@@ -12,6 +12,7 @@
 //   it_binit_kernel / it_bhead_kernel   their transposes, flow n -> 1
 //   it_dx_kernel      the start conv transposed, added to the running d x
 //   it_denc_kernel    a flow's d enc rows, unscaled, stored or added into its stack's slice
+//   it_dnoise_kernel  wn_iaf_backward_input: d x of flow 1's input plus the noise's own factor in x
 // The layer inputs l_i live in consecutive slots of the tape: the gate reads slot i, the residual GEMM (RSC epilogue) reads
 // slot i and writes slot i + 1 -- two launches per layer and no copy.
 // Pad columns as in DESIGN.md 12 / 14: the tape may hold anything at [T, Tp), cotangents are exactly zero there, the time
@@ -173,6 +174,13 @@ __global__ __launch_bounds__(256) void it_dx_kernel(const unsigned* __restrict__
     if (wave == 0 && t < T) dx[(size_t)b * T + t] += (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) * scal[1];
 }
 
+// d noise = d x_0 (the chain through the flows) + d_x scale_tot (x = noise scale_tot + mean_tot read the noise itself)
+__global__ __launch_bounds__(256) void it_dnoise_kernel(const float* __restrict__ dx, const float* __restrict__ d_x,
+                                                        const float* __restrict__ Sn, float* __restrict__ d_noise, size_t n) {
+    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < n) d_noise[j] = fmaf(d_x[j], fminf(Sn[j], EXP_7), dx[j]);
+}
+
 // a flow's d enc: G4 rows [B][Cd][RE] (scaled) -> float32 [B][TE][Cd], stored or added
 __global__ __launch_bounds__(256) void it_denc_kernel(const unsigned* __restrict__ g4, const float* __restrict__ scal,
                                                       float* __restrict__ out, long long TE, long long RE, int Cd, int add) {
@@ -269,10 +277,11 @@ struct ItBwdLayout {
     int nchunk, chunk;
     size_t scal, doutf, dout, dh1, dl, dd, dx, dM, dS, aux, xa, denc, slab, slab_floats, total;
 };
-ItBwdLayout it_bwd_layout(const wn_handle* h, const ItLayout& TL, int B) {
+// wg: with the operands and slabs of the weight products (wn_iaf_backward_weights); without them, wn_iaf_backward_input's
+ItBwdLayout it_bwd_layout(const wn_handle* h, const ItLayout& TL, int B, bool wg) {
     const wn_config& c = h->cfg;
     const size_t W = c.width, H = W / 2, Cd = c.deconv_width, cols = (size_t)B * TL.Tp, bt = (size_t)B * TL.T * 4;
-    ItBwdLayout L;
+    ItBwdLayout L{};
     tw_chunks(B, TL.Tp, TL.T, &L.chunk, &L.nchunk);
     size_t o = 0;
     auto carve = [&](size_t bytes) { size_t r = o; o += align_up(bytes, 256); return r; };
@@ -283,13 +292,17 @@ ItBwdLayout it_bwd_layout(const wn_handle* h, const ItLayout& TL, int B) {
     L.dl = carve(cols * W * 4);
     L.dd = carve((size_t)B * W * TL.RD * 4);
     L.dx = carve(bt); L.dM = carve(bt); L.dS = carve(bt);
-    L.aux = carve(cols * TW_AUXC * 4);
-    L.xa = carve(cols * W * 4);
+    if (wg) {
+        L.aux = carve(cols * TW_AUXC * 4);
+        L.xa = carve(cols * W * 4);
+    }
     L.denc = carve((size_t)B * Cd * TL.RE * 4);
-    const size_t layer = W * H + TW_AUXC * W + 3 * W * W + W * Cd + TW_AUXC * W;
-    const size_t head = 32 * (W + TW_AUXC) + W * (W + Cd + TW_AUXC);
-    L.slab_floats = std::max(layer, std::max(head, (size_t)TW_AUXC * W));
-    L.slab = carve((size_t)B * L.nchunk * L.slab_floats * 4);
+    if (wg) {
+        const size_t layer = W * H + TW_AUXC * W + 3 * W * W + W * Cd + TW_AUXC * W;
+        const size_t head = 32 * (W + TW_AUXC) + W * (W + Cd + TW_AUXC);
+        L.slab_floats = std::max(layer, std::max(head, (size_t)TW_AUXC * W));
+        L.slab = carve((size_t)B * L.nchunk * L.slab_floats * 4);
+    }
     L.total = o;
     return L;
 }
@@ -475,7 +488,12 @@ extern "C" size_t wn_iaf_train_workspace_bytes(const wn_handle* h, int B, int F,
 
 extern "C" size_t wn_iaf_backward_weights_workspace_bytes(const wn_handle* h, int B, int F, int64_t T) {
     if (!it_supported(h) || !it_shape_ok(h, B, F, T)) return 0;
-    return it_bwd_layout(h, it_layout(h, B, F, T), B).total;
+    return it_bwd_layout(h, it_layout(h, B, F, T), B, true).total;
+}
+
+extern "C" size_t wn_iaf_backward_input_workspace_bytes(const wn_handle* h, int B, int F, int64_t T) {
+    if (!it_supported(h) || !it_shape_ok(h, B, F, T)) return 0;
+    return it_bwd_layout(h, it_layout(h, B, F, T), B, false).total;
 }
 
 extern "C" int wn_iaf_grad_count(const wn_handle* h) {
@@ -599,13 +617,18 @@ extern "C" int wn_iaf_forward_train_tape(wn_handle* h, const float* noise, const
     return WN_OK;
 }
 
-extern "C" int wn_iaf_backward_weights(wn_handle* h, const void* tape, size_t tape_bytes, const float* d_x,
-                                       const float* d_mean_tot, const float* d_scale_tot, int B, int F, int64_t T, float* grads,
-                                       size_t grads_floats, float* d_encoding, void* ws, size_t ws_bytes, void* stream) {
-    const char* fn = "wn_iaf_backward_weights";
+// The reverse pass over a tape, flow n -> 1.  grads: the weight products and their reductions (null: none of them, nor their
+// operands -- the data path alone, as tb_reverse without wg); d_noise: null, or the chain is carried through flow 1's start
+// conv and the noise's own term added.  What both leave out changes no bit of what remains.
+namespace {
+int it_reverse(wn_handle* h, const char* fn, const void* tape, size_t tape_bytes, const float* d_x, const float* d_mean_tot,
+               const float* d_scale_tot, int B, int F, int64_t T, float* grads, size_t grads_floats, float* d_noise,
+               float* d_encoding, void* ws, size_t ws_bytes, void* stream) {
+    const bool wg = grads != nullptr;
     if (int rc = it_check(h, fn)) return rc;
     if (int rc = it_shape_check(h, fn, B, F, T)) return rc;
-    if (!tape || !d_x || !d_mean_tot || !d_scale_tot || !grads || !ws) return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
+    if (!tape || !d_x || !d_mean_tot || !d_scale_tot || (!grads && !d_noise) || !ws)
+        return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
     const IafTrainPack& P = h->iaf_train;
     {
         uint64_t ser = 0;
@@ -621,11 +644,11 @@ extern "C" int wn_iaf_backward_weights(wn_handle* h, const void* tape, size_t ta
     if (tape_bytes < TL.total)
         return wn_fail(h, WN_EINVAL, "%s: a tape of %zu bytes cannot hold the training tape of B = %d, F = %d, T = %lld "
                        "(%zu bytes)", fn, tape_bytes, B, F, (long long)T, TL.total);
-    const std::vector<WnGradEntry> tab = it_grad_table(h);
-    if (grads_floats < wn_grad_floats(tab))
+    const std::vector<WnGradEntry> tab = wg ? it_grad_table(h) : std::vector<WnGradEntry>();
+    if (wg && grads_floats < wn_grad_floats(tab))
         return wn_fail(h, WN_ENOMEM, "%s: grads holds %zu floats, the gradients need %zu", fn, grads_floats, wn_grad_floats(tab));
-    const ItBwdLayout BL = it_bwd_layout(h, TL, B);
-    if ((long long)B * BL.nchunk > 65535) return wn_fail(h, WN_EINVAL, "%s: B = %d needs more than 65535 slabs", fn, B);
+    const ItBwdLayout BL = it_bwd_layout(h, TL, B, wg);
+    if (wg && (long long)B * BL.nchunk > 65535) return wn_fail(h, WN_EINVAL, "%s: B = %d needs more than 65535 slabs", fn, B);
     if (ws_bytes < BL.total) return wn_fail(h, WN_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, BL.total);
     const WnWork work(h);
     const wn_config& c = h->cfg;
@@ -675,7 +698,7 @@ extern "C" int wn_iaf_backward_weights(wn_handle* h, const void* tape, size_t ta
         // the operand scale of this flow's cotangents
         wn_pow2_scale(doutf, (long long)B * T * 2, scal + 4, scal, nullptr, st);
         wn_tb_dout(doutf, scal, dout, B, T, Tp, 2, Kp, st);
-        wn_tw_aux(xs, aux, B, T, Tp, st);
+        if (wg) wn_tw_aux(xs, aux, B, T, Tp, st);
         if (d_encoding) WN_HIP(h, hipMemsetAsync(denc, 0, (size_t)B * Cd * RE * 4, st));
         {   // d relu(h1) = W_out2^T d out, masked by h1 > 0
             TgArgs a = args(fl.out2_t, dh1, Tp, 0, W);
@@ -683,8 +706,8 @@ extern "C" int wn_iaf_backward_weights(wn_handle* h, const void* tape, size_t ta
             a.tape = at<float>(tp, fo.h1); a.tape_bstride = (long long)W * Tp; a.tape_nmb = W / 16;
             wn_tg_launch(TG_EPI_MASK, a, fl.out2_t.mtiles, B, Tp, st);
         }
-        wn_tw_act(at<float>(tp, fo.h1), (long long)W * Tp, W / 16, 0, xa, B, T, Tp, W, 0, st);      // relu(h1)
-        {
+        if (wg) {
+            wn_tw_act(at<float>(tp, fo.h1), (long long)W * Tp, W / 16, 0, xa, B, T, Tp, W, 0, st);      // relu(h1)
             TwBatch b;
             const unsigned* rl = at<unsigned>(tp, fo.rl);
             const long long o2w = b.add(dout, Kp, Tp, xa, W, Tp, 0);
@@ -720,8 +743,8 @@ extern "C" int wn_iaf_backward_weights(wn_handle* h, const void* tape, size_t ta
                 a.bg_rows = H % 64 ? H : 0;             // width 64: the tile's upper 32 rows are padding
                 wn_tg_launch(TG_EPI_BGATE, a, tl.res_t.mtiles, B, Tp, st);
             }
-            wn_tw_act(gt, (long long)W * Tp, W / 16, H / 16, xa, B, T, Tp, H, 1, st);               // m_i = sigma * tanh
-            {
+            if (wg) {
+                wn_tw_act(gt, (long long)W * Tp, W / 16, H / 16, xa, B, T, Tp, H, 1, st);           // m_i = sigma * tanh
                 TwBatch b;
                 const long long rw = b.add(dl, W, Tp, xa, H, Tp, 0);
                 const long long rb = b.add(dl, W, Tp, aux, TW_AUXC, Tp, 0);
@@ -748,14 +771,14 @@ extern "C" int wn_iaf_backward_weights(wn_handle* h, const void* tape, size_t ta
                 wn_tg_launch(TG_EPI_RS, a, tl.gate_t.mtiles, B, Tp, st);
             }
         }
-        {   // dl = d l_0: the start conv's variables, and its transpose into d x_{k-1}
+        if (wg) {   // dl = d l_0: the start conv's variables, and its transpose into d x_{k-1}
             TwBatch b;
             const long long cs = b.add(dl, W, Tp, aux, TW_AUXC, Tp, 0);
             b.red(cs, 3, W, W, wn_grad_off(tab, p + "start_conv/W"), W);
             b.red(cs + 3 * W, 1, W, W, wn_grad_off(tab, p + "start_conv/biases"), W);
             if (int rc = b.run(h, run, st)) return rc;
         }
-        if (k > 0)
+        if (k > 0 || d_noise)   // flow 1's input is the noise
             hipLaunchKernelGGL(it_dx_kernel, dim3((unsigned)((T + 63) / 64), B), dim3(256), 0, st, dl, h->d_blob + fl.start_off, scal,
                                dx, W, (long long)T, Tp);
         if (d_encoding) {
@@ -765,6 +788,26 @@ extern "C" int wn_iaf_backward_weights(wn_handle* h, const void* tape, size_t ta
                                d_encoding + (size_t)fl.deconv_stack * B * TL.TE * Cd, TL.TE, RE, Cd, add);
         }
     }
+    if (d_noise) {
+        const size_t n = (size_t)B * T;
+        hipLaunchKernelGGL(it_dnoise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dx, d_x,
+                           at<float>(tp, TL.f[NF - 1].S), d_noise, n);
+    }
     WN_HIP(h, hipGetLastError());
     return WN_OK;
+}
+}  // namespace
+
+extern "C" int wn_iaf_backward_weights(wn_handle* h, const void* tape, size_t tape_bytes, const float* d_x,
+                                       const float* d_mean_tot, const float* d_scale_tot, int B, int F, int64_t T, float* grads,
+                                       size_t grads_floats, float* d_encoding, void* ws, size_t ws_bytes, void* stream) {
+    return it_reverse(h, "wn_iaf_backward_weights", tape, tape_bytes, d_x, d_mean_tot, d_scale_tot, B, F, T, grads, grads_floats,
+                      nullptr, d_encoding, ws, ws_bytes, stream);
+}
+
+extern "C" int wn_iaf_backward_input(wn_handle* h, const void* tape, size_t tape_bytes, const float* d_x, const float* d_mean_tot,
+                                     const float* d_scale_tot, int B, int F, int64_t T, float* d_noise, float* d_encoding, void* ws,
+                                     size_t ws_bytes, void* stream) {
+    return it_reverse(h, "wn_iaf_backward_input", tape, tape_bytes, d_x, d_mean_tot, d_scale_tot, B, F, T, nullptr, 0, d_noise,
+                      d_encoding, ws, ws_bytes, stream);
 }

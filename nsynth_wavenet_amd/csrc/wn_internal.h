@@ -48,6 +48,10 @@ struct DeconvLayerPack {
     // available (the first layer of a stack needs none)
     size_t wt_off = 0;
     float wt_inv_scale = 1.f;
+    // wn_deconv_backward_input: the FIRST layer's W^T [k][cinp][cout], cinp = cin rounded up to 64 with zero rows behind cin,
+    // packed after every wt_off pack; 0 = not available (set on the first layer of a stack only)
+    size_t wt_in_off = 0;
+    float wt_in_inv_scale = 1.f;
 };
 
 struct DeconvStackPack {

@@ -193,14 +193,20 @@ __global__ __launch_bounds__(TR_NT) void tr_deconv_h_kernel(DeconvHArgs a) {
     }
     a.dst[i] = (uint32_t)hh[0] | ((uint32_t)hh[1] << 16);
 }
-// W^T as two planes of halves [k][ci][co] (wn_pack_deconv_bwd); one thread per pair of neighbouring co
+// W^T as two planes of halves [k][ci][co] (wn_pack_deconv_bwd); one thread per pair of neighbouring co.  rows: ci rows per k
+// of the pack -- cin, or cin rounded up to 64 for the first layer's pack, whose rows behind cin are zero
 __global__ __launch_bounds__(TR_NT) void tr_deconv_t_kernel(const float* __restrict__ W, unsigned* __restrict__ dst, float sc, int K,
-                                                            int cin, int cout) {
-    const size_t n2 = (size_t)K * cin * cout / 2;
+                                                            int cin, int rows, int cout) {
+    const size_t n2 = (size_t)K * rows * cout / 2;
     const size_t i = (size_t)blockIdx.x * TR_NT + threadIdx.x;
     if (i >= n2) return;
     const size_t at = 2 * i;
-    const int co = (int)(at % cout), ci = (int)((at / cout) % cin), k = (int)(at / cout / cin);
+    const int co = (int)(at % cout), ci = (int)((at / cout) % rows), k = (int)(at / cout / rows);
+    if (ci >= cin) {
+        dst[i] = 0u;
+        dst[n2 + i] = 0u;
+        return;
+    }
     const float v0 = __fmul_rn(sc, W[((size_t)k * cout + co) * cin + ci]);
     const float v1 = __fmul_rn(sc, W[((size_t)k * cout + co + 1) * cin + ci]);
     dst[i] = (uint32_t)split_half(v0, 0) | ((uint32_t)split_half(v1, 0) << 16);
@@ -324,7 +330,14 @@ void wn_repack_deconv_split(wn_handle* h, DeconvStackPack& sp, const std::vector
             lp.wt_inv_scale = 1.0f / sc;
             const size_t n2 = (size_t)lp.K * lp.cin * lp.cout / 2;
             hipLaunchKernelGGL(tr_deconv_t_kernel, dim3(tr_blocks(n2)), dim3(TR_NT), 0, st, W,
-                               reinterpret_cast<unsigned*>(blob + lp.wt_off), sc, lp.K, lp.cin, lp.cout);
+                               reinterpret_cast<unsigned*>(blob + lp.wt_off), sc, lp.K, lp.cin, lp.cin, lp.cout);
+        }
+        if (lp.wt_in_off) {
+            lp.wt_in_inv_scale = 1.0f / sc;
+            const int rows = (lp.cin + 63) / 64 * 64;
+            const size_t n2 = (size_t)lp.K * rows * lp.cout / 2;
+            hipLaunchKernelGGL(tr_deconv_t_kernel, dim3(tr_blocks(n2)), dim3(TR_NT), 0, st, W,
+                               reinterpret_cast<unsigned*>(blob + lp.wt_in_off), sc, lp.K, lp.cin, rows, lp.cout);
         }
     }
 }

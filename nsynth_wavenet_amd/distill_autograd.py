@@ -26,6 +26,32 @@ class TeacherForward(torch.autograd.Function):
         return dwav, None, None
 
 
+class IafFeedForward(torch.autograd.Function):
+    """(mel [B,F,n_mel], noise [B,T]) -> (x, mean_tot, scale_tot) of a student Engine's tape forward (DESIGN.md 26);
+    differentiable in both inputs.  The student is frozen here: its weights get their gradients from
+    ParallelWavenet.loss_and_weight_grads.  stacks: [(engine, scope)] per slice of d_encoding, in the order of
+    Engine.iaf_stack_scopes() -- a teacher-owned stack is differentiated under the teacher's handle."""
+
+    @staticmethod
+    def forward(ctx, mel, noise, eng, stacks):
+        mel, noise = eng._dev(mel.detach()), eng._dev(noise.detach())
+        ff, tape = eng.iaf_forward_train_tape(mel, noise=noise)
+        ctx.eng, ctx.tape, ctx.stacks, ctx.mel = eng, tape, stacks, mel
+        return ff['x'], ff['mean_tot'], ff['scale_tot']
+
+    @staticmethod
+    def backward(ctx, d_x, d_mean_tot, d_scale_tot):
+        want_mel = ctx.needs_input_grad[0]
+        res = ctx.eng.iaf_backward_input(ctx.tape, d_x, d_mean_tot, d_scale_tot, want_encoding=want_mel)
+        d_mel = None
+        if want_mel:
+            for s, (eng, scope) in enumerate(ctx.stacks):
+                g = eng.deconv_backward_input(ctx.mel, res['d_encoding'][s], scope)
+                d_mel = g if d_mel is None else d_mel + g
+        ctx.tape = None
+        return d_mel, res['d_noise'] if ctx.needs_input_grad[1] else None, None, None
+
+
 class TeacherLogProb(torch.autograd.Function):
     """(out_params [B,T,out_width], wav [B,T]) -> log_probs [B,T] of a teacher Engine.  The gradient to wav is
     the one through the TARGET (zero for mu-law and ce teachers); the one through the network input is TeacherForward's."""

@@ -730,6 +730,27 @@ class Engine(object):
             grads = self._grad_views(flat, self.iaf_grad_table())
         return {'grads': grads, 'flat_grads': flat[:n], 'd_encoding': denc}
 
+    def iaf_backward_input(self, tape, d_x, d_mean_tot, d_scale_tot, want_encoding=True, n_frames=None):
+        """iaf_backward_weights' reverse pass on the same tape without the weight products: the cotangents of
+        the three returned tensors -> {'d_noise': [B,T], the gradient of the draw iaf_forward_train_tape was given,
+        'd_encoding': [n_stacks, B, F frame_shift, deconv_width] (iaf_backward_weights' bits) or None}."""
+        g = [self._dev(v) for v in (d_x, d_mean_tot, d_scale_tot)]
+        if g[0].dim() != 2 or any(tuple(v.shape) != tuple(g[0].shape) for v in g):
+            raise ValueError('iaf_backward_input: d_x, d_mean_tot and d_scale_tot must be [B,T]')
+        F = int(n_frames if n_frames is not None else self._train_frames.get(tape.data_ptr(), 0))
+        if F < 1:
+            raise ValueError('iaf_backward_input: pass n_frames for a tape this engine object did not write')
+        B, T = int(g[0].shape[0]), int(g[0].shape[1])
+        with torch.cuda.device(self.device):
+            dn = torch.empty((B, T), dtype=torch.float32, device=self.device)
+            denc = torch.empty((self.iaf_n_stacks(), B, F * self.frame_shift, int(self.hp.deconv_width)), dtype=torch.float32,
+                               device=self.device) if want_encoding else None
+            ws = torch.empty(max(int(self.lib.wn_iaf_backward_input_workspace_bytes(self._h, B, F, T)), 256),
+                             dtype=torch.uint8, device=self.device)
+            self._check(self.lib.wn_iaf_backward_input(self._h, _ptr(tape), tape.numel(), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]),
+                                                       B, F, T, _ptr(dn), _ptr(denc), _ptr(ws), ws.numel(), self._stream()))
+        return {'d_noise': dn, 'd_encoding': denc}
+
     # ---- reverse pass of the upsampler (DESIGN.md 15) ----
     def deconv_grad_table(self, scope=''):
         """[(tf variable name, float offset, TF shape)] of deconv_backward's flat gradient buffer: per layer
@@ -759,6 +780,27 @@ class Engine(object):
                                                     self._stream()))
             grads = self._grad_views(flat, self.deconv_grad_table(scope))
         return {'grads': grads, 'flat_grads': flat[:n]}
+
+    def deconv_backward_input(self, mel, d_encoding, scope=''):
+        """VJP of deconv(mel, scope) with respect to mel: mel [B,F,n_mel] and a cotangent d_encoding
+        [B, F frame_shift, deconv_width] -> d_mel [B,F,n_mel].  Reruns the stack's forward like deconv_backward; no tape, no
+        weight gradients."""
+        mel, g = self._dev(mel), self._dev(d_encoding)
+        if mel.dim() != 3 or int(mel.shape[2]) != self.n_mel:
+            raise ValueError('deconv_backward_input: mel must be [B,F,{}]'.format(self.n_mel))
+        B, F = int(mel.shape[0]), int(mel.shape[1])
+        want = (B, F * self.frame_shift, int(self.hp.deconv_width))
+        if tuple(g.shape) != want:
+            raise ValueError('deconv_backward_input: d_encoding must be [B, F frame_shift, deconv_width] = {}, got {}'.format(
+                list(want), list(g.shape)))
+        sc = scope.encode()
+        with torch.cuda.device(self.device):
+            d_mel = torch.empty((B, F, self.n_mel), dtype=torch.float32, device=self.device)
+            ws = torch.empty(max(int(self.lib.wn_deconv_backward_input_workspace_bytes(self._h, sc, B, F)), 256),
+                             dtype=torch.uint8, device=self.device)
+            self._check(self.lib.wn_deconv_backward_input(self._h, sc, _ptr(mel), _ptr(g), B, F, _ptr(d_mel), _ptr(ws),
+                                                          ws.numel(), self._stream()))
+        return d_mel
 
     # ---- training step on the device (DESIGN.md 16; the trainer is train.TeacherTrainer) ----
     def teacher_set_weights(self, params, up_params=None):

@@ -74,13 +74,38 @@ class ParallelWavenet(object):
         """inputs: {'mel': [B,F,80]} (numpy or torch).  Returns device tensors
         x, mean_tot, scale_tot, log_scale_tot, rand_input, each [B,T].
         `noise` injects the logistic/normal draws (the reference draws them inside
-        the graph, unseeded); `seed` drives the on-device Philox generator otherwise."""
+        the graph, unseeded); `seed` drives the on-device Philox generator otherwise.
+        When grad mode is on and inputs['mel'] or `noise` is a tensor that requires grad, x, mean_tot and scale_tot come
+        from the tape forward instead (Engine.iaf_forward_train_tape: the values loss_and_weight_grads differentiates)
+        and carry a gradient to those inputs; a drawn noise (noise=None) gets none.  The tape forward's
+        refusals (mu-law, weight norm, a width that is no multiple of 64) surface as they are."""
+        if torch.is_grad_enabled() and (_req(inputs, 'mel') or _req({'noise': noise}, 'noise')):
+            return self._feed_forward_grad(inputs['mel'], noise, seed)
         out = self.engine.iaf_generate(inputs['mel'], noise=noise, seed=seed,
                                        want=('x', 'mean_tot', 'scale_tot', 'rand_input'))
         # log_scale_tot = min(sum_k log scale_k, 7) == log(min(prod_k scale_k, e^7)): a derived
         # diagnostic the generation path never consumes (only the training losses do).
         out['log_scale_tot'] = torch.log(out['scale_tot'])
         return {k: out[k] for k in ('x', 'mean_tot', 'scale_tot', 'log_scale_tot', 'rand_input')}
+
+    def _input_grad_stacks(self):
+        """[(engine, scope)] that differentiates each slice of d_encoding with respect to mel.  A teacher-owned stack
+        (use_teacher_deconv) goes to the teacher's handle; without a teacher object, to this handle's copy of the same
+        variables ('iaf_share')."""
+        eng = self.engine
+        if self.use_teacher_deconv:
+            return [(self.teacher.engine, '')] if self.teacher is not None else [(eng, 'iaf_share')]
+        return [(eng, scope) for scope in eng.iaf_stack_scopes()]
+
+    def _feed_forward_grad(self, mel, noise, seed):
+        eng = self.engine
+        mel = eng._dev(mel)           # differentiable for a tensor: the gradient returns to the caller's device and dtype
+        if noise is None:
+            noise = eng.iaf_generate(mel.detach(), seed=seed, want=('rand_input',), check_range=False)['rand_input']
+        noise = eng._dev(noise)
+        x, mean_tot, scale_tot = dag.IafFeedForward.apply(mel, noise, eng, self._input_grad_stacks())
+        return {'x': x, 'mean_tot': mean_tot, 'scale_tot': scale_tot, 'log_scale_tot': torch.log(scale_tot),
+                'rand_input': noise.detach()}
 
     def encode(self, inputs, **kw):
         """The inverse of feed_forward.  inputs: 'mel' [B,F,80] and the audio as 'x' (feed_forward's key)
