@@ -624,6 +624,38 @@ WN_API int wn_iaf_backward_input(wn_handle* h, const void* tape, size_t tape_byt
                                  const float* d_scale_tot, int B, int F, int64_t T, float* d_noise, float* d_encoding, void* ws,
                                  size_t ws_bytes, void* stream);
 
+/* ---- the gradient of the student's log-likelihood.  log p(x) = log f(z) - log scale_tot at z = encode(x).
+ * wn_iaf_latent_log_prob_grad is wn_iaf_latent_log_prob's counterpart: for a cotangent d_log_prob [B,T] of log p (NULL: the
+ * constant -1 / (B T), the cotangent of -mean log p)
+ *   g_z = d_log_prob (log f)'(z)      (log f)' = -tanh(z / 2) for loss_type logistic, -z for gauss
+ *   d_scale_tot = -d_log_prob / scale_tot
+ * both [B,T] float32, evaluated in double and rounded once; scale_tot is taken as given, as wn_iaf_latent_log_prob takes it.
+ * Refused: a teacher handle, a null z / scale_tot / g_z / d_scale_tot, B < 1 or T < 1. */
+WN_API int wn_iaf_latent_log_prob_grad(wn_handle* h, const float* z, const float* scale_tot, int B, int64_t T,
+                                       const float* d_log_prob, float* g_z, float* d_scale_tot, void* stream);
+/* The adjoint of the inverse.  On a tape wn_iaf_forward_train_tape wrote at noise = z, with A = d x / d noise (lower
+ * triangular, diagonal scale_tot), the call solves A^T lam = g_z + (d mean_tot / d noise)^T d_mean_tot + (d scale_tot /
+ * d noise)^T d_scale_tot by n_sweeps Jacobi sweeps, enqueued without a host synchronisation:
+ *   lam <- lam + (g_z + r) / min(scale_tot, e^7),   r = d_noise of wn_iaf_backward_input(tape, -lam, d_mean_tot, d_scale_tot)
+ * A^T is upper triangular: after k sweeps the last k samples of a row are exact, after T sweeps the row.  With the outputs of
+ * wn_iaf_latent_log_prob_grad, lam is the gradient with respect to x, and wn_iaf_backward_weights(tape, -lam, 0, d_scale_tot)
+ * gives those of the weights and the encoding.
+ *   lam         [B,T]: the starting iterate on entry, the last sweep's on return
+ *   d_mean_tot  [B,T] or NULL (zero)
+ *   tol         a row has converged when its last sweep had max |lam' - lam| <= tol max |lam'|
+ *   resid       float [B][2]: max |lam' - lam| and max |lam'| of the row in the last sweep
+ *   counts      int32 [4]: [0] values of the last sweep that were not finite and were replaced by 0; [1] rows above tol in
+ *               the last sweep; [2] the first sweep of this call, counted from 1, after which every row had converged and
+ *               nothing was replaced, 0 if none -- the call's later sweeps then change nothing: lam and resid are that
+ *               sweep's; [3] 0
+ * No atomics: a repeated call gives the same bits.  Refused as wn_iaf_backward_input refuses (handle, shape, tape), and:
+ * n_sweeps < 1, tol < 0 or NaN, a null tape / g_z / d_scale_tot / lam / resid / counts / workspace (WN_EINVAL); a workspace
+ * below wn_iaf_adjoint_workspace_bytes (WN_ENOMEM), which is 0 for a handle or a shape the call refuses. */
+WN_API size_t wn_iaf_adjoint_workspace_bytes(const wn_handle* h, int B, int F, int64_t T);
+WN_API int wn_iaf_adjoint(wn_handle* h, const void* tape, size_t tape_bytes, const float* g_z, const float* d_mean_tot,
+                          const float* d_scale_tot, int B, int F, int64_t T, float* lam, int n_sweeps, float tol, float* resid,
+                          int32_t* counts, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- reverse pass of the upsampler: the gradients of trans_conv_j/kernel and trans_conv_j/bias of the deconv
  * stack `scope` ("" for a teacher; "iaf_share", "iaf_1" ... for a student, as in wn_deconv) from mel [B,F,n_mel] and a
  * cotangent d_enc [B, F frame_shift, deconv_width] of wn_deconv's output, e.g. d_encoding of wn_teacher_backward_weights.

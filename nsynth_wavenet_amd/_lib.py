@@ -32,7 +32,8 @@ SYMBOLS = ['wn_abi_version', 'wn_create', 'wn_set_weight', 'wn_finalize', 'wn_ia
            'wn_iaf_encode_workspace_bytes', 'wn_iaf_encode', 'wn_iaf_latent_log_prob',
            'wn_train_batch',
            'wn_deconv_backward_input_workspace_bytes', 'wn_deconv_backward_input',
-           'wn_iaf_backward_input_workspace_bytes', 'wn_iaf_backward_input']
+           'wn_iaf_backward_input_workspace_bytes', 'wn_iaf_backward_input',
+           'wn_iaf_latent_log_prob_grad', 'wn_iaf_adjoint_workspace_bytes', 'wn_iaf_adjoint']
 
 
 class WindowRow(ctypes.Structure):
@@ -154,12 +155,14 @@ def load():
     lib.wn_iaf_grad_floats.argtypes = [vp]
     lib.wn_iaf_grad_floats.restype = sz
     for name in ('wn_iaf_train_tape_bytes', 'wn_iaf_train_workspace_bytes', 'wn_iaf_backward_weights_workspace_bytes',
-                 'wn_iaf_backward_input_workspace_bytes'):
+                 'wn_iaf_backward_input_workspace_bytes', 'wn_iaf_adjoint_workspace_bytes'):
         getattr(lib, name).argtypes = [vp, i32, i32, i64]
         getattr(lib, name).restype = sz
     lib.wn_iaf_forward_train_tape.argtypes = [vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, sz, vp, sz, vp]
     lib.wn_iaf_backward_weights.argtypes = [vp, vp, sz, vp, vp, vp, i32, i32, i64, vp, sz, vp, vp, sz, vp]
     lib.wn_iaf_backward_input.argtypes = [vp, vp, sz, vp, vp, vp, i32, i32, i64, vp, vp, vp, sz, vp]
+    lib.wn_iaf_latent_log_prob_grad.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp, vp]
+    lib.wn_iaf_adjoint.argtypes = [vp, vp, sz, vp, vp, vp, i32, i32, i64, vp, i32, c.c_float, vp, vp, vp, sz, vp]
     lib.wn_deconv_grad_count.argtypes = [vp, c.c_char_p]
     lib.wn_deconv_grad_info.argtypes = [vp, c.c_char_p, i32, c.c_char_p, sz, c.POINTER(i64), c.POINTER(i64), c.POINTER(i32)]
     lib.wn_deconv_grad_floats.argtypes = [vp, c.c_char_p]

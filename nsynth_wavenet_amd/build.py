@@ -25,7 +25,7 @@ CODEGEN_FLAGS = ['-O3', '-std=c++17', '-fno-slp-vectorize']
 # The C ABI of include/wnhip.h (WN_API = default visibility) is the library's whole dynamic symbol table: everything
 # else -- the C++ helpers shared by the translation units, STL instantiations -- is local to it.
 VISIBILITY_FLAGS = ['-fvisibility=hidden', '-fvisibility-inlines-hidden']
-SOURCES = ['wn_host.cpp', 'wn_deconv.hip', 'wn_deconv_bwd.hip', 'wn_iaf.hip', 'wn_iaf_call.hip', 'wn_iaf_h.hip', 'wn_iaf_c.hip', 'wn_iaf_g.hip', 'wn_iaf_f.hip', 'wn_iaf_x.hip', 'wn_iaf_train.hip', 'wn_iaf_repack.hip', 'wn_ar.hip', 'wn_teacher.hip', 'wn_teacher_bwd.hip', 'wn_teacher_wgrad.hip', 'wn_teacher_dropout.hip', 'wn_train.hip', 'wn_scale.hip', 'wn_mel.hip', 'wn_batch.hip', 'wn_distill.hip']
+SOURCES = ['wn_host.cpp', 'wn_deconv.hip', 'wn_deconv_bwd.hip', 'wn_iaf.hip', 'wn_iaf_call.hip', 'wn_iaf_h.hip', 'wn_iaf_c.hip', 'wn_iaf_g.hip', 'wn_iaf_f.hip', 'wn_iaf_x.hip', 'wn_iaf_train.hip', 'wn_iaf_nll.hip', 'wn_iaf_repack.hip', 'wn_ar.hip', 'wn_teacher.hip', 'wn_teacher_bwd.hip', 'wn_teacher_wgrad.hip', 'wn_teacher_dropout.hip', 'wn_train.hip', 'wn_scale.hip', 'wn_mel.hip', 'wn_batch.hip', 'wn_distill.hip']
 HEADERS = ['wn_internal.h', 'wn_teacher.h', 'wn_codec.h', 'wn_g4.h', 'wn_dropout.h', 'wn_mol.h', 'wn_pack_h.h', 'wn_repack.h', 'wn_mfma_h.h', 'wn_iaf_c.h', 'wn_mel.h', os.path.join(ROOT, 'include', 'wnhip.h')]
 
 

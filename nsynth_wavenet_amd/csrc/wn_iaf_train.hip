@@ -617,40 +617,32 @@ extern "C" int wn_iaf_forward_train_tape(wn_handle* h, const float* noise, const
     return WN_OK;
 }
 
-// The reverse pass over a tape, flow n -> 1.  grads: the weight products and their reductions (null: none of them, nor their
-// operands -- the data path alone, as tb_reverse without wg); d_noise: null, or the chain is carried through flow 1's start
-// conv and the noise's own term added.  What both leave out changes no bit of what remains.
 namespace {
-int it_reverse(wn_handle* h, const char* fn, const void* tape, size_t tape_bytes, const float* d_x, const float* d_mean_tot,
-               const float* d_scale_tot, int B, int F, int64_t T, float* grads, size_t grads_floats, float* d_noise,
-               float* d_encoding, void* ws, size_t ws_bytes, void* stream) {
-    const bool wg = grads != nullptr;
-    if (int rc = it_check(h, fn)) return rc;
-    if (int rc = it_shape_check(h, fn, B, F, T)) return rc;
-    if (!tape || !d_x || !d_mean_tot || !d_scale_tot || (!grads && !d_noise) || !ws)
-        return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
-    const IafTrainPack& P = h->iaf_train;
-    {
-        uint64_t ser = 0;
-        int tB = 0, tF = 0;
-        long long tT = 0;
-        if (!wn_tape_lookup(tape, &ser, &tB, &tT, &tF) || ser != P.serial)
-            return wn_fail(h, WN_EINVAL, "%s: the tape was not written by wn_iaf_forward_train_tape of this handle", fn);
-        if (tB != B || tT != (long long)T)
-            return wn_fail(h, WN_EINVAL, "%s: the tape holds B = %d, T = %lld, not B = %d, T = %lld", fn, tB, tT, B, (long long)T);
-        if (tF != F) return wn_fail(h, WN_EINVAL, "%s: the tape holds F = %d mel frames, not %d", fn, tF, F);
-    }
-    const ItLayout TL = it_layout(h, B, F, T);
+// the tape belongs to this handle and this shape
+int it_tape_check(wn_handle* h, const char* fn, const void* tape, size_t tape_bytes, const ItLayout& TL, int B, int F, int64_t T) {
+    uint64_t ser = 0;
+    int tB = 0, tF = 0;
+    long long tT = 0;
+    if (!wn_tape_lookup(tape, &ser, &tB, &tT, &tF) || ser != h->iaf_train.serial)
+        return wn_fail(h, WN_EINVAL, "%s: the tape was not written by wn_iaf_forward_train_tape of this handle", fn);
+    if (tB != B || tT != (long long)T)
+        return wn_fail(h, WN_EINVAL, "%s: the tape holds B = %d, T = %lld, not B = %d, T = %lld", fn, tB, tT, B, (long long)T);
+    if (tF != F) return wn_fail(h, WN_EINVAL, "%s: the tape holds F = %d mel frames, not %d", fn, tF, F);
     if (tape_bytes < TL.total)
         return wn_fail(h, WN_EINVAL, "%s: a tape of %zu bytes cannot hold the training tape of B = %d, F = %d, T = %lld "
                        "(%zu bytes)", fn, tape_bytes, B, F, (long long)T, TL.total);
-    const std::vector<WnGradEntry> tab = wg ? it_grad_table(h) : std::vector<WnGradEntry>();
-    if (wg && grads_floats < wn_grad_floats(tab))
-        return wn_fail(h, WN_ENOMEM, "%s: grads holds %zu floats, the gradients need %zu", fn, grads_floats, wn_grad_floats(tab));
-    const ItBwdLayout BL = it_bwd_layout(h, TL, B, wg);
-    if (wg && (long long)B * BL.nchunk > 65535) return wn_fail(h, WN_EINVAL, "%s: B = %d needs more than 65535 slabs", fn, B);
-    if (ws_bytes < BL.total) return wn_fail(h, WN_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, BL.total);
-    const WnWork work(h);
+    return WN_OK;
+}
+
+// The reverse pass over a tape, flow n -> 1.  grads: the weight products and their reductions (null: none of them, nor their
+// operands -- the data path alone, as tb_reverse without wg); d_noise: null, or the chain is carried through flow 1's start
+// conv and the noise's own term added.  What both leave out changes no bit of what remains.
+// These are the launches alone: the caller has checked everything (it_reverse, wn_iaf_adjoint) and holds the work lock.
+int it_reverse_run(wn_handle* h, const char* fn, const void* tape, const ItLayout& TL, const ItBwdLayout& BL,
+                   const std::vector<WnGradEntry>& tab, const float* d_x, const float* d_mean_tot, const float* d_scale_tot, int B,
+                   int64_t T, float* grads, float* d_noise, float* d_encoding, void* ws, void* stream) {
+    const bool wg = grads != nullptr;
+    const IafTrainPack& P = h->iaf_train;
     const wn_config& c = h->cfg;
     const int W = c.width, H = W / 2, Cd = c.deconv_width, NF = c.n_flows, Kp = 32;
     const long long Tp = TL.Tp, RS = TL.RS, RD = TL.RD, RE = TL.RE;
@@ -796,7 +788,45 @@ int it_reverse(wn_handle* h, const char* fn, const void* tape, size_t tape_bytes
     WN_HIP(h, hipGetLastError());
     return WN_OK;
 }
+
+int it_reverse(wn_handle* h, const char* fn, const void* tape, size_t tape_bytes, const float* d_x, const float* d_mean_tot,
+               const float* d_scale_tot, int B, int F, int64_t T, float* grads, size_t grads_floats, float* d_noise,
+               float* d_encoding, void* ws, size_t ws_bytes, void* stream) {
+    const bool wg = grads != nullptr;
+    if (int rc = it_check(h, fn)) return rc;
+    if (int rc = it_shape_check(h, fn, B, F, T)) return rc;
+    if (!tape || !d_x || !d_mean_tot || !d_scale_tot || (!grads && !d_noise) || !ws)
+        return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
+    const ItLayout TL = it_layout(h, B, F, T);
+    if (int rc = it_tape_check(h, fn, tape, tape_bytes, TL, B, F, T)) return rc;
+    const std::vector<WnGradEntry> tab = wg ? it_grad_table(h) : std::vector<WnGradEntry>();
+    if (wg && grads_floats < wn_grad_floats(tab))
+        return wn_fail(h, WN_ENOMEM, "%s: grads holds %zu floats, the gradients need %zu", fn, grads_floats, wn_grad_floats(tab));
+    const ItBwdLayout BL = it_bwd_layout(h, TL, B, wg);
+    if (wg && (long long)B * BL.nchunk > 65535) return wn_fail(h, WN_EINVAL, "%s: B = %d needs more than 65535 slabs", fn, B);
+    if (ws_bytes < BL.total) return wn_fail(h, WN_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, BL.total);
+    const WnWork work(h);
+    return it_reverse_run(h, fn, tape, TL, BL, tab, d_x, d_mean_tot, d_scale_tot, B, T, grads, d_noise, d_encoding, ws, stream);
+}
 }  // namespace
+
+// ---- for wn_iaf_adjoint (wn_iaf_nll.hip): the checks of a reverse pass by name, and its data path alone ----
+int wn_iaf_reverse_check(wn_handle* h, const char* fn, int B, int F, int64_t T) {
+    if (int rc = it_check(h, fn)) return rc;
+    return it_shape_check(h, fn, B, F, T);
+}
+int wn_iaf_reverse_tape_check(wn_handle* h, const char* fn, const void* tape, size_t tape_bytes, int B, int F, int64_t T) {
+    return it_tape_check(h, fn, tape, tape_bytes, it_layout(h, B, F, T), B, F, T);
+}
+const float* wn_iaf_tape_scale_prod(const wn_handle* h, const void* tape, int B, int F, int64_t T) {
+    return at<float>(const_cast<void*>(tape), it_layout(h, B, F, T).f[h->cfg.n_flows - 1].S);
+}
+int wn_iaf_reverse_input_run(wn_handle* h, const char* fn, const void* tape, const float* d_x, const float* d_mean_tot,
+                             const float* d_scale_tot, int B, int F, int64_t T, float* d_noise, void* ws, void* stream) {
+    const ItLayout TL = it_layout(h, B, F, T);
+    return it_reverse_run(h, fn, tape, TL, it_bwd_layout(h, TL, B, false), std::vector<WnGradEntry>(), d_x, d_mean_tot, d_scale_tot,
+                          B, T, nullptr, d_noise, nullptr, ws, stream);
+}
 
 extern "C" int wn_iaf_backward_weights(wn_handle* h, const void* tape, size_t tape_bytes, const float* d_x,
                                        const float* d_mean_tot, const float* d_scale_tot, int B, int F, int64_t T, float* grads,

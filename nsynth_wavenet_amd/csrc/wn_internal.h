@@ -269,6 +269,14 @@ std::vector<WnGradEntry> wn_iaf_grad_table(const wn_handle* h);            // wn
 int wn_iaf_train_check(wn_handle* h, const char* fn);                       // ... and what its training calls refuse, by name
 int wn_grad_info(const wn_handle* h, const char* fn, const std::vector<WnGradEntry>& t, int i, char* name, size_t name_cap,
                  int64_t* offset, int64_t* shape4, int* ndim);
+// wn_iaf_train.hip for wn_iaf_adjoint (wn_iaf_nll.hip): the refusals of a reverse pass under the caller's name (handle and
+// shape; then the tape), the tape's scale_tot before the e^7 clamp [B][T], and the launches of wn_iaf_backward_input without
+// d_encoding -- nothing checked, the work lock is the caller's, ws holds wn_iaf_backward_input_workspace_bytes
+int wn_iaf_reverse_check(wn_handle* h, const char* fn, int B, int F, int64_t T);
+int wn_iaf_reverse_tape_check(wn_handle* h, const char* fn, const void* tape, size_t tape_bytes, int B, int F, int64_t T);
+const float* wn_iaf_tape_scale_prod(const wn_handle* h, const void* tape, int B, int F, int64_t T);
+int wn_iaf_reverse_input_run(wn_handle* h, const char* fn, const void* tape, const float* d_x, const float* d_mean_tot,
+                             const float* d_scale_tot, int B, int F, int64_t T, float* d_noise, void* ws, void* stream);
 
 // ---- sizes of the IAF packs (width 64, deconv_width 256) ----
 // layer: P 112 K-steps * 4 mb * 64 lanes | PR 8 * 4 * 64 | bgate 64 | bres 64

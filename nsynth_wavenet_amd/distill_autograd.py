@@ -52,6 +52,50 @@ class IafFeedForward(torch.autograd.Function):
         return d_mel, res['d_noise'] if ctx.needs_input_grad[1] else None, None, None
 
 
+def iaf_log_prob_adjoint(eng, mel, z, d_log_prob, adjoint_tol=None, max_sweeps=None, check_every=8):
+    """What every gradient of the student's log-likelihood starts from: the tape forward at noise = z, the
+    cotangents of wn_iaf_latent_log_prob_grad on the tape's scale_tot, and the adjoint solve.  d_log_prob [B,T] float32.
+    -> {'tape', 'lam' (= d / d x), 'd_scale_tot', 'sweeps', 'converged'}; the weights and the encoding take theirs from
+    iaf_backward_weights / iaf_backward_input(tape, -lam, 0, d_scale_tot).  Raises when the solve did not converge."""
+    ff, tape = eng.iaf_forward_train_tape(mel, noise=z)
+    g_z, d_s = eng.iaf_latent_log_prob_grad(z, ff['scale_tot'], d_log_prob)
+    r = eng.iaf_adjoint(tape, g_z, d_s, tol=eng.ADJOINT_TOL if adjoint_tol is None else adjoint_tol, max_sweeps=max_sweeps,
+                        check_every=check_every)
+    if r['replaced'] or not bool(r['converged'].all()):
+        raise RuntimeError('log_prob: the adjoint of the inverse did not converge in {} sweeps (max |update| / max |lam| = {:.3g}'
+                           ', {} non-finite values)'.format(r['sweeps'], float((r['resid'][:, 0] / r['resid'][:, 1]).max()),
+                                                             r['replaced']))
+    return {'tape': tape, 'lam': r['lam'], 'd_scale_tot': d_s, 'sweeps': r['sweeps'], 'converged': r['converged']}
+
+
+class IafLogProb(torch.autograd.Function):
+    """(wav [B,T], mel [B,F,n_mel]) -> (log_probs [B,T], log_prob_sums [B] float64) of a student Engine: the values an encode
+    already computed (`enc`: Engine.iaf_encode's 'z', 'log_prob', 'log_prob_sums'), handed on unchanged; differentiable in
+    both inputs by the adjoint of the inverse.  stacks: as for IafFeedForward.  adj: keyword arguments of
+    iaf_log_prob_adjoint."""
+
+    @staticmethod
+    def forward(ctx, wav, mel, eng, stacks, enc, adj):
+        ctx.eng, ctx.stacks, ctx.adj = eng, stacks, adj
+        ctx.mel, ctx.z = eng._dev(mel.detach()), enc['z']
+        return enc['log_prob'].clone(), enc['log_prob_sums'].clone()
+
+    @staticmethod
+    def backward(ctx, d_lp, d_sums):
+        eng, z = ctx.eng, ctx.z
+        c = d_sums.to(torch.float32)[:, None].expand_as(z)
+        c = (c + d_lp if d_lp is not None else c).contiguous()
+        a = iaf_log_prob_adjoint(eng, ctx.mel, z, c, **ctx.adj)
+        d_mel = None
+        if ctx.needs_input_grad[1]:
+            zero = torch.zeros_like(a['lam'])
+            res = eng.iaf_backward_input(a['tape'], -a['lam'], zero, a['d_scale_tot'], want_encoding=True)
+            for s, (e, scope) in enumerate(ctx.stacks):
+                g = e.deconv_backward_input(ctx.mel, res['d_encoding'][s], scope)
+                d_mel = g if d_mel is None else d_mel + g
+        return a['lam'] if ctx.needs_input_grad[0] else None, d_mel, None, None, None, None
+
+
 class TeacherLogProb(torch.autograd.Function):
     """(out_params [B,T,out_width], wav [B,T]) -> log_probs [B,T] of a teacher Engine.  The gradient to wav is
     the one through the TARGET (zero for mu-law and ce teachers); the one through the network input is TeacherForward's."""

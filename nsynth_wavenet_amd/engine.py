@@ -751,6 +751,65 @@ class Engine(object):
                                                        B, F, T, _ptr(dn), _ptr(denc), _ptr(ws), ws.numel(), self._stream()))
         return {'d_noise': dn, 'd_encoding': denc}
 
+    # ---- the gradient of the student's log-likelihood ----
+    ADJOINT_TOL = 1e-5          # the default tolerance of iaf_adjoint: DESIGN.md 27.3 has the measurements behind it
+
+    def iaf_latent_log_prob_grad(self, z, scale_tot, d_log_prob=None):
+        """wn_iaf_latent_log_prob_grad, iaf_latent_log_prob's counterpart: for a cotangent d_log_prob [B,T] of log p (None:
+        the constant -1 / (B T) of -mean log p) -> (g_z, d_scale_tot), [B,T] float32: d_log_prob (log f)'(z) and
+        -d_log_prob / scale_tot."""
+        z, scale_tot, d_log_prob = self._dev(z), self._dev(scale_tot), self._dev(d_log_prob)
+        if z.dim() != 2 or z.shape != scale_tot.shape or (d_log_prob is not None and d_log_prob.shape != z.shape):
+            raise ValueError('z, scale_tot and d_log_prob must be [batch, T] alike, got {}'.format(
+                [tuple(v.shape) for v in (z, scale_tot, d_log_prob) if v is not None]))
+        g_z, d_s = torch.empty_like(z), torch.empty_like(z)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.wn_iaf_latent_log_prob_grad(self._h, _ptr(z), _ptr(scale_tot), int(z.shape[0]), int(z.shape[1]),
+                                                             _ptr(d_log_prob), _ptr(g_z), _ptr(d_s), self._stream()))
+        return g_z, d_s
+
+    def iaf_adjoint(self, tape, g_z, d_scale_tot, d_mean_tot=None, lam_init=None, max_sweeps=None, tol=ADJOINT_TOL, check_every=8,
+                    n_frames=None):
+        """The adjoint of the inverse (wn_iaf_adjoint): on a tape of iaf_forward_train_tape at noise = z, solve
+        A^T lam = g_z + (d scale_tot / d z)^T d_scale_tot (+ the same of d_mean_tot), A = d x / d z, by Jacobi sweeps
+        lam <- lam + (g_z + r) / scale_tot with r = iaf_backward_input(tape, -lam, d_mean_tot, d_scale_tot)['d_noise'].  A^T is
+        upper triangular: k sweeps make the last k samples of a row exact, T sweeps the row.  Starts from lam_init, or zeros.
+
+        `check_every` sweeps are enqueued per C call, then the residuals and counts come back in ONE read-back.  The solve
+        stops after the first sweep in which every row had max |lam' - lam| <= tol max |lam'|, or at max_sweeps (default T);
+        sweeps a C call has enqueued past that one change nothing, so the result does not depend on check_every.
+        Returns {'lam' [B,T], 'sweeps' (int), 'converged' ([B] bool), 'resid' ([B,2] float32: max |lam' - lam|, max |lam'| of
+        the last sweep), 'replaced' (int: non-finite values the last sweep replaced by 0)}."""
+        g_z, d_scale_tot, d_mean_tot = self._dev(g_z), self._dev(d_scale_tot), self._dev(d_mean_tot)
+        if g_z.dim() != 2 or any(v is not None and tuple(v.shape) != tuple(g_z.shape) for v in (d_scale_tot, d_mean_tot, lam_init)):
+            raise ValueError('iaf_adjoint: g_z, d_scale_tot, d_mean_tot and lam_init must be [B,T] alike')
+        F = int(n_frames if n_frames is not None else self._train_frames.get(tape.data_ptr(), 0))
+        if F < 1:
+            raise ValueError('iaf_adjoint: pass n_frames for a tape this engine object did not write')
+        if check_every < 1:
+            raise ValueError('check_every must be >= 1, got {}'.format(check_every))
+        B, T = int(g_z.shape[0]), int(g_z.shape[1])
+        max_sweeps = T if max_sweeps is None else int(max_sweeps)
+        lam = torch.zeros((B, T), dtype=torch.float32, device=self.device) if lam_init is None else self._dev(lam_init).clone()
+        meta = torch.zeros(2 * B + 4, dtype=torch.int32, device=self.device)          # resid [B][2] (float32), then counts [4]
+        sweeps, replaced = 0, 0
+        with torch.cuda.device(self.device):
+            ws = torch.empty(max(int(self.lib.wn_iaf_adjoint_workspace_bytes(self._h, B, F, T)), 256), dtype=torch.uint8,
+                             device=self.device)
+            while True:
+                n = min(int(check_every), max_sweeps - sweeps)
+                self._check(self.lib.wn_iaf_adjoint(
+                    self._h, _ptr(tape), tape.numel(), _ptr(g_z), _ptr(d_mean_tot), _ptr(d_scale_tot), B, F, T, _ptr(lam), n,
+                    float(tol), _ptr(meta), ctypes.c_void_p(meta.data_ptr() + 8 * B), _ptr(ws), ws.numel(), self._stream()))
+                m = meta.cpu()
+                replaced, done_at = int(m[2 * B]), int(m[2 * B + 2])
+                sweeps += done_at if done_at else n
+                if done_at or sweeps >= max_sweeps:
+                    break
+        resid = meta[:2 * B].view(torch.float32).view(B, 2).clone()
+        return {'lam': lam, 'sweeps': sweeps, 'converged': resid[:, 0] <= torch.tensor(tol, dtype=torch.float32) * resid[:, 1],
+                'resid': resid, 'replaced': replaced}
+
     # ---- reverse pass of the upsampler (DESIGN.md 15) ----
     def deconv_grad_table(self, scope=''):
         """[(tf variable name, float offset, TF shape)] of deconv_backward's flat gradient buffer: per layer

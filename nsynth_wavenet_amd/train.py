@@ -434,23 +434,28 @@ class StudentTrainer(_DeviceTrainer):
                  upsampler=True, seed=0):
         if getattr(pw, 'teacher', None) is None:
             raise ValueError('StudentTrainer needs a student with a teacher: ParallelWavenet(hparams, teacher=Wavenet(te_hparams))')
+        self._init_student(pw, weights, lr, beta1, beta2, eps, ema_decay, clip_norm, upsampler)
+        self.seed = int(seed)
+
+    def _init_student(self, pw, weights, lr, beta1, beta2, eps, ema_decay, clip_norm, upsampler):
+        """the optimiser and the buffers of the flows and of every trained stack (StudentMleTrainer's as well)"""
+        who = type(self).__name__
         self.net = pw
         self.eng = eng = pw.engine
         self._init_optimiser(lr, beta1, beta2, eps, ema_decay, clip_norm)
-        self.seed = int(seed)
         self.upsampler = bool(upsampler) and not getattr(pw, 'use_teacher_deconv', False)
         tables = [eng.iaf_grad_table()]
         if not tables[0]:
-            raise ValueError('StudentTrainer: this model has no weight gradients on the device (mu-law, weight norm, or a '
-                             'width / deconv_width that is no multiple of 64)')
+            raise ValueError('{}: this model has no weight gradients on the device (mu-law, weight norm, or a '
+                             'width / deconv_width that is no multiple of 64)'.format(who))
         sizes = [eng.iaf_grad_floats()]
         self.scopes = list(eng.iaf_stack_scopes()) if self.upsampler else []
         for scope in self.scopes:
             tables.append(eng.deconv_grad_table(scope))
             sizes.append(eng.deconv_grad_floats(scope))
         if not all(tables):
-            raise ValueError('StudentTrainer: a deconv stack has no weight gradients on the device (a resize-conv upsampler needs '
-                             'upsampler=False)')
+            raise ValueError('{}: a deconv stack has no weight gradients on the device (a resize-conv upsampler needs '
+                             'upsampler=False)'.format(who))
         self._init_buffers(weights, tables, sizes)
 
     def _repack(self, bufs):
@@ -468,3 +473,47 @@ class StudentTrainer(_DeviceTrainer):
         ret = {k: v for k, v in out.items() if k not in ('grads', 'flat_grads', 'd_encoding', 'flat_upsampler_grads')}
         ret['grad_norm'] = norm
         return ret
+
+
+class StudentMleTrainer(StudentTrainer):
+    """One student handle trained by maximum likelihood on real audio: the loss is -mean log p(wav | mel) of
+    ParallelWavenet.nll_and_weight_grads, and no teacher is needed -- ParallelWavenet(hparams) will do, and a teacher the
+    student has is not used.  Also the likelihood fine-tuning of a distilled student.
+
+    pw, weights, lr, beta1, beta2, eps, ema_decay, clip_norm, upsampler: as for StudentTrainer (no mu-law, no weight norm;
+    width and deconv_width multiples of 64).  encode_tol: the tolerance of the encode's sweeps (README: 1e-5 for the shipped
+    student); adjoint_tol: that of the adjoint's (None: Engine.ADJOINT_TOL).  max_sweeps: the bound of both, None for T.
+    The buffers, the update, the re-pack, save() and restore() are StudentTrainer's; nothing is drawn, so there is no seed."""
+
+    def __init__(self, pw, weights, lr=2e-4, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay=0.9999, clip_norm=None,
+                 upsampler=True, encode_tol=1e-5, adjoint_tol=None, max_sweeps=None):
+        for name, tol in (('encode_tol', encode_tol), ('adjoint_tol', adjoint_tol)):
+            if tol is not None and not float(tol) >= 0.0:
+                raise ValueError('StudentMleTrainer: {} must be >= 0, got {}'.format(name, tol))
+        if encode_tol is None:
+            raise ValueError('StudentMleTrainer: encode_tol must be >= 0, got None')
+        if max_sweeps is not None and int(max_sweeps) < 1:
+            raise ValueError('StudentMleTrainer: max_sweeps must be >= 1, got {}'.format(max_sweeps))
+        if getattr(pw, 'use_mu_law', False):
+            raise ValueError('StudentMleTrainer: mu-law students are not supported (their audio is not the flow\'s output x)')
+        self._init_student(pw, weights, lr, beta1, beta2, eps, ema_decay, clip_norm, upsampler)
+        self.encode_tol, self.adjoint_tol = float(encode_tol), None if adjoint_tol is None else float(adjoint_tol)
+        self.max_sweeps = None if max_sweeps is None else int(max_sweeps)
+
+    def step(self, inputs):
+        """One training step on {'mel': [B,F,80], 'wav': [B,T']} -> {'loss': -mean log p BEFORE the update (the bits of
+        nll_and_weight_grads under the weights in force at entry), 'log_probs', 'grad_norm': the global norm of the gradient
+        before clipping, 'sweeps', 'adjoint_sweeps', 'converged'}.  Raises, with nothing updated, when the encode or the
+        adjoint did not converge."""
+        for k in ('mel', 'wav'):
+            if k not in inputs:
+                raise KeyError('StudentMleTrainer.step: inputs lack {!r}'.format(k))
+        kw = {} if self.max_sweeps is None else {'max_sweeps': self.max_sweeps}
+        out = self.net.nll_and_weight_grads(inputs, upsampler=self.upsampler, encode_tol=self.encode_tol,
+                                            adjoint_tol=self.adjoint_tol, **kw)
+        flats = [out['flat_grads']] + [out['flat_upsampler_grads'][s] for s in self.scopes]
+        norm = self._update(flats)
+        self._repack(self.p)
+        self.global_step += 1
+        return {'loss': out['loss'], 'log_probs': out['log_probs'], 'grad_norm': norm, 'sweeps': out['sweeps'],
+                'adjoint_sweeps': out['adjoint_sweeps'], 'converged': out['converged']}

@@ -17,6 +17,10 @@ on and one of them requires grad, they are composed of the autograd Functions of
 for the values (the same bits), the gradient kernels and the teacher's input VJP for `backward()`.  Otherwise they take the
 plain path (no tape).  H_Ps is computed from scale_tot, so its gradient goes to scale_tot: 1 / (N scale_tot), which is the
 reference's gradient through log_scale_tot wherever scale_tot = exp(log_scale_tot).
+
+Without a teacher: `encode` / `log_prob` give the student's own likelihood of real audio, and
+`nll_and_weight_grads` its gradient with respect to the student's variables, the audio and the encoding --
+the loss of maximum-likelihood training (train.StudentMleTrainer).
 """
 import numpy as np
 import torch
@@ -117,13 +121,73 @@ class ParallelWavenet(object):
         return {'z': r['z'], 'log_scale_tot': torch.log(r['scale_tot']), 'log_probs': r['log_prob'],
                 'log_prob_sums': r['log_prob_sums'], 'sweeps': r['sweeps'], 'converged': r['converged']}
 
-    def log_prob(self, inputs, **kw):
+    def log_prob(self, inputs, adjoint_tol=None, **kw):
         """The student's log-likelihood of real audio: {'log_probs': [B,T], 'loss': -mean log p} (a 0-d float64 device
-        tensor, from the kernel's float64 row sums).  Needs no teacher.  Raises when a row did not converge."""
+        tensor, from the kernel's float64 row sums).  Needs no teacher.  Raises when a row did not converge.
+        When grad mode is on and inputs['mel'] or the audio is a tensor that requires grad, both results carry a gradient to
+        them: the values are the same bits -- the encode runs as it does without grad -- and backward() runs
+        the tape forward at z, the adjoint solve (Engine.iaf_adjoint, tolerance `adjoint_tol`) and, for mel, one
+        Engine.deconv_backward_input per stack; it raises when the adjoint did not converge.  The student's weights get
+        their gradient from nll_and_weight_grads."""
+        key = 'x' if 'x' in inputs else 'wav'
+        if torch.is_grad_enabled() and (_req(inputs, 'mel') or _req(inputs, key)):
+            return self._log_prob_grad(inputs[key], inputs['mel'], adjoint_tol, kw)
         r = self.encode(inputs, **kw)
         if not bool(r['converged'].all()):
             raise RuntimeError('log_prob: the inverse did not converge in {} sweeps'.format(r['sweeps']))
         return {'log_probs': r['log_probs'], 'loss': -(r['log_prob_sums'].sum() / r['log_probs'].numel())}
+
+    def _log_prob_grad(self, wav, mel, adjoint_tol, kw):
+        eng = self.engine
+        wav, mel = eng._dev(wav), eng._dev(mel)          # differentiable for tensors: the gradients return to the caller's
+        enc = eng.iaf_encode(wav.detach(), mel.detach(), want=('z', 'log_prob'), **kw)
+        if not bool(enc['converged'].all()):
+            raise RuntimeError('log_prob: the inverse did not converge in {} sweeps'.format(enc['sweeps']))
+        adj = {'adjoint_tol': adjoint_tol, 'check_every': kw.get('check_every', 8)}
+        lp, sums = dag.IafLogProb.apply(wav, mel, eng, self._input_grad_stacks(), enc, adj)
+        return {'log_probs': lp, 'loss': -(sums.sum() / lp.numel())}
+
+    def nll_and_weight_grads(self, inputs, upsampler=True, encode_tol=1e-5, adjoint_tol=None, **kw):
+        """-mean log p(wav | mel) under the student and its gradient with respect to the student's own variables, the audio
+        and the encoding: maximum-likelihood training on real audio, no teacher.  inputs: 'mel' [B,F,80] and
+        'wav' [B,T']; a wav longer than T = the student's length for F frames is centre-cropped as power_loss crops it, a
+        shorter one is refused.  One encode (Engine.iaf_encode with tol = encode_tol; further keyword arguments go there),
+        one tape forward at z, the adjoint solve (Engine.iaf_adjoint, tolerance adjoint_tol; max_sweeps and check_every bound
+        and pace it as they do the encode), one reverse pass over the tape
+        (Engine.iaf_backward_weights).  Raises when the encode or the adjoint did not converge.
+        Returns 'loss' and 'log_probs' -- the bits of log_prob(inputs, tol=encode_tol) -- 'grads', 'flat_grads', 'd_encoding'
+        and, with upsampler=True, the deconv stacks' entries and 'flat_upsampler_grads', laid out as loss_and_weight_grads
+        lays them out; 'd_wav' [B,T] (of the cropped audio), 'sweeps' and 'adjoint_sweeps' (int) and 'converged' ([B] bool)."""
+        from ..engine import _trim
+        eng = self.engine
+        mel = eng._dev(inputs['mel']).detach()
+        wav = eng._dev(inputs['wav']).detach()
+        T = eng.iaf_length(int(mel.shape[1])) if mel.dim() == 3 else 0
+        if wav.dim() != 2 or int(wav.shape[1]) < T:
+            raise ValueError('nll_and_weight_grads: wav must be [B, >= {}] for {} mel frames, got {}'.format(
+                T, int(mel.shape[1]) if mel.dim() == 3 else '?', tuple(wav.shape)))
+        if int(wav.shape[1]) > T:
+            wav = _trim(wav, int(wav.shape[1]) - T).contiguous()
+        enc = eng.iaf_encode(wav, mel, want=('z', 'log_prob'), tol=encode_tol, **kw)
+        if not bool(enc['converged'].all()):
+            raise RuntimeError('nll_and_weight_grads: the inverse did not converge in {} sweeps'.format(enc['sweeps']))
+        lp, n = enc['log_prob'], enc['log_prob'].numel()
+        # the cotangent of log p under -mean, as autograd hands it to IafLogProb.backward: the same bits on both roads
+        c = torch.full(tuple(lp.shape), -1.0 / n, dtype=torch.float64, device=lp.device).to(torch.float32)
+        a = dag.iaf_log_prob_adjoint(eng, mel, enc['z'], c, adjoint_tol=adjoint_tol, max_sweeps=kw.get('max_sweeps'),
+                                     check_every=kw.get('check_every', 8))
+        res = eng.iaf_backward_weights(a['tape'], -a['lam'], torch.zeros_like(a['lam']), a['d_scale_tot'], want_encoding=True)
+        ret = {'loss': -(enc['log_prob_sums'].sum() / n), 'log_probs': lp, 'grads': res['grads'], 'flat_grads': res['flat_grads'],
+               'd_encoding': res['d_encoding'], 'd_wav': a['lam'], 'sweeps': enc['sweeps'], 'adjoint_sweeps': a['sweeps'],
+               'converged': enc['converged'] & a['converged']}
+        if upsampler and not self.use_teacher_deconv:
+            ret['grads'] = dict(res['grads'])
+            ret['flat_upsampler_grads'] = {}
+            for s, scope in enumerate(eng.iaf_stack_scopes()):
+                up = eng.deconv_backward(mel, res['d_encoding'][s], scope)
+                ret['grads'].update(up['grads'])
+                ret['flat_upsampler_grads'][scope] = up['flat_grads']
+        return ret
 
     def _clip_quant_scale(self, x, quant_chann=None, use_mu_law=None):
         wav, _ = self.engine.clip_quant(x)
