@@ -757,6 +757,15 @@ WN_API int wn_iaf_set_weights(wn_handle* h, const float* params, size_t params_f
 WN_API size_t wn_grad_sumsq_workspace_bytes(size_t n);
 WN_API int wn_grad_sumsq(const float* g, size_t n, double* acc, int accumulate, void* ws, size_t ws_bytes, void* stream);
 
+/* Combine the gradients of S shards of one training step: with r_j = rows + j * row_stride,
+ *   out[i] = (((r_0[i] + r_1[i]) + r_2[i]) + ... + r_{S-1}[i]) * (1.0f / S)   for i < n,
+ * in float32, strictly left to right with one rounding per add and one for the product, so the result depends on the
+ * rows and their order alone -- not on how the shards were spread over devices.  S in [1, 64] (S = 1: a copy times 1);
+ * row_stride >= n floats; `out` may be row 0 and must not overlap any other row.  One writer per element, no atomics: a
+ * repeated call gives the same bits.  16-byte accesses with a scalar tail (all scalar when rows, out or row_stride * 4 is
+ * off the 16-byte grid); any n >= 1.  Needs no handle; errors through wn_last_error(NULL).  Asynchronous on `stream`. */
+WN_API int wn_grad_combine(const float* rows, size_t n, size_t row_stride, int S, float* out, void* stream);
+
 /* One step of TensorFlow's Adam on n device floats, with the shadow of tf.train.ExponentialMovingAverage:
  *   m <- beta1 m + (1 - beta1) g',  v <- beta2 v + (1 - beta2) g'^2,  p <- p - lr_t m / (sqrt(v) + eps),
  *   ema <- ema - (1 - ema_decay_t) (ema - p)   on the updated p (ema may be NULL).

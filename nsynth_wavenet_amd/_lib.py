@@ -23,7 +23,7 @@ SYMBOLS = ['wn_abi_version', 'wn_create', 'wn_set_weight', 'wn_finalize', 'wn_ia
            'wn_iaf_range_status_since_reset', 'wn_clip_quant',
            'wn_ar_n_rand', 'wn_ar_state_bytes', 'wn_ar_reset', 'wn_ar_step', 'wn_ar_generate', 'wn_ar_set_graph', 'wn_ar_cond_vars', 'wn_ar_cond_vars_floats',
            'wn_iaf_cond_hoisted', 'wn_iaf_layer_groups', 'wn_iaf_set_groups', 'wn_teacher_workspace_bytes', 'wn_teacher_forward', 'wn_teacher_log_prob', 'wn_teacher_log_prob_grad', 'wn_distill_workspace_bytes', 'wn_distill_mol_xent', 'wn_distill_gauss_kl', 'wn_power_loss_workspace_bytes', 'wn_power_loss', 'wn_teacher_tape_bytes', 'wn_teacher_forward_tape', 'wn_teacher_backward_workspace_bytes', 'wn_teacher_backward_input', 'wn_teacher_grad_count', 'wn_teacher_grad_info', 'wn_teacher_grad_floats', 'wn_teacher_train_tape_bytes', 'wn_teacher_forward_train_tape', 'wn_teacher_backward_weights_workspace_bytes', 'wn_teacher_backward_weights', 'wn_distill_mol_xent_grad', 'wn_distill_gauss_kl_grad', 'wn_power_loss_grad_workspace_bytes', 'wn_power_loss_grad', 'wn_profile_begin', 'wn_profile_pause', 'wn_profile_end', 'wn_profile_parts_begin', 'wn_profile_parts_end', 'wn_profile_parts_only', 'wn_mel_frames', 'wn_mel_spectrogram', 'wn_last_error', 'wn_destroy', 'wn_crc32c', 'wn_deconv_grad_count', 'wn_deconv_grad_info', 'wn_deconv_grad_floats', 'wn_deconv_backward_workspace_bytes', 'wn_deconv_backward', 'wn_teacher_set_weights_workspace_bytes', 'wn_teacher_set_weights',
-           'wn_grad_sumsq_workspace_bytes', 'wn_grad_sumsq', 'wn_adam_ema_step',
+           'wn_grad_sumsq_workspace_bytes', 'wn_grad_sumsq', 'wn_adam_ema_step', 'wn_grad_combine',
            'wn_teacher_train_tape_dropout_bytes', 'wn_teacher_forward_train_tape_dropout', 'wn_teacher_dropout_keep',
            'wn_iaf_grad_count', 'wn_iaf_grad_info', 'wn_iaf_grad_floats', 'wn_iaf_train_tape_bytes',
            'wn_iaf_train_workspace_bytes', 'wn_iaf_forward_train_tape', 'wn_iaf_backward_weights_workspace_bytes',
@@ -182,6 +182,7 @@ def load():
     lib.wn_grad_sumsq_workspace_bytes.argtypes = [sz]
     lib.wn_grad_sumsq_workspace_bytes.restype = sz
     lib.wn_grad_sumsq.argtypes = [vp, sz, vp, i32, vp, sz, vp]
+    lib.wn_grad_combine.argtypes = [vp, sz, sz, i32, vp, vp]
     f32 = c.c_float
     lib.wn_adam_ema_step.argtypes = [vp, vp, vp, vp, vp, sz, f32, f32, f32, f32, f32, vp, f32, vp]
     lib.wn_distill_mol_xent_grad.argtypes = [vp, vp, i32, vp, vp, i32, i64, i32, vp, u64, vp, vp, vp, vp, vp]

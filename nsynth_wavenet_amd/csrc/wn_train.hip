@@ -101,6 +101,56 @@ __global__ __launch_bounds__(TR_NT) void tr_adam_kernel(AdamArgs a) {
     if (i < a.n - 4 * nq && (!VEC || i < 4)) adam_one(a, gs, a.p[t], a.g[t], a.m[t], a.v[t], a.ema ? a.ema + t : nullptr);
 }
 
+// Shard combine: out[i] = (((r_0[i] + r_1[i]) + ...) + r_{S-1}[i]) * inv, r_j = rows + j * row_stride.  One
+// thread per quad (VEC) or per element, strictly left to right with one rounding per add; rows and out carry no
+// __restrict__, since out may be row 0: every thread reads its own elements of every row before it writes them.
+// The loads of up to GC_BATCH rows are issued together, the adds follow in row order.
+constexpr int GC_BATCH = 8;
+template <typename V>
+__device__ inline V gc_chain(const float* rows, size_t at, size_t row_stride, int S) {
+    V acc = *reinterpret_cast<const V*>(rows + at);
+    int j = 1;
+    for (; j + GC_BATCH <= S; j += GC_BATCH) {
+        V r[GC_BATCH];
+#pragma unroll
+        for (int k = 0; k < GC_BATCH; ++k) r[k] = *reinterpret_cast<const V*>(rows + (size_t)(j + k) * row_stride + at);
+#pragma unroll
+        for (int k = 0; k < GC_BATCH; ++k) {
+            if constexpr (sizeof(V) == sizeof(float)) {
+                acc = __fadd_rn(acc, r[k]);
+            } else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[c] = __fadd_rn(acc[c], r[k][c]);
+            }
+        }
+    }
+    for (; j < S; ++j) {
+        const V r = *reinterpret_cast<const V*>(rows + (size_t)j * row_stride + at);
+        if constexpr (sizeof(V) == sizeof(float)) {
+            acc = __fadd_rn(acc, r);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc[c] = __fadd_rn(acc[c], r[c]);
+        }
+    }
+    return acc;
+}
+// VEC: 16-byte accesses over the first n / 4 quads and a scalar tail, as tr_adam_kernel; otherwise all scalar
+template <bool VEC>
+__global__ __launch_bounds__(TR_NT) void tr_combine_kernel(const float* rows, size_t n, size_t row_stride, int S, float inv,
+                                                           float* out) {
+    const size_t i = (size_t)blockIdx.x * TR_NT + threadIdx.x;
+    const size_t nq = VEC ? n / 4 : 0;
+    if (VEC && i < nq) {
+        f4 acc = gc_chain<f4>(rows, 4 * i, row_stride, S);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[c] = __fmul_rn(acc[c], inv);
+        reinterpret_cast<f4*>(out)[i] = acc;
+    }
+    const size_t t = 4 * nq + i;
+    if (i < n - 4 * nq && (!VEC || i < 4)) out[t] = __fmul_rn(gc_chain<float>(rows, t, row_stride, S), inv);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // re-pack: plain fp32 parts
 // ---------------------------------------------------------------------------------------------------------------------
@@ -353,6 +403,19 @@ extern "C" int wn_grad_sumsq(const float* g, size_t n, double* acc, int accumula
     double* part = reinterpret_cast<double*>(ws);
     hipLaunchKernelGGL(tr_sumsq1_kernel, dim3(nb), dim3(TR_NT), 0, st, g, n, part);
     hipLaunchKernelGGL(tr_sumsq2_kernel, dim3(1), dim3(TR_NT), 0, st, part, nb, acc, accumulate);
+    WN_HIP(nullptr, hipGetLastError());
+    return WN_OK;
+}
+
+extern "C" int wn_grad_combine(const float* rows, size_t n, size_t row_stride, int S, float* out, void* stream) {
+    if (!rows || !out || n < 1) return wn_fail(nullptr, WN_EINVAL, "wn_grad_combine: bad argument");
+    if (S < 1 || S > 64) return wn_fail(nullptr, WN_EINVAL, "wn_grad_combine: S = %d is outside [1, 64]", S);
+    if (row_stride < n) return wn_fail(nullptr, WN_EINVAL, "wn_grad_combine: row_stride %zu < n = %zu", row_stride, n);
+    const float inv = 1.0f / (float)S;
+    const uintptr_t bits = (uintptr_t)rows | (uintptr_t)out | (uintptr_t)(row_stride * sizeof(float));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (bits & 15) hipLaunchKernelGGL(tr_combine_kernel<false>, dim3(tr_blocks(n)), dim3(TR_NT), 0, st, rows, n, row_stride, S, inv, out);
+    else hipLaunchKernelGGL(tr_combine_kernel<true>, dim3(tr_blocks(std::max<size_t>(n / 4, 4))), dim3(TR_NT), 0, st, rows, n, row_stride, S, inv, out);
     WN_HIP(nullptr, hipGetLastError());
     return WN_OK;
 }

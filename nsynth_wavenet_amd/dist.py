@@ -7,6 +7,9 @@ contiguously over one process per GPU with NO collective on the data path.  The
 only communication is a one-time broadcast of the weight blob from rank 0 over
 RCCL/xGMI (backend "nccl"; "gloo" in the CPU tests) so that only rank 0 has to read
 the checkpoint, and an optional gather of the generated audio to rank 0.
+
+Data-parallel training adds one collective per step, exchange_rows: the all-gather of the shards' gradient
+rows, after which every rank combines them in the same fixed order.
 """
 import os
 
@@ -22,8 +25,14 @@ def env_rank_world():
         int(os.environ.get('LOCAL_RANK', '0'))
 
 
-def init_process_group(backend=None):
-    """One process per GPU (torch.distributed.run sets RANK/LOCAL_RANK/WORLD_SIZE/MASTER_*)."""
+TRAIN_TIMEOUT_S = 600      # training's: a collective a rank never joins ends the job after this long instead of hanging it
+
+
+def init_process_group(backend=None, timeout_s=None):
+    """One process per GPU (torch.distributed.run sets RANK/LOCAL_RANK/WORLD_SIZE/MASTER_*).  timeout_s: the timeout of every
+    collective of the group in seconds; None keeps torch's default, as the generation CLIs always had.  Training passes
+    TRAIN_TIMEOUT_S (train_cli.py)."""
+    import datetime
     rank, world, local = env_rank_world()
     if world > 1 and not dist.is_initialized():
         if backend is None:
@@ -32,7 +41,8 @@ def init_process_group(backend=None):
         os.environ.setdefault('MASTER_PORT', '29500')
         if backend == 'nccl':
             torch.cuda.set_device(local)
-        dist.init_process_group(backend=backend, rank=rank, world_size=world)
+        kw = {} if timeout_s is None else {'timeout': datetime.timedelta(seconds=float(timeout_s))}
+        dist.init_process_group(backend=backend, rank=rank, world_size=world, **kw)
     return rank, world, local
 
 
@@ -46,6 +56,30 @@ def shard_range(n_items, rank, world):
 def shard_batch(array, rank, world):
     lo, hi = shard_range(len(array), rank, world)
     return array[lo:hi]
+
+
+def exchange_rows(buf, lo, hi):
+    """The row exchange of a data-parallel training step.  buf: [S, n], contiguous, on every rank; this rank
+    has filled rows [lo, hi) = shard_range(S, rank, world) (S % world == 0).  One all-gather puts every rank's rows at their
+    shard index, so all ranks end with the same [S, n] bytes.  All-gather and not all-reduce: the order of the sum over the
+    rows is then the combine's, whatever the world size."""
+    if not dist.is_initialized() or dist.get_world_size() == 1:
+        return buf
+    world, rank = dist.get_world_size(), dist.get_rank()
+    S = int(buf.shape[0])
+    if not buf.is_contiguous() or S % world != 0 or (lo, hi) != shard_range(S, rank, world):
+        raise ValueError('exchange_rows: rows [{}, {}) of a {}contiguous buffer of {} rows are not the share of rank {} of {}'.format(
+            lo, hi, '' if buf.is_contiguous() else 'non-', S, rank, world))
+    mine = buf[lo:hi].clone()                        # the send buffer must not alias the receive buffer
+    if dist.get_backend() == 'nccl':
+        dist.all_gather_into_tensor(buf, mine)
+    elif buf.is_cuda:                                # gloo under device rows (the tests' ranks on one GPU): through the host
+        full = torch.empty(buf.shape, dtype=buf.dtype)
+        dist.all_gather(list(full.view(world, -1).unbind(0)), mine.cpu().view(-1))
+        buf.copy_(full)
+    else:
+        dist.all_gather(list(buf.view(world, -1).unbind(0)), mine.view(-1))
+    return buf
 
 
 def pack_weights(weights, hp, kind=None):

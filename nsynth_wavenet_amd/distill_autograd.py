@@ -62,9 +62,9 @@ def iaf_log_prob_adjoint(eng, mel, z, d_log_prob, adjoint_tol=None, max_sweeps=N
     r = eng.iaf_adjoint(tape, g_z, d_s, tol=eng.ADJOINT_TOL if adjoint_tol is None else adjoint_tol, max_sweeps=max_sweeps,
                         check_every=check_every)
     if r['replaced'] or not bool(r['converged'].all()):
-        raise RuntimeError('log_prob: the adjoint of the inverse did not converge in {} sweeps (max |update| / max |lam| = {:.3g}'
-                           ', {} non-finite values)'.format(r['sweeps'], float((r['resid'][:, 0] / r['resid'][:, 1]).max()),
-                                                             r['replaced']))
+        raise _engine.NotConverged('log_prob: the adjoint of the inverse did not converge in {} sweeps (max |update| / max |lam| = '
+                                   '{:.3g}, {} non-finite values)'.format(r['sweeps'], float((r['resid'][:, 0] / r['resid'][:, 1]).max()),
+                                                                          r['replaced']))
     return {'tape': tape, 'lam': r['lam'], 'd_scale_tot': d_s, 'sweeps': r['sweeps'], 'converged': r['converged']}
 
 

@@ -19,6 +19,12 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+class NotConverged(RuntimeError):
+    """The inverse of the student (the encode's sweeps) or its adjoint did not converge within the sweeps it was given.
+    A RuntimeError, as these refusals always were; a type of its own so that a caller that goes on after one -- the sharded
+    maximum-likelihood step -- tells it from any other failure without reading the message."""
+
+
 class Engine(object):
     """Replaces one TF graph + Session of the reference (parallelgen.py:24-41,
     fastgen.py:139-150): built from hparams, filled with named weights."""
@@ -930,6 +936,11 @@ class Engine(object):
         into `acc` ([1] float64) or added to it with accumulate.  Returns acc."""
         return grad_sumsq(g, acc, accumulate)
 
+    def grad_combine(self, rows, out=None):
+        """The mean of the S rows of a [S, n] float32 device tensor, summed strictly left to right in float32:
+        into `out` ([n], may be rows[0]) or a new tensor.  Returns out."""
+        return grad_combine(rows, out)
+
     def adam_ema_step(self, p, g, m, v, ema, lr_t, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay_t=0.0, sumsq=None,
                       clip_norm=1.0):
         """One Adam step in place on flat float32 device tensors, with the EMA shadow (or None) and, with `sumsq` (the [1]
@@ -1373,6 +1384,41 @@ def grad_sumsq(g, acc=None, accumulate=False):
         _lib.check(lib.wn_grad_sumsq(_ptr(g), g.numel(), _ptr(acc), 1 if accumulate else 0, _ptr(ws), nb,
                                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     return acc
+
+
+GRAD_COMBINE_MAX_ROWS = 64
+
+
+def grad_combine(rows, out=None):
+    """wn_grad_combine: out[i] = (((rows[0, i] + rows[1, i]) + ...) + rows[S - 1, i]) * float32(1 / S), in float32 and in
+    that order (train.combine_np is the numpy twin).  rows: a [S, n] float32 device tensor, 1 <= S <= 64, with unit inner
+    stride and a row stride >= n (a view of a wider buffer will do); out: a flat float32 device tensor of n values with unit
+    stride, rows[0] itself or memory outside rows (None: a new one).  Returns out."""
+    lib = _lib.load()
+    if not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2):
+        raise ValueError('grad_combine: rows must be a [S, n] float32 device tensor')
+    S, n = int(rows.shape[0]), int(rows.shape[1])
+    if not 1 <= S <= GRAD_COMBINE_MAX_ROWS:
+        raise ValueError('grad_combine: {} rows; the combine takes 1 to {}'.format(S, GRAD_COMBINE_MAX_ROWS))
+    if n < 1:
+        raise ValueError('grad_combine: rows are empty')
+    stride = int(rows.stride(0)) if S > 1 else n
+    if rows.stride(1) != 1 or stride < n:
+        raise ValueError('grad_combine: rows need unit inner stride and a row stride >= n, got strides {}'.format(tuple(rows.stride())))
+    dev = rows.device
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == torch.float32 and out.dim() == 1
+              and out.numel() == n and (n == 1 or out.stride(0) == 1)):
+        raise ValueError('grad_combine: out must be a flat float32 tensor of {} values on the device of rows'.format(n))
+    lo, hi = out.data_ptr(), out.data_ptr() + 4 * n
+    r0 = rows.data_ptr()
+    if lo != r0 and lo < r0 + 4 * ((S - 1) * stride + n) and hi > r0:
+        raise ValueError('grad_combine: out overlaps rows (only rows[0] itself may be the output)')
+    with torch.cuda.device(dev):
+        _lib.check(lib.wn_grad_combine(_ptr(rows), n, stride, S, _ptr(out),
+                                       ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return out
 
 
 def adam_ema_step(p, g, m, v, ema, lr_t, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay_t=0.0, sumsq=None, clip_norm=1.0):

@@ -27,6 +27,10 @@ the optimiser state, so that a restored trainer continues with the bits of the u
     trainer.save(logdir)
 
 train_wavenet.py / train_parallel_wavenet.py (train_cli.py) are this loop behind the reference's command lines.
+
+Shards: trainer.step(batch, micro_batch=m) runs the step in B / m shards and averages their gradients in a
+fixed order (Engine.grad_combine); a trainer built with data_parallel=True under torch.distributed spreads the shards over
+the ranks.  The result depends on (B, m) alone, so a run on N GPUs has the bits of the run on one.
 """
 import math
 import os
@@ -36,7 +40,7 @@ import torch
 
 from . import _lib
 from . import weights as wts
-from .engine import adam_ema_step, grad_sumsq
+from .engine import NotConverged, adam_ema_step, grad_sumsq
 
 
 def scheduled_lr(lr, global_step):
@@ -98,6 +102,67 @@ def dropout_step_seed(base, step):
     (base + step * 0x9E3779B97F4A7C15) mod 2^64.  The multiplier is odd, so for one base the seeds of 2^64 consecutive steps
     are distinct, and a trainer resumed at step n continues the sequence it would have run."""
     return (int(base) + int(step) * 0x9E3779B97F4A7C15) & (2 ** 64 - 1)
+
+
+_M64 = 2 ** 64 - 1
+MAX_SHARDS = 64                     # wn_grad_combine's bound on the rows of one call
+SCALAR_KEYS = ('loss', 'kl_loss', 'H_Ps', 'H_Ps_Pt', 'power_loss', 'contrastive_loss')
+ROW_SCALARS = 8                     # scalar slots behind the gradients of a row: SCALAR_KEYS in order, then zero padding
+ROW_INPUTS = ('wav', 'mel', 'mel_rand')
+
+
+def _mix64(x):
+    """the finaliser of SplitMix64: a bijection of the 64-bit words"""
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def shard_seed(seed, j):
+    """The seed of shard j of a step whose seed is `seed`, a pure function of the two: `seed` itself for
+    j = 0, so that a step of one shard draws what the unsharded step draws, and for j > 0 the 64-bit value
+    mix(mix(seed mod 2^64) + j mod 2^64) with mix the finaliser of SplitMix64.  No plain seed + j: the seeds of consecutive
+    steps are seed + k (the student) or base + k * odd (dropout_step_seed), and an additive shard seed would hand a shard
+    of one step the draws of a neighbouring step's.  mix is a bijection, so for one j distinct seeds stay distinct."""
+    seed, j = int(seed), int(j)
+    if j < 0:
+        raise ValueError('shard_seed: shard index {} is negative'.format(j))
+    if j == 0:
+        return seed
+    return _mix64((_mix64(seed & _M64) + j) & _M64)
+
+
+def combine_np(rows):
+    """wn_grad_combine on the host: (((rows[0] + rows[1]) + rows[2]) + ...) * (float32(1) / float32(S)) in float32, one
+    rounding per operation, over the S = len(rows) arrays of equal shape.  The bits of Engine.grad_combine."""
+    rows = [np.asarray(r, np.float32) for r in rows]
+    if not 1 <= len(rows) <= MAX_SHARDS:
+        raise ValueError('combine_np: {} rows; the combine takes 1 to {}'.format(len(rows), MAX_SHARDS))
+    acc = rows[0].copy()
+    for r in rows[1:]:
+        acc = (acc + r).astype(np.float32)
+    return (acc * (np.float32(1) / np.float32(len(rows)))).astype(np.float32)
+
+
+def shard_plan(B, m, world=1, rank=0):
+    """How a step on B rows is cut: micro-batches of m rows give S = B / m shards, shard j being rows
+    [j m, (j + 1) m), and rank `rank` of `world` computes the contiguous shards dist.shard_range(S, rank, world).
+    Returns (S, (first shard, one past the last), (first row, one past the last)) of that rank.  ValueError for B % m != 0,
+    for more than MAX_SHARDS shards and for S % world != 0."""
+    from .dist import shard_range
+    B, m, world, rank = int(B), int(m), int(world), int(rank)
+    if B < 1 or m < 1 or B % m != 0:
+        raise ValueError('a batch of B = {} rows does not split into micro-batches of m = {}: B % m must be 0'.format(B, m))
+    S = B // m
+    if S > MAX_SHARDS:
+        raise ValueError('B = {} rows in micro-batches of m = {} are S = {} shards; a step takes at most {}'.format(B, m, S, MAX_SHARDS))
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError('rank {} is outside a world of {}'.format(rank, world))
+    if S % world != 0:
+        raise ValueError('B = {} rows in micro-batches of m = {} are S = {} shards, which W = {} ranks do not share evenly: '
+                         'S % W must be 0'.format(B, m, S, world))
+    lo, hi = shard_range(S, rank, world)
+    return S, (lo, hi), (lo * m, hi * m)
 
 
 def batch_picks(seed, step, B, lengths, L, stream=0):
@@ -240,10 +305,46 @@ def checkpoint_weights(prefix_or_logdir, hp, kind=None):
     return out
 
 
-class _DeviceTrainer(object):
-    """What the two trainers share: the flat (p, m, v, ema) buffers of one or more gradient tables scattered from a weights
-    dict, the Adam / EMA update with its learning-rate bookkeeping, and weights() / use_ema() / use_weights().  A subclass sets
-    self.eng and implements _repack(bufs)."""
+class _TrainerType(type):
+    """Takes the construction keyword every trainer shares, data_parallel=, before __init__ runs, so that the __init__
+    signatures of the three trainers stay what their callers know.  data_parallel=True needs an initialised
+    torch.distributed process group: the trainer then computes its rank's shards of every step."""
+
+    def __call__(cls, *args, data_parallel=False, **kw):
+        world, rank = 1, 0
+        if data_parallel:
+            import torch.distributed as td
+            if cls.DATA_PARALLEL_REFUSAL:
+                raise ValueError('{}: data_parallel=True is not supported: {}'.format(cls.__name__, cls.DATA_PARALLEL_REFUSAL))
+            if not (td.is_available() and td.is_initialized()):
+                raise ValueError('{}: data_parallel=True needs an initialised torch.distributed process group '
+                                 '(dist.init_process_group)'.format(cls.__name__))
+            world, rank = td.get_world_size(), td.get_rank()
+        self = cls.__new__(cls)
+        self.data_parallel, self.world, self.rank = bool(data_parallel), world, rank
+        self.__init__(*args, **kw)
+        return self
+
+
+class _DeviceTrainer(object, metaclass=_TrainerType):
+    """What the trainers share: the flat (p, m, v, ema) buffers of one or more gradient tables scattered from a weights
+    dict, the Adam / EMA update with its learning-rate bookkeeping, the sharded step, and weights() /
+    use_ema() / use_weights().  A subclass sets self.eng and implements _repack(bufs) and _shard(rows, j, extra).
+
+    Shards: step(inputs, micro_batch=m) cuts the B rows of every per-row input ('wav', 'mel', 'mel_rand', a `noise`) into
+    S = B / m shards (at most 64), evaluates each by the model's own public call under train.shard_seed(step seed, j), and
+    writes its flat gradients and scalars into row j of one [S, row_floats] buffer: gradient buffer i at row_offsets[i] (the
+    table's order, each start rounded up to 4 floats), then ROW_SCALARS slots for SCALAR_KEYS.  Engine.grad_combine reduces
+    the rows in shard order into row 0, which feeds the update.  The result depends on (B, m) alone.
+
+    data_parallel=True (construction keyword, with torch.distributed initialised, world size W): every rank is handed the
+    full batch, computes the shards dist.shard_range(S, rank, W) (S % W == 0) and the ranks exchange rows by one all-gather;
+    the combine, Adam and the re-pack then run on every rank on identical bits, so a run on W ranks has the bits of the
+    run on one with the same (B, m).  save() writes on rank 0 only; restore() is every rank's."""
+    DATA_PARALLEL_REFUSAL = None
+    data_parallel, world, rank = False, 1, 0
+    record_events = False             # True: step keeps (start, exchanged, combined) device events in last_events
+    last_events = None
 
     def _init_optimiser(self, lr, beta1, beta2, eps, ema_decay, clip_norm):
         self.lr, self.beta1, self.beta2, self.eps = lr, float(beta1), float(beta2), float(eps)
@@ -272,6 +373,13 @@ class _DeviceTrainer(object):
         trained = set(name for tab in tables for name, _, _ in tab)
         self._frozen = {k: np.array(a, np.float32) for k, a in weights.items() if k not in trained}   # upsampler=False
         self.sumsq = torch.zeros(1, dtype=torch.float64, device=dev)
+        # a shard's row: every gradient buffer on the 16-byte grid (the vector paths of the combine and of Adam), the scalars last
+        self.row_offsets, off = [], 0
+        for p in self.p:
+            self.row_offsets.append(off)
+            off += (p.numel() + 3) // 4 * 4
+        self.row_scalars, self.row_floats = off, off + ROW_SCALARS
+        self._rows = None                 # the [S, row_floats] buffer of the last sharded step, kept for the next
         self.global_step = 0              # completed steps
         self.lr_t = None                  # the bias-corrected rate of the last step, as handed to the kernel (float32)
         self.lr_history = []              # the scheduled rate of every step
@@ -290,6 +398,80 @@ class _DeviceTrainer(object):
                           sumsq=self.sumsq if self.clip_norm is not None else None,
                           clip_norm=self.clip_norm if self.clip_norm is not None else 1.0)
         return self.sumsq.sqrt()[0]
+
+    DEFER_NON_CONVERGENCE = False     # True: a shard that did not converge fails the step only after every shard has run
+
+    def _plan(self, inputs, micro_batch, noise=None):
+        """A step's cut, settled before anything is computed -- every refusal here is one all ranks share, so none of them
+        leaves the others waiting in the exchange.  None: one shard, the unsharded path.  Otherwise (m, S, first shard, one
+        past the last shard of this rank)."""
+        if micro_batch is None and self.world == 1:
+            return None
+        who = type(self).__name__
+        per_row = [(k, inputs[k]) for k in ROW_INPUTS if k in inputs] + ([('noise', noise)] if noise is not None else [])
+        if 'mel' not in inputs:
+            raise KeyError("{}.step: inputs lack 'mel'".format(who))
+        B = int(inputs['mel'].shape[0])
+        for k, v in per_row:
+            if int(v.shape[0]) != B:
+                raise ValueError('{}.step: {} has {} rows, mel has {}'.format(who, k, int(v.shape[0]), B))
+        m = B if micro_batch is None else int(micro_batch)
+        S, (lo, hi), _ = shard_plan(B, m, self.world, self.rank)
+        return None if S == 1 else (m, S, lo, hi)
+
+    def _sharded_step(self, inputs, plan, noise=None):
+        """shards lo .. hi - 1 into their rows, the exchange, the combine, the update; returns (the shards' outputs, the
+        step's dict: the combined scalars, 'log_probs' of this rank's rows where the model gives them, 'rows', 'grad_norm')"""
+        from . import dist as wdist
+        from .engine import grad_combine
+        m, S, lo, hi = plan
+        dev = self.eng.device
+        if self._rows is None or int(self._rows.shape[0]) != S:
+            self._rows = None             # let go of the old buffer first
+            self._rows = torch.zeros(S, self.row_floats, dtype=torch.float32, device=dev)
+        buf = self._rows
+        outs, failed = [], []
+        for j in range(lo, hi):
+            rows = {k: inputs[k][j * m:(j + 1) * m] for k in ROW_INPUTS if k in inputs}
+            try:
+                out, flats = self._shard(rows, j, None if noise is None else noise[j * m:(j + 1) * m])
+            except NotConverged as e:
+                if not self.DEFER_NON_CONVERGENCE:
+                    raise
+                failed.append('shard {}: {}'.format(j, e))
+                continue
+            row = buf[j]
+            for off, g in zip(self.row_offsets, flats):
+                row[off:off + g.numel()].copy_(g)
+            for i, key in enumerate(SCALAR_KEYS):         # a slot without its key stays at the zero it was created with
+                if key in out:
+                    row[self.row_scalars + i].copy_(out[key])
+            outs.append(out)
+        if failed:
+            raise NotConverged('{}.step: {} of {} shards did not converge, nothing was updated; {}'.format(
+                type(self).__name__, len(failed), hi - lo, '; '.join(failed)))
+        with torch.cuda.device(dev):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if self.record_events else None
+            if ev:
+                ev[0].record()
+            if self.world > 1:
+                wdist.exchange_rows(buf, lo, hi)
+            if ev:
+                ev[1].record()
+            grad_combine(buf, out=buf[0])
+            if ev:
+                ev[2].record()
+                self.last_events = ev
+        scalars = buf[0, self.row_scalars:].clone()           # row 0 is the next step's first row
+        norm = self._update([buf[0, off:off + p.numel()] for off, p in zip(self.row_offsets, self.p)])
+        self._repack(self.p)
+        self.global_step += 1
+        ret = {key: scalars[i] for i, key in enumerate(SCALAR_KEYS) if key in outs[0]}
+        if 'log_probs' in outs[0]:
+            ret['log_probs'] = torch.cat([o['log_probs'] for o in outs], dim=0)
+        ret['rows'] = torch.arange(lo * m, hi * m, device=dev)
+        ret['grad_norm'] = norm
+        return outs, ret
 
     def weights(self, ema=False):
         """{tf name: numpy array in the TF shape} of every variable of the model: the weights, or with ema=True the shadow
@@ -316,7 +498,10 @@ class _DeviceTrainer(object):
         reference's training graph -- '<var>', '<var>/Adam', '<var>/Adam_1', '<var>/ExponentialMovingAverage' for every
         trained variable, the plain name alone for a frozen one, 'global_step', 'beta1_power', 'beta2_power' -- and the
         `checkpoint` state file.  The eval CLIs load the directory as it is (shadows preferred); restore() continues from it.
-        Returns the prefix."""
+        Returns the prefix.  In a data-parallel run every rank holds the same state: rank 0 alone writes, the others return
+        the prefix it writes to."""
+        if self.rank != 0:
+            return os.path.join(logdir, 'model.ckpt-{:d}'.format(self.global_step))
         host = [[b.cpu().numpy() for b in bufs] for bufs in (self.p, self.m, self.v, self.ema)]
         trained = {}
         for i, tab in enumerate(self.tables):
@@ -368,6 +553,10 @@ class TeacherTrainer(_DeviceTrainer):
               dropout_step_seed(dropout_seed, k), so a trainer built with global_step = n set continues the same sequence.
               feed_forward, calculate_loss and generation on the handle stay deterministic, like the reference's
               use_as_teacher graph.
+    data_parallel: (keyword) True under an initialised torch.distributed group: the trainer computes its rank's shards of
+              every step and all ranks keep the same state (_DeviceTrainer).
+    step(batch, micro_batch=m) runs the step in B / m shards, shard j under the seed shard_seed(step seed, j); the result is
+    a function of (B, m) and not of the number of ranks.
 
     Order inside a step (the reference's tf.group leaves it open): Adam first, with t = completed steps + 1; then the EMA of
     the UPDATED weights with num_updates = the number of steps completed BEFORE this one, i.e. the decay of step 1 is
@@ -391,23 +580,36 @@ class TeacherTrainer(_DeviceTrainer):
         sizes = [eng.teacher_grad_floats()] + ([eng.deconv_grad_floats('')] if self.upsampler else [])
         self._init_buffers(weights, tables, sizes)
 
-    def _grads(self, inputs):
-        seed = dropout_step_seed(self.dropout_seed, self.global_step) if self.dropout else None
+    def _shard(self, inputs, j=0, noise=None):
+        """(the call's dict, its flat gradients in table order) of shard j of the current step; j = 0 on the whole batch is
+        the unsharded step"""
+        seed = shard_seed(dropout_step_seed(self.dropout_seed, self.global_step), j) if self.dropout else None
         out = self.net.loss_and_weight_grads(inputs, upsampler=self.upsampler, dropout_seed=seed)
         flats = [out['flat_grads']]
         if self.upsampler:
             flats.append(out['flat_upsampler_grads'])
         return out, flats
 
+    def _grads(self, inputs):
+        return self._shard(inputs)
+
     def _repack(self, bufs):
         self.eng.teacher_set_weights(bufs[0], bufs[1] if self.upsampler else None)
 
-    def step(self, inputs):
+    def step(self, inputs, micro_batch=None):
         """One training step on {'wav': [B,T], 'mel': [B,F,80]} -> {'loss': the loss BEFORE the update (the bits of
         calculate_loss(feed_forward(.)) under the weights in force at entry; with dropout those of
         loss_and_weight_grads(dropout_seed=dropout_step_seed(dropout_seed, global_step))), 'log_probs': [B,T], 'grad_norm':
-        the global norm of the gradient before clipping}, all device tensors."""
-        out, flats = self._grads(inputs)
+        the global norm of the gradient before clipping}, all device tensors.
+
+        micro_batch=m < B: the step in S = B / m shards (the class's notes).  Shard j is
+        loss_and_weight_grads on rows [j m, (j + 1) m) under dropout_seed = shard_seed(dropout_step_seed(dropout_seed,
+        global_step), j); 'loss' is the combine of the shards' losses (float32), 'log_probs' holds the rows this process
+        computed, in shard order, and 'rows' names their indices in the batch.  None or m = B is the step above, bit for bit."""
+        plan = self._plan(inputs, micro_batch)
+        if plan is not None:
+            return self._sharded_step(inputs, plan)[1]
+        out, flats = self._shard(inputs)
         norm = self._update(flats)
         self._repack(self.p)
         self.global_step += 1
@@ -424,7 +626,9 @@ class StudentTrainer(_DeviceTrainer):
     upsampler: also train the deconv stacks the student owns ('iaf_share', or 'iaf_k' per flow), as the reference's
               filter_update_variables keeps them; with use_teacher_deconv the encoding is the teacher's and no stack is trained.
     seed:     step k (k completed steps before it) runs loss_and_weight_grads(seed=seed + k): the student's draw (unless
-              `noise` is handed to step) and the Monte-Carlo draws of the losses.
+              `noise` is handed to step) and the Monte-Carlo draws of the losses.  Shard j of a sharded step
+              (step(batch, micro_batch=m)) runs under shard_seed(seed + k, j).
+    data_parallel: (keyword) as for TeacherTrainer.
 
     Buffers: one (p, m, v, ema) set for the flows, laid out by Engine.iaf_grad_table(), and one per trained stack, laid out
     by Engine.deconv_grad_table(scope).  Order inside a step, the learning-rate schedule and the EMA decay are
@@ -461,12 +665,24 @@ class StudentTrainer(_DeviceTrainer):
     def _repack(self, bufs):
         self.eng.iaf_set_weights(bufs[0], dict(zip(self.scopes, bufs[1:])))
 
-    def step(self, inputs, noise=None):
+    def _shard(self, inputs, j=0, noise=None):
+        out = self.net.loss_and_weight_grads(inputs, seed=shard_seed(self.seed + self.global_step, j), noise=noise,
+                                             upsampler=self.upsampler)
+        return out, [out['flat_grads']] + [out['flat_upsampler_grads'][s] for s in self.scopes]
+
+    def step(self, inputs, noise=None, micro_batch=None):
         """One training step on {'mel': [B,F,80], 'wav': [B,T'] (+ 'mel_rand')} -> calculate_loss's entries BEFORE the update
         (the bits of loss_and_weight_grads(inputs, seed=seed + global_step, noise=noise) under the weights in force at entry)
-        plus 'grad_norm', the global norm of the gradient before clipping; all device tensors."""
-        out = self.net.loss_and_weight_grads(inputs, seed=self.seed + self.global_step, noise=noise, upsampler=self.upsampler)
-        flats = [out['flat_grads']] + [out['flat_upsampler_grads'][s] for s in self.scopes]
+        plus 'grad_norm', the global norm of the gradient before clipping; all device tensors.
+
+        micro_batch=m < B: the step in S = B / m shards (_DeviceTrainer's notes).  Shard j is
+        loss_and_weight_grads on rows [j m, (j + 1) m) of the inputs (and of `noise`) under seed = shard_seed(seed +
+        global_step, j); every entry of calculate_loss is the combine of the shards' (float32), and 'rows' names the rows this
+        process computed.  None or m = B is the step above, bit for bit."""
+        plan = self._plan(inputs, micro_batch, noise)
+        if plan is not None:
+            return self._sharded_step(inputs, plan, noise)[1]
+        out, flats = self._shard(inputs, 0, noise)
         norm = self._update(flats)
         self._repack(self.p)
         self.global_step += 1
@@ -483,7 +699,9 @@ class StudentMleTrainer(StudentTrainer):
     pw, weights, lr, beta1, beta2, eps, ema_decay, clip_norm, upsampler: as for StudentTrainer (no mu-law, no weight norm;
     width and deconv_width multiples of 64).  encode_tol: the tolerance of the encode's sweeps (README: 1e-5 for the shipped
     student); adjoint_tol: that of the adjoint's (None: Engine.ADJOINT_TOL).  max_sweeps: the bound of both, None for T.
-    The buffers, the update, the re-pack, save() and restore() are StudentTrainer's; nothing is drawn, so there is no seed."""
+    The buffers, the update, the re-pack, save() and restore() are StudentTrainer's; nothing is drawn, so there is no seed.
+    step(batch, micro_batch=m) shards the step in one process; data_parallel=True is refused (a rank that did not converge
+    could not tell the others before the exchange)."""
 
     def __init__(self, pw, weights, lr=2e-4, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay=0.9999, clip_norm=None,
                  upsampler=True, encode_tol=1e-5, adjoint_tol=None, max_sweeps=None):
@@ -500,18 +718,37 @@ class StudentMleTrainer(StudentTrainer):
         self.encode_tol, self.adjoint_tol = float(encode_tol), None if adjoint_tol is None else float(adjoint_tol)
         self.max_sweeps = None if max_sweeps is None else int(max_sweeps)
 
-    def step(self, inputs):
-        """One training step on {'mel': [B,F,80], 'wav': [B,T']} -> {'loss': -mean log p BEFORE the update (the bits of
-        nll_and_weight_grads under the weights in force at entry), 'log_probs', 'grad_norm': the global norm of the gradient
-        before clipping, 'sweeps', 'adjoint_sweeps', 'converged'}.  Raises, with nothing updated, when the encode or the
-        adjoint did not converge."""
-        for k in ('mel', 'wav'):
-            if k not in inputs:
-                raise KeyError('StudentMleTrainer.step: inputs lack {!r}'.format(k))
+    DATA_PARALLEL_REFUSAL = ('a rank whose encode or adjoint did not converge would have to tell the others through the '
+                             'exchange; run the shards in one process (micro_batch=)')
+    DEFER_NON_CONVERGENCE = True
+
+    def _shard(self, inputs, j=0, noise=None):
         kw = {} if self.max_sweeps is None else {'max_sweeps': self.max_sweeps}
         out = self.net.nll_and_weight_grads(inputs, upsampler=self.upsampler, encode_tol=self.encode_tol,
                                             adjoint_tol=self.adjoint_tol, **kw)
-        flats = [out['flat_grads']] + [out['flat_upsampler_grads'][s] for s in self.scopes]
+        return out, [out['flat_grads']] + [out['flat_upsampler_grads'][s] for s in self.scopes]
+
+    def step(self, inputs, micro_batch=None):
+        """One training step on {'mel': [B,F,80], 'wav': [B,T']} -> {'loss': -mean log p BEFORE the update (the bits of
+        nll_and_weight_grads under the weights in force at entry), 'log_probs', 'grad_norm': the global norm of the gradient
+        before clipping, 'sweeps', 'adjoint_sweeps', 'converged'}.  Raises, with nothing updated, when the encode or the
+        adjoint did not converge.
+
+        micro_batch=m < B: the step in S = B / m shards (_DeviceTrainer's notes), shard j being
+        nll_and_weight_grads on rows [j m, (j + 1) m).  'loss' is the combine of the shards' losses (float32), 'sweeps' and
+        'adjoint_sweeps' the largest of any shard, 'converged' and 'log_probs' cover all rows, 'rows' names them.  Every
+        shard runs; if one did not converge the step raises afterwards, with nothing updated.  None or m = B is the step
+        above, bit for bit.  One process only: data_parallel=True is refused."""
+        for k in ('mel', 'wav'):
+            if k not in inputs:
+                raise KeyError('StudentMleTrainer.step: inputs lack {!r}'.format(k))
+        plan = self._plan(inputs, micro_batch)
+        if plan is not None:
+            outs, ret = self._sharded_step(inputs, plan)
+            ret.update({'sweeps': max(o['sweeps'] for o in outs), 'adjoint_sweeps': max(o['adjoint_sweeps'] for o in outs),
+                        'converged': torch.cat([o['converged'] for o in outs])})
+            return ret
+        out, flats = self._shard(inputs)
         norm = self._update(flats)
         self._repack(self.p)
         self.global_step += 1

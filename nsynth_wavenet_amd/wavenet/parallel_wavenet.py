@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from .. import config as cfg
-from ..engine import Engine
+from ..engine import Engine, NotConverged
 from .. import distill_autograd as dag
 
 
@@ -134,7 +134,7 @@ class ParallelWavenet(object):
             return self._log_prob_grad(inputs[key], inputs['mel'], adjoint_tol, kw)
         r = self.encode(inputs, **kw)
         if not bool(r['converged'].all()):
-            raise RuntimeError('log_prob: the inverse did not converge in {} sweeps'.format(r['sweeps']))
+            raise NotConverged('log_prob: the inverse did not converge in {} sweeps'.format(r['sweeps']))
         return {'log_probs': r['log_probs'], 'loss': -(r['log_prob_sums'].sum() / r['log_probs'].numel())}
 
     def _log_prob_grad(self, wav, mel, adjoint_tol, kw):
@@ -142,7 +142,7 @@ class ParallelWavenet(object):
         wav, mel = eng._dev(wav), eng._dev(mel)          # differentiable for tensors: the gradients return to the caller's
         enc = eng.iaf_encode(wav.detach(), mel.detach(), want=('z', 'log_prob'), **kw)
         if not bool(enc['converged'].all()):
-            raise RuntimeError('log_prob: the inverse did not converge in {} sweeps'.format(enc['sweeps']))
+            raise NotConverged('log_prob: the inverse did not converge in {} sweeps'.format(enc['sweeps']))
         adj = {'adjoint_tol': adjoint_tol, 'check_every': kw.get('check_every', 8)}
         lp, sums = dag.IafLogProb.apply(wav, mel, eng, self._input_grad_stacks(), enc, adj)
         return {'log_probs': lp, 'loss': -(sums.sum() / lp.numel())}
@@ -170,7 +170,7 @@ class ParallelWavenet(object):
             wav = _trim(wav, int(wav.shape[1]) - T).contiguous()
         enc = eng.iaf_encode(wav, mel, want=('z', 'log_prob'), tol=encode_tol, **kw)
         if not bool(enc['converged'].all()):
-            raise RuntimeError('nll_and_weight_grads: the inverse did not converge in {} sweeps'.format(enc['sweeps']))
+            raise NotConverged('nll_and_weight_grads: the inverse did not converge in {} sweeps'.format(enc['sweeps']))
         lp, n = enc['log_prob'], enc['log_prob'].numel()
         # the cotangent of log p under -mean, as autograd hands it to IafLogProb.backward: the same bits on both roads
         c = torch.full(tuple(lp.shape), -1.0 / n, dtype=torch.float64, device=lp.device).to(torch.float32)
