@@ -449,20 +449,6 @@ int bwd_check(const wn_handle* h, const char* fn, const char* scope, int* si, bo
 #undef DB_REFUSE
 }
 
-std::vector<WnGradEntry> dgrad_table(const wn_handle* h, int si) {
-    std::vector<WnGradEntry> t;
-    const DeconvStackPack& sp = h->stacks[si];
-    size_t off = 0;
-    for (size_t j = 0; j < sp.layers.size(); ++j) {
-        const DeconvLayerPack& lp = sp.layers[j];
-        const std::string base = (sp.prefix.empty() ? std::string() : sp.prefix + "/") + "trans_conv_" + std::to_string(j + 1);
-        t.push_back(WnGradEntry{base + "/kernel", off, {1, lp.K, lp.cout, lp.cin}, 4});
-        off += (size_t)lp.K * lp.cout * lp.cin;
-        t.push_back(WnGradEntry{base + "/bias", off, {lp.cout, 0, 0, 0}, 1});
-        off += (size_t)lp.cout;
-    }
-    return t;
-}
 }  // namespace
 
 // W^T of every layer but the first as two planes of halves [k][ci][co], prescaled like the forward's packs; called by
@@ -506,25 +492,36 @@ int wn_pack_deconv_bwd(wn_handle* h, std::vector<float>& blob) {
     return WN_OK;
 }
 
-std::vector<WnGradEntry> wn_deconv_grad_table(const wn_handle* h, int si) { return dgrad_table(h, si); }
+// the parameter layout of every stack: per layer the kernel [1][K][cout][cin], then the bias
+void wn_deconv_build_layout(wn_handle* h) {
+    for (DeconvStackPack& sp : h->stacks) {
+        sp.lay.clear();
+        sp.table = WnGradTable();
+        for (size_t j = 0; j < sp.layers.size(); ++j) {
+            const DeconvLayerPack& lp = sp.layers[j];
+            const std::string scope = (sp.prefix.empty() ? std::string() : sp.prefix + "/") + "trans_conv_" + std::to_string(j + 1);
+            sp.lay.push_back(sp.table.conv(scope, "/kernel", "/bias", lp.K, lp.cout, lp.cin, lp.cout));
+        }
+    }
+}
 
 extern "C" int wn_deconv_grad_count(const wn_handle* h, const char* scope) {
     int si;
     if (bwd_check(h, "wn_deconv_grad_count", scope, &si, true)) return 0;
-    return (int)dgrad_table(h, si).size();
+    return (int)h->stacks[si].table.entries.size();
 }
 
 extern "C" int wn_deconv_grad_info(const wn_handle* h, const char* scope, int i, char* name, size_t name_cap, int64_t* offset,
                                    int64_t* shape4, int* ndim) {
     int si;
     if (int rc = bwd_check(h, "wn_deconv_grad_info", scope, &si, false)) return rc;
-    return wn_grad_info(h, "wn_deconv_grad_info", dgrad_table(h, si), i, name, name_cap, offset, shape4, ndim);
+    return wn_grad_info(h, "wn_deconv_grad_info", h->stacks[si].table.entries, i, name, name_cap, offset, shape4, ndim);
 }
 
 extern "C" size_t wn_deconv_grad_floats(const wn_handle* h, const char* scope) {
     int si;
     if (bwd_check(h, "wn_deconv_grad_floats", scope, &si, true)) return 0;
-    return wn_grad_floats(dgrad_table(h, si));
+    return h->stacks[si].table.floats;
 }
 
 extern "C" size_t wn_deconv_backward_workspace_bytes(const wn_handle* h, const char* scope, int B, int F) {
@@ -541,9 +538,8 @@ extern "C" int wn_deconv_backward(wn_handle* h, const char* scope, const float* 
     if (!mel || !d_enc || !grads || !ws || B < 1 || F < 1) return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
     if (B > 65535) return wn_fail(h, WN_EINVAL, "%s: B = %d above 65535", fn, B);
     const DeconvStackPack& sp = h->stacks[si];
-    const std::vector<WnGradEntry> tab = dgrad_table(h, si);
-    if (grads_floats < wn_grad_floats(tab))
-        return wn_fail(h, WN_EINVAL, "%s: grads holds %zu floats, the gradients need %zu", fn, grads_floats, wn_grad_floats(tab));
+    if (grads_floats < sp.table.floats)
+        return wn_fail(h, WN_EINVAL, "%s: grads holds %zu floats, the gradients need %zu", fn, grads_floats, sp.table.floats);
     const BwdLayout BL = bwd_layout(h, sp, B, F);
     if (ws_bytes < BL.total) return wn_fail(h, WN_EINVAL, "%s: workspace %zu < %zu bytes", fn, ws_bytes, BL.total);
     const int nl = (int)sp.layers.size();
@@ -613,8 +609,8 @@ extern "C" int wn_deconv_backward(wn_handle* h, const char* scope, const float* 
         hipLaunchKernelGGL(db_wgrad_kernel, dim3((d.C / 64) * (d.cinp / 64), d.S * d.taps, d.nslab), dim3(256), 0, st, dzc, xs, d.C,
                            d.cin, d.cinp, d.N, d.S, d.taps, d.pL, d.nsh, DB_SLAB, part, nw);
         hipLaunchKernelGGL(db_reduce_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, part, nw, d.nslab, sj,
-                           grads + tab[2 * j].off);
-        hipLaunchKernelGGL(db_bias_kernel, dim3(d.C), dim3(256), 0, st, dzc, d.C, d.S, d.N, sj, grads + tab[2 * j + 1].off);
+                           grads + sp.lay[j].W);
+        hipLaunchKernelGGL(db_bias_kernel, dim3(d.C), dim3(256), 0, st, dzc, d.C, d.S, d.N, sj, grads + sp.lay[j].b);
         if (j > 0) {
             // the slabs of the weight gradient are reduced by now: `part` holds the phase chunks of dx next
             hipLaunchKernelGGL(db_dgrad_kernel, dim3((d.cin / 64) * ((d.L + 63) / 64), B, d.npc), dim3(256), 0, st,

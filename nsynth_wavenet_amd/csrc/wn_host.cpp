@@ -299,6 +299,10 @@ extern "C" int wn_finalize(wn_handle* h) {
     }
     rc = wn_pack_deconv_bwd(h, blob);   // last: the packs above keep their offsets
     if (rc) return rc;
+    // the parameter layouts of the training calls: a function of the configuration and the packs' shapes
+    if (h->cfg.kind == WN_KIND_STUDENT) wn_iaf_build_layout(h);
+    else wn_teacher_build_layout(h);
+    wn_deconv_build_layout(h);
     WN_HIP(h, hipSetDevice(h->device));
     h->blob_floats = blob.size();
     WN_HIP(h, hipMalloc((void**)&h->d_blob, blob.size() * sizeof(float)));

@@ -98,17 +98,13 @@ struct Plan {
     size_t o_rb = 0, o_post = 0, o_abs = 0, o_copy = 0, o_pcopy = 0, o_frag = 0, o_bias = 0, o_tile = 0, total = 0;
 };
 
-struct Conv {
-    const float *W, *b;
-};
-
 void build_plan(wn_handle* h, const float* params, Plan& P) {
     const wn_config& c = h->cfg;
     const int W = c.width, H = W / 2, Cd = c.deconv_width;
     float* blob = h->d_blob;
-    const std::vector<WnGradEntry> tab = wn_iaf_grad_table(h);
-    size_t k = 0;
-    auto next = [&]() { Conv v{params + tab[k].off, params + tab[k + 1].off}; k += 2; return v; };
+    // a source variable: params + its offset in the handle's layout
+    auto Wp = [&](const WnConvOff& o) { return params + o.W; };
+    auto bp = [&](const WnConvOff& o) { return params + o.b; };
     auto absmax = [&](const float* src, size_t n) {
         P.abs.push_back(RpAbs{src, (unsigned)n, (unsigned)P.nslots});
         P.max_abs = std::max(P.max_abs, (unsigned)n);
@@ -165,93 +161,93 @@ void build_plan(wn_handle* h, const float* params, Plan& P) {
 
     for (int f = 0; f < c.n_flows; ++f) {
         const int nl = c.iaf_layers[f];
-        const Conv start = next();
-        std::vector<Conv> dil(nl), cond(nl), res(nl);
-        for (int i = 0; i < nl; ++i) { dil[i] = next(); cond[i] = next(); res[i] = next(); }
-        const Conv out1 = next(), cout1 = next(), omean = next(), oscale = next();
+        const IafFlowLayout& fo = h->iaf_train.lay.flows[f];
+        const std::vector<IafLayerOff>& lo = fo.layers;
         // ---- the absolute maxima, per source variable
         std::vector<int> s_d(nl), s_c(nl), s_r(nl);
         for (int i = 0; i < nl; ++i) {
-            s_d[i] = absmax(dil[i].W, (size_t)3 * W * W);
-            s_c[i] = absmax(cond[i].W, (size_t)Cd * W);
-            s_r[i] = absmax(res[i].W, (size_t)H * W);
+            s_d[i] = absmax(Wp(lo[i].dil), (size_t)3 * W * W);
+            s_c[i] = absmax(Wp(lo[i].cond), (size_t)Cd * W);
+            s_r[i] = absmax(Wp(lo[i].res), (size_t)H * W);
         }
-        const int s_o = absmax(out1.W, (size_t)W * W), s_co = absmax(cout1.W, (size_t)Cd * W);
-        const int s_m = absmax(omean.W, W), s_s = absmax(oscale.W, W);
+        const int s_o = absmax(Wp(fo.out1), (size_t)W * W), s_co = absmax(Wp(fo.cond_out1), (size_t)Cd * W);
+        const int s_m = absmax(Wp(fo.out2_mean), W), s_s = absmax(Wp(fo.out2_scale), W);
         // ---- generation packs
         if (h->generic_student) {                        // wn_pack_iaf_x: plain copies; the two head biases are host floats
             IafFlowX& fx = h->flows_x[f];
-            copy(start.W, blob + fx.start, (size_t)4 * W);          // W [3][1][W] and the biases are neighbours in the table
+            copy(Wp(fo.start), blob + fx.start, (size_t)4 * W);      // W [3][1][W] and the biases are neighbours in the table
             for (int i = 0; i < nl; ++i) {
                 const IafLayerX& lx = fx.layers[i];
-                copy(dil[i].W, blob + lx.wd, (size_t)3 * W * W);
-                copy(cond[i].W, blob + lx.wc, (size_t)Cd * W);
-                copy(res[i].W, blob + lx.wr, (size_t)H * W);
-                copy(dil[i].b, blob + lx.bd, W);
-                copy(cond[i].b, blob + lx.bc, W);
-                copy(res[i].b, blob + lx.br, W);
+                copy(Wp(lo[i].dil), blob + lx.wd, (size_t)3 * W * W);
+                copy(Wp(lo[i].cond), blob + lx.wc, (size_t)Cd * W);
+                copy(Wp(lo[i].res), blob + lx.wr, (size_t)H * W);
+                copy(bp(lo[i].dil), blob + lx.bd, W);
+                copy(bp(lo[i].cond), blob + lx.bc, W);
+                copy(bp(lo[i].res), blob + lx.br, W);
             }
-            copy(out1.W, blob + fx.wo, (size_t)W * W);
-            copy(cout1.W, blob + fx.wco, (size_t)Cd * W);
-            copy(out1.b, blob + fx.bo, W);
-            copy(cout1.b, blob + fx.bco, W);
-            copy(omean.W, blob + fx.wm, W);
-            copy(oscale.W, blob + fx.ws, W);
-            read_back(omean.b);
-            read_back(oscale.b);
+            copy(Wp(fo.out1), blob + fx.wo, (size_t)W * W);
+            copy(Wp(fo.cond_out1), blob + fx.wco, (size_t)Cd * W);
+            copy(bp(fo.out1), blob + fx.bo, W);
+            copy(bp(fo.cond_out1), blob + fx.bco, W);
+            copy(Wp(fo.out2_mean), blob + fx.wm, W);
+            copy(Wp(fo.out2_scale), blob + fx.ws, W);
+            read_back(bp(fo.out2_mean));
+            read_back(bp(fo.out2_scale));
         } else {                                         // wn_pack_iaf and wn_pack_iaf_h, width 64 and deconv_width 256
             IafFlowPack& fp = h->flows[f];
-            copy(start.W, blob + fp.start_off, (size_t)4 * W);
+            copy(Wp(fo.start), blob + fp.start_off, (size_t)4 * W);
             for (int i = 0; i < nl; ++i) {
                 const IafLayerPack& lp = fp.layers[i];
-                frag32(dil[i].W, cond[i].W, 3 * IAF_W, lp.off, 112);
-                frag32(res[i].W, nullptr, IAF_W / 2, lp.off + IAF_P_FLOATS, 8);
+                frag32(Wp(lo[i].dil), Wp(lo[i].cond), 3 * IAF_W, lp.off, 112);
+                frag32(Wp(lo[i].res), nullptr, IAF_W / 2, lp.off + IAF_P_FLOATS, 8);
                 const size_t tb = lp.off + IAF_P_FLOATS + IAF_PR_FLOATS;
-                lane_bias(dil[i].b, cond[i].b, tb, 0);
-                lane_bias(res[i].b, nullptr, tb + 64, 0);
+                lane_bias(bp(lo[i].dil), bp(lo[i].cond), tb, 0);
+                lane_bias(bp(lo[i].res), nullptr, tb + 64, 0);
                 const int rm = rule(s_d[i], s_c[i], true), rr = rule(s_r[i], -1, false);
-                frag_h(lp.off_h, rm, dil[i].W, cond[i].W, 3 * IAF_W, 14);
-                frag_h(lp.off_h + IAF_P_FLOATS, rr, res[i].W, nullptr, IAF_W / 2, 1);
+                frag_h(lp.off_h, rm, Wp(lo[i].dil), Wp(lo[i].cond), 3 * IAF_W, 14);
+                frag_h(lp.off_h + IAF_P_FLOATS, rr, Wp(lo[i].res), nullptr, IAF_W / 2, 1);
                 const size_t th = lp.off_h + IAF_P_FLOATS + IAF_PR_FLOATS;
-                lane_bias(dil[i].b, cond[i].b, th, 1);
-                lane_bias(res[i].b, nullptr, th + 64, 0);
+                lane_bias(bp(lo[i].dil), bp(lo[i].cond), th, 1);
+                lane_bias(bp(lo[i].res), nullptr, th + 64, 0);
                 post_inv(th + 128, rm);
                 post_inv(th + 129, rr);
             }
             for (int form = 0; form < 2; ++form) {       // the head of the fp32 pack, then of the split-fp16 pack
                 const size_t head = form == 0 ? fp.head_off : fp.head_off_h, tb = head + IAF_PH_FLOATS;
-                if (form == 0) frag32(out1.W, cout1.W, IAF_W, head, 80);
+                if (form == 0) frag32(Wp(fo.out1), Wp(fo.cond_out1), IAF_W, head, 80);
                 else {
                     const int rh = rule(s_o, s_co, true);
-                    frag_h(head, rh, out1.W, cout1.W, IAF_W, 10);
+                    frag_h(head, rh, Wp(fo.out1), Wp(fo.cond_out1), IAF_W, 10);
                     post_inv(tb + 194, rh);
                 }
-                lane_bias(out1.b, cout1.b, tb, 0);
-                lane_bias(omean.W, nullptr, tb + 64, 0);
-                lane_bias(oscale.W, nullptr, tb + 128, 0);
-                copy(omean.b, blob + tb + 192, 1);
-                copy(oscale.b, blob + tb + 193, 1);
+                lane_bias(bp(fo.out1), bp(fo.cond_out1), tb, 0);
+                lane_bias(Wp(fo.out2_mean), nullptr, tb + 64, 0);
+                lane_bias(Wp(fo.out2_scale), nullptr, tb + 128, 0);
+                copy(bp(fo.out2_mean), blob + tb + 192, 1);
+                copy(bp(fo.out2_scale), blob + tb + 193, 1);
             }
         }
         // ---- training packs (wn_pack_iaf_train): each scale over the sources the host hands to pick_scale
         IafTrainFlow& fl = h->iaf_train.flows[f];
-        copy(start.W, blob + fl.start_off, (size_t)4 * W);
+        copy(Wp(fo.start), blob + fl.start_off, (size_t)4 * W);
         for (int i = 0; i < nl; ++i) {
             IafTrainLayer& tl = fl.layers[i];
-            gemm(tl.gate, rule(s_d[i], s_c[i], false), SRC_CAT_T, dil[i].W, cond[i].W, 3 * W, W, ROW_GATE, W, dil[i].b, cond[i].b);
-            gemm(tl.res, rule(s_r[i], -1, false), SRC_CAT_T, res[i].W, nullptr, H, W, ROW_IDENT, W, res[i].b, nullptr);
-            gemm(tl.gate_t, rule(s_d[i], -1, false), SRC_TAP_T, dil[i].W, nullptr, 0, 0, ROW_IDENT, W, nullptr, nullptr);
-            gemm(tl.res_t, rule(s_r[i], -1, false), SRC_DIRECT, res[i].W, nullptr, 0, W, ROW_IDENT, H, nullptr, nullptr);
-            gemm(tl.cond_t, rule(s_c[i], -1, false), SRC_DIRECT, cond[i].W, nullptr, 0, W, ROW_IDENT, Cd, nullptr, nullptr);
+            gemm(tl.gate, rule(s_d[i], s_c[i], false), SRC_CAT_T, Wp(lo[i].dil), Wp(lo[i].cond), 3 * W, W, ROW_GATE, W, bp(lo[i].dil),
+                 bp(lo[i].cond));
+            gemm(tl.res, rule(s_r[i], -1, false), SRC_CAT_T, Wp(lo[i].res), nullptr, H, W, ROW_IDENT, W, bp(lo[i].res), nullptr);
+            gemm(tl.gate_t, rule(s_d[i], -1, false), SRC_TAP_T, Wp(lo[i].dil), nullptr, 0, 0, ROW_IDENT, W, nullptr, nullptr);
+            gemm(tl.res_t, rule(s_r[i], -1, false), SRC_DIRECT, Wp(lo[i].res), nullptr, 0, W, ROW_IDENT, H, nullptr, nullptr);
+            gemm(tl.cond_t, rule(s_c[i], -1, false), SRC_DIRECT, Wp(lo[i].cond), nullptr, 0, W, ROW_IDENT, Cd, nullptr, nullptr);
         }
-        gemm(fl.out1, rule(s_o, s_co, false), SRC_CAT_T, out1.W, cout1.W, W, W, ROW_IDENT, W, out1.b, cout1.b);
+        gemm(fl.out1, rule(s_o, s_co, false), SRC_CAT_T, Wp(fo.out1), Wp(fo.cond_out1), W, W, ROW_IDENT, W, bp(fo.out1),
+             bp(fo.cond_out1));
         const int r2 = rule(s_m, s_s, false);
-        gemm(fl.out2, r2, SRC_ROWS2, omean.W, oscale.W, 0, W, ROW_IDENT, 2, nullptr, nullptr);
-        copy(omean.b, blob + fl.out2.b_off, 1);          // its bias rows 0 and 1; the other 62 stay zero
-        copy(oscale.b, blob + fl.out2.b_off + 1, 1);
-        gemm(fl.out1_t, rule(s_o, -1, false), SRC_DIRECT, out1.W, nullptr, 0, W, ROW_IDENT, W, nullptr, nullptr);
-        gemm(fl.out2_t, r2, SRC_COLS2, omean.W, oscale.W, 0, 32, ROW_IDENT, W, nullptr, nullptr);
-        gemm(fl.cond_out1_t, rule(s_co, -1, false), SRC_DIRECT, cout1.W, nullptr, 0, W, ROW_IDENT, Cd, nullptr, nullptr);
+        gemm(fl.out2, r2, SRC_ROWS2, Wp(fo.out2_mean), Wp(fo.out2_scale), 0, W, ROW_IDENT, 2, nullptr, nullptr);
+        copy(bp(fo.out2_mean), blob + fl.out2.b_off, 1);     // its bias rows 0 and 1; the other 62 stay zero
+        copy(bp(fo.out2_scale), blob + fl.out2.b_off + 1, 1);
+        gemm(fl.out1_t, rule(s_o, -1, false), SRC_DIRECT, Wp(fo.out1), nullptr, 0, W, ROW_IDENT, W, nullptr, nullptr);
+        gemm(fl.out2_t, r2, SRC_COLS2, Wp(fo.out2_mean), Wp(fo.out2_scale), 0, 32, ROW_IDENT, W, nullptr, nullptr);
+        gemm(fl.cond_out1_t, rule(s_co, -1, false), SRC_DIRECT, Wp(fo.cond_out1), nullptr, 0, W, ROW_IDENT, Cd, nullptr, nullptr);
     }
 }
 
@@ -313,15 +309,13 @@ extern "C" int wn_iaf_set_weights(wn_handle* h, const float* params, size_t para
     if (int rc = wn_iaf_train_check(h, fn)) return rc;
     if (!params || !ws) return wn_fail(h, WN_EINVAL, "%s: null argument", fn);
     const wn_config& c = h->cfg;
-    const std::vector<WnGradEntry> PT = wn_iaf_grad_table(h);
-    if (params_floats != wn_grad_floats(PT))
+    if (params_floats != h->iaf_train.lay.table.floats)
         return wn_fail(h, WN_EINVAL, "%s: params holds %zu floats, the layout of wn_iaf_grad_info has %zu", fn, params_floats,
-                       wn_grad_floats(PT));
+                       h->iaf_train.lay.table.floats);
     const int NS = (int)h->stacks.size();
     if (n_up != 0 && n_up != NS)
         return wn_fail(h, WN_EINVAL, "%s: n_up = %d, the student has %d deconv stack%s (or pass 0)", fn, n_up, NS, NS == 1 ? "" : "s");
     if (n_up && (!up_params || !up_floats)) return wn_fail(h, WN_EINVAL, "%s: null argument", fn);
-    std::vector<std::vector<WnGradEntry>> UT(NS);
     for (int s = 0; s < n_up; ++s) {
         if (!up_params[s]) continue;
         const std::string& scope = h->stacks[s].prefix;
@@ -329,10 +323,9 @@ extern "C" int wn_iaf_set_weights(wn_handle* h, const float* params, size_t para
             return wn_fail(h, WN_EINVAL, "%s: use_resize_conv: the resize-conv upsampler has no parameter layout; pass no up_params", fn);
         if (wn_deconv_grad_floats(h, scope.c_str()) == 0)
             return wn_fail(h, WN_EINVAL, "%s: the upsampler '%s' has no parameter layout (wn_deconv_grad_floats is 0)", fn, scope.c_str());
-        UT[s] = wn_deconv_grad_table(h, s);
-        if (up_floats[s] != wn_grad_floats(UT[s]) || UT[s].size() != 2 * h->stacks[s].layers.size())
+        if (up_floats[s] != h->stacks[s].table.floats)
             return wn_fail(h, WN_EINVAL, "%s: up_params[%d] holds %zu floats, the layout of wn_deconv_grad_info has %zu", fn, s,
-                           up_floats[s], wn_grad_floats(UT[s]));
+                           up_floats[s], h->stacks[s].table.floats);
     }
     // the tables and the scale table are read by asynchronous uploads: the handle keeps them until its next re-pack
     std::shared_ptr<Plan> keep = std::make_shared<Plan>();
@@ -374,8 +367,8 @@ extern "C" int wn_iaf_set_weights(wn_handle* h, const float* params, size_t para
         up_slot0[s] = slot0;
         slot0 += (int)h->stacks[s].layers.size();
         if (!up_params[s]) continue;
-        wn_repack_deconv_absmax(h->stacks[s], UT[s], up_params[s], amax + up_slot0[s], st);
-        wn_repack_deconv_plain(h, h->stacks[s], UT[s], up_params[s], st);
+        wn_repack_deconv_absmax(h->stacks[s], up_params[s], amax + up_slot0[s], st);
+        wn_repack_deconv_plain(h, h->stacks[s], up_params[s], st);
     }
 
     // ---- 2. the maxima and the generic flows' head biases come back (the call's one read-back: it synchronises the stream)
@@ -406,7 +399,7 @@ extern "C" int wn_iaf_set_weights(wn_handle* h, const float* params, size_t para
         hipLaunchKernelGGL(rp_copy_kernel, dim3(1, (unsigned)P.post_copy.size()), dim3(TR_NT), 0, st,
                            reinterpret_cast<const RpCopy*>(wsb + P.o_pcopy));
     for (int s = 0; s < n_up; ++s)
-        if (up_params[s]) wn_repack_deconv_split(h, h->stacks[s], UT[s], up_params[s], mx.data() + up_slot0[s], st);
+        if (up_params[s]) wn_repack_deconv_split(h, h->stacks[s], up_params[s], mx.data() + up_slot0[s], st);
     WN_HIP(h, hipGetLastError());
     return WN_OK;
 }

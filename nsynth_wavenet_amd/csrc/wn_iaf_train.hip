@@ -10,7 +10,6 @@
 //                     the pre-ReLU values in accumulator layout (the mask of out1^T)
 //   it_head_kernel    after out2: scale = clamp(softplus(p)), x <- x scale + mean, mean_tot, scale_tot; tapes x, scale, p
 //   it_binit_kernel / it_bhead_kernel   their transposes, flow n -> 1
-//   it_dx_kernel      the start conv transposed, added to the running d x
 //   it_denc_kernel    a flow's d enc rows, unscaled, stored or added into its stack's slice
 //   it_dnoise_kernel  wn_iaf_backward_input: d x of flow 1's input plus the noise's own factor in x
 // The layer inputs l_i live in consecutive slots of the tape: the gate reads slot i, the residual GEMM (RSC epilogue) reads
@@ -139,39 +138,6 @@ __global__ __launch_bounds__(256) void it_bhead_kernel(const ItBHead a) {
     a.dx[j] = gx * s;
     a.dM[j] = gM * s;
     a.dS[j] = gS * s;
-}
-
-// the start conv transposed (l0(t) = b + w0 x(t-3) + w1 x(t-2) + w2 x(t-1), the arithmetic of tb_dx_kernel), added:
-// dx(t) += scal[1] sum_c (w0[c] dl0[c](t+3) + w1[c] dl0[c](t+2) + w2[c] dl0[c](t+1))
-__global__ __launch_bounds__(256) void it_dx_kernel(const unsigned* __restrict__ dl, const float* __restrict__ wb,
-                                                    const float* __restrict__ scal, float* __restrict__ dx, int W, long long T,
-                                                    long long Tp) {
-    __shared__ float red[4][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.y, NG = W / 8;
-    const long long t = (long long)blockIdx.x * 64 + lane;
-    float acc = 0.f;
-    if (t < T) {
-        const unsigned* base = dl + (size_t)b * W * Tp;
-        for (int gr = wave; gr < NG; gr += 4) {
-            for (int k = 0; k < 3; ++k) {
-                const long long col = t + 3 - k;
-                if (col >= T) continue;
-                wn_u4 hw, lw;
-                wn_g4_load(base, NG, Tp, gr, col, hw, lw);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float v0, v1;
-                    wn_join_pair(hw[i], lw[i], v0, v1);
-                    const int ch = wn_g4_channel(gr, i);
-                    acc = fmaf(wb[k * W + ch], v0, acc);
-                    acc = fmaf(wb[k * W + ch + 1], v1, acc);
-                }
-            }
-        }
-    }
-    red[wave][lane] = acc;
-    __syncthreads();
-    if (wave == 0 && t < T) dx[(size_t)b * T + t] += (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) * scal[1];
 }
 
 // d noise = d x_0 (the chain through the flows) + d_x scale_tot (x = noise scale_tot + mean_tot read the noise itself)
@@ -307,72 +273,39 @@ ItBwdLayout it_bwd_layout(const wn_handle* h, const ItLayout& TL, int B, bool wg
     return L;
 }
 
-// the gradient table: every variable of every flow in the order weights.py lists them
-std::vector<WnGradEntry> it_grad_table(const wn_handle* h) {
+// what the training calls refuse about the handle; quiet: no message (the size and table queries return 0)
+int it_check(const wn_handle* h, const char* fn, bool quiet = false) {
+#define IT_REFUSE(code, ...) return quiet ? code : wn_fail(h, code, __VA_ARGS__)
+    if (!h) IT_REFUSE(WN_EINVAL, "%s: null handle", fn);
     const wn_config& c = h->cfg;
-    const int W = c.width, H = W / 2, Cd = c.deconv_width;
-    std::vector<WnGradEntry> t;
-    size_t off = 0;
-    auto conv = [&](const std::string& scope, int K, int cin, int cout) {
-        t.push_back({scope + "/W", off, {1, K, cin, cout}, 4});
-        off += (size_t)K * cin * cout;
-        t.push_back({scope + "/biases", off, {cout, 0, 0, 0}, 1});
-        off += cout;
-    };
-    for (int k = 0; k < c.n_flows; ++k) {
-        const std::string p = "iaf_" + std::to_string(k + 1) + "/";
-        conv(p + "start_conv", 3, 1, W);
-        for (int i = 0; i < c.iaf_layers[k]; ++i) {
-            const std::string n = std::to_string(i + 1);
-            conv(p + "dilated_conv_" + n, 3, W, W);
-            conv(p + "mel_cond_" + n, 1, Cd, W);
-            conv(p + "res_" + n, 1, H, W);
-        }
-        conv(p + "out1", 1, W, W);
-        conv(p + "mel_cond_out1", 1, Cd, W);
-        conv(p + "out2_mean", 1, W, 1);
-        conv(p + "out2_scale", 1, W, 1);
-    }
-    return t;
-}
-
-// what the training calls accept, without a message (the size queries) ...
-bool it_supported(const wn_handle* h) {
-    return h && h->finalized && h->cfg.kind == WN_KIND_STUDENT && !h->cfg.use_mu_law && !h->cfg.use_weight_norm &&
-           h->iaf_train.ok;
-}
-bool it_shape_ok(const wn_handle* h, int B, int F, long long T) {
-    if (B < 1 || F < 1 || T < 1) return false;
-    const long long TE = (long long)F * h->frame_shift, md = 1ll << (h->cfg.num_stages - 1);
-    return T <= TE && T % md == 0 && TE <= WN_MAX_ROW_SAMPLES;
-}
-// ... and by name
-int it_check(wn_handle* h, const char* fn) {
-    if (!h) return wn_fail(nullptr, WN_EINVAL, "%s: null handle", fn);
-    const wn_config& c = h->cfg;
-    if (c.kind != WN_KIND_STUDENT) return wn_fail(h, WN_EINVAL, "%s: handle is not a ParallelWavenet student", fn);
+    if (c.kind != WN_KIND_STUDENT) IT_REFUSE(WN_EINVAL, "%s: handle is not a ParallelWavenet student", fn);
     if (c.use_mu_law)
-        return wn_fail(h, WN_EINVAL, "%s: mu-law student: mu-law students and teachers are not supported by the "
-                       "distillation losses", fn);
+        IT_REFUSE(WN_EINVAL, "%s: mu-law student: mu-law students and teachers are not supported by the "
+                  "distillation losses", fn);
     if (c.use_weight_norm)
-        return wn_fail(h, WN_EINVAL, "%s: weight-norm student: the gradients of W_V / W_g are not implemented", fn);
-    if (!h->finalized) return wn_fail(h, WN_ESTATE, "%s: call wn_finalize first", fn);
+        IT_REFUSE(WN_EINVAL, "%s: weight-norm student: the gradients of W_V / W_g are not implemented", fn);
+    if (!h->finalized) IT_REFUSE(WN_ESTATE, "%s: call wn_finalize first", fn);
     if (!h->iaf_train.ok)
-        return wn_fail(h, WN_EINVAL, "%s: width %d and deconv_width %d must be multiples of 64 for the GEMM kernels", fn,
-                       c.width, c.deconv_width);
+        IT_REFUSE(WN_EINVAL, "%s: width %d and deconv_width %d must be multiples of 64 for the GEMM kernels", fn,
+                  c.width, c.deconv_width);
     return WN_OK;
 }
-int it_shape_check(wn_handle* h, const char* fn, int B, int F, int64_t T) {
-    if (B < 1 || F < 1 || T < 1) return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
+// ... and about the shape
+int it_shape_check(const wn_handle* h, const char* fn, int B, int F, int64_t T, bool quiet = false) {
+    if (B < 1 || F < 1 || T < 1) IT_REFUSE(WN_EINVAL, "%s: bad argument", fn);
     const long long TE = (long long)F * h->frame_shift, md = 1ll << (h->cfg.num_stages - 1);
-    if (T > TE) return wn_fail(h, WN_EINVAL, "%s: %lld samples need more than %d mel frames "
-                               "(wavenet.py:79 assert cond_len >= x_len)", fn, (long long)T, F);
-    if (T % md) return wn_fail(h, WN_EINVAL, "%s: length %lld is not a multiple of the largest "
-                               "dilation %lld (masked.py:188)", fn, (long long)T, md);
-    if (TE > WN_MAX_ROW_SAMPLES) return wn_fail(h, WN_EINVAL, "%s: utterance too long (32-bit row offsets)", fn);
+    if (T > TE) IT_REFUSE(WN_EINVAL, "%s: %lld samples need more than %d mel frames "
+                          "(wavenet.py:79 assert cond_len >= x_len)", fn, (long long)T, F);
+    if (T % md) IT_REFUSE(WN_EINVAL, "%s: length %lld is not a multiple of the largest "
+                          "dilation %lld (masked.py:188)", fn, (long long)T, md);
+    if (TE > WN_MAX_ROW_SAMPLES) IT_REFUSE(WN_EINVAL, "%s: utterance too long (32-bit row offsets)", fn);
     return WN_OK;
+#undef IT_REFUSE
 }
-
+// both, quietly: what the size queries answer 0 for
+bool it_sized(const wn_handle* h, int B, int F, int64_t T) {
+    return !it_check(h, "", true) && !it_shape_check(h, "", B, F, T, true);
+}
 template <class T>
 T* at(void* base, size_t off) { return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + off); }
 }  // namespace
@@ -476,46 +409,80 @@ int wn_pack_iaf_train(wn_handle* h, std::vector<float>& blob) {
     return WN_OK;
 }
 
+// the parameter layout: every variable of every flow in the order weights.py lists them
+void wn_iaf_build_layout(wn_handle* h) {
+    const wn_config& c = h->cfg;
+    const int W = c.width, H = W / 2, Cd = c.deconv_width;
+    IafParamLayout L;
+    auto conv = [&](const std::string& scope, int K, int cin, int cout) {
+        return L.table.conv(scope, "/W", "/biases", K, cin, cout, cout);
+    };
+    for (int k = 0; k < c.n_flows; ++k) {
+        const std::string p = "iaf_" + std::to_string(k + 1) + "/";
+        IafFlowLayout f;
+        f.start = conv(p + "start_conv", 3, 1, W);
+        for (int i = 0; i < c.iaf_layers[k]; ++i) {
+            const std::string n = std::to_string(i + 1);
+            IafLayerOff o;
+            o.dil = conv(p + "dilated_conv_" + n, 3, W, W);
+            o.cond = conv(p + "mel_cond_" + n, 1, Cd, W);
+            o.res = conv(p + "res_" + n, 1, H, W);
+            f.layers.push_back(o);
+        }
+        f.out1 = conv(p + "out1", 1, W, W);
+        f.cond_out1 = conv(p + "mel_cond_out1", 1, Cd, W);
+        f.out2_mean = conv(p + "out2_mean", 1, W, 1);
+        f.out2_scale = conv(p + "out2_scale", 1, W, 1);
+        L.flows.push_back(f);
+    }
+    h->iaf_train.lay = std::move(L);
+}
+
 extern "C" size_t wn_iaf_train_tape_bytes(const wn_handle* h, int B, int F, int64_t T) {
-    if (!it_supported(h) || !it_shape_ok(h, B, F, T)) return 0;
+    if (!it_sized(h, B, F, T)) return 0;
     return it_layout(h, B, F, T).total;
 }
 
 extern "C" size_t wn_iaf_train_workspace_bytes(const wn_handle* h, int B, int F, int64_t T) {
-    if (!it_supported(h) || !it_shape_ok(h, B, F, T)) return 0;
+    if (!it_sized(h, B, F, T)) return 0;
     return it_fwd_layout(h, B, F, T).total;
 }
 
 extern "C" size_t wn_iaf_backward_weights_workspace_bytes(const wn_handle* h, int B, int F, int64_t T) {
-    if (!it_supported(h) || !it_shape_ok(h, B, F, T)) return 0;
+    if (!it_sized(h, B, F, T)) return 0;
     return it_bwd_layout(h, it_layout(h, B, F, T), B, true).total;
 }
 
 extern "C" size_t wn_iaf_backward_input_workspace_bytes(const wn_handle* h, int B, int F, int64_t T) {
-    if (!it_supported(h) || !it_shape_ok(h, B, F, T)) return 0;
+    if (!it_sized(h, B, F, T)) return 0;
     return it_bwd_layout(h, it_layout(h, B, F, T), B, false).total;
 }
 
 extern "C" int wn_iaf_grad_count(const wn_handle* h) {
-    if (!it_supported(h)) return 0;
-    return (int)it_grad_table(h).size();
+    if (it_check(h, "", true)) return 0;
+    return (int)h->iaf_train.lay.table.entries.size();
 }
 
 extern "C" int wn_iaf_grad_info(const wn_handle* h, int i, char* name, size_t name_cap, int64_t* offset, int64_t* shape4,
                                 int* ndim) {
-    if (!it_supported(h))
+    if (it_check(h, "", true))
         return wn_fail(h, WN_EINVAL, "wn_iaf_grad_info: needs a finalized student handle the training calls accept");
-    return wn_grad_info(h, "wn_iaf_grad_info", it_grad_table(h), i, name, name_cap, offset, shape4, ndim);
+    return wn_grad_info(h, "wn_iaf_grad_info", h->iaf_train.lay.table.entries, i, name, name_cap, offset, shape4, ndim);
 }
 
 extern "C" size_t wn_iaf_grad_floats(const wn_handle* h) {
-    if (!it_supported(h)) return 0;
-    return wn_grad_floats(it_grad_table(h));
+    if (it_check(h, "", true)) return 0;
+    return h->iaf_train.lay.table.floats;
 }
 
-// for wn_iaf_set_weights (wn_iaf_repack.hip): the layout of the flat parameter buffer and the refusals by name
-std::vector<WnGradEntry> wn_iaf_grad_table(const wn_handle* h) { return it_grad_table(h); }
+// for wn_iaf_set_weights (wn_iaf_repack.hip): the refusals by name
 int wn_iaf_train_check(wn_handle* h, const char* fn) { return it_check(h, fn); }
+// it_denc_kernel for both reverse passes (the teacher's stores: add == 0)
+void wn_tw_denc(const unsigned* g4, const float* scal, float* out, int B, long long TE, long long RE, int Cd, int add,
+                hipStream_t st) {
+    hipLaunchKernelGGL(it_denc_kernel, dim3((unsigned)((TE + 255) / 256), Cd / 8, B), dim3(256), 0, st, g4, scal, out, TE, RE, Cd,
+                       add);
+}
 
 extern "C" int wn_iaf_forward_train_tape(wn_handle* h, const float* noise, const float* mel, int B, int F, int64_t T, float* x,
                                          float* mean_tot, float* scale_tot, void* tape, size_t tape_bytes, void* ws,
@@ -638,9 +605,9 @@ int it_tape_check(wn_handle* h, const char* fn, const void* tape, size_t tape_by
 // operands -- the data path alone, as tb_reverse without wg); d_noise: null, or the chain is carried through flow 1's start
 // conv and the noise's own term added.  What both leave out changes no bit of what remains.
 // These are the launches alone: the caller has checked everything (it_reverse, wn_iaf_adjoint) and holds the work lock.
-int it_reverse_run(wn_handle* h, const char* fn, const void* tape, const ItLayout& TL, const ItBwdLayout& BL,
-                   const std::vector<WnGradEntry>& tab, const float* d_x, const float* d_mean_tot, const float* d_scale_tot, int B,
-                   int64_t T, float* grads, float* d_noise, float* d_encoding, void* ws, void* stream) {
+int it_reverse_run(wn_handle* h, const char* fn, const void* tape, const ItLayout& TL, const ItBwdLayout& BL, const float* d_x,
+                   const float* d_mean_tot, const float* d_scale_tot, int B, int64_t T, float* grads, float* d_noise,
+                   float* d_encoding, void* ws, void* stream) {
     const bool wg = grads != nullptr;
     const IafTrainPack& P = h->iaf_train;
     const wn_config& c = h->cfg;
@@ -676,7 +643,7 @@ int it_reverse_run(wn_handle* h, const char* fn, const void* tape, const ItLayou
     for (int k = NF; k-- > 0;) {
         const IafTrainFlow& fl = P.flows[k];
         const ItFlowOff& fo = TL.f[k];
-        const std::string p = "iaf_" + std::to_string(k + 1) + "/";
+        const IafFlowLayout& lay = P.lay.flows[k];
         const unsigned* enc = at<unsigned>(tp, TL.enc + fl.deconv_stack * TL.enc_bytes);
         const float* xs = at<float>(tp, fo.xs);
         auto slot = [&](size_t i) { return at<unsigned>(tp, TL.l + (fo.slot0 + i) * TL.slot_bytes); };
@@ -707,14 +674,14 @@ int it_reverse_run(wn_handle* h, const char* fn, const void* tape, const ItLayou
             const long long o1w = b.add(dh1, W, Tp, rl, W, Tp, 0);
             const long long c1w = b.add(dh1, W, Tp, enc, Cd, TL.TE, TL.c0);
             const long long o1b = b.add(dh1, W, Tp, aux, TW_AUXC, Tp, 0);
-            b.red(o2w, W, 1, Kp, wn_grad_off(tab, p + "out2_mean/W"), 1);
-            b.red(o2w + 1, W, 1, Kp, wn_grad_off(tab, p + "out2_scale/W"), 1);
-            b.red(o2b + 3 * Kp, 1, 1, Kp, wn_grad_off(tab, p + "out2_mean/biases"), 1);
-            b.red(o2b + 3 * Kp + 1, 1, 1, Kp, wn_grad_off(tab, p + "out2_scale/biases"), 1);
-            b.red(o1w, W, W, W, wn_grad_off(tab, p + "out1/W"), W);
-            b.red(c1w, Cd, W, W, wn_grad_off(tab, p + "mel_cond_out1/W"), W);
-            b.red(o1b + 3 * W, 1, W, W, wn_grad_off(tab, p + "out1/biases"), W);
-            b.red(o1b + 3 * W, 1, W, W, wn_grad_off(tab, p + "mel_cond_out1/biases"), W);
+            b.red(o2w, W, 1, Kp, lay.out2_mean.W, 1);
+            b.red(o2w + 1, W, 1, Kp, lay.out2_scale.W, 1);
+            b.red(o2b + 3 * Kp, 1, 1, Kp, lay.out2_mean.b, 1);
+            b.red(o2b + 3 * Kp + 1, 1, 1, Kp, lay.out2_scale.b, 1);
+            b.red(o1w, W, W, W, lay.out1.W, W);
+            b.red(c1w, Cd, W, W, lay.cond_out1.W, W);
+            b.red(o1b + 3 * W, 1, W, W, lay.out1.b, W);
+            b.red(o1b + 3 * W, 1, W, W, lay.cond_out1.b, W);
             if (int rc = b.run(h, run, st)) return rc;
         }
         if (d_encoding) denc_gemm(fl.cond_out1_t, dh1, W, Tp);
@@ -726,7 +693,7 @@ int it_reverse_run(wn_handle* h, const char* fn, const void* tape, const ItLayou
         }
         for (size_t li = fl.layers.size(); li-- > 0;) {
             const IafTrainLayer& tl = fl.layers[li];
-            const std::string n = std::to_string(li + 1);
+            const IafLayerOff& lo = lay.layers[li];
             const float* gt = at<float>(tp, fo.g) + li * (size_t)B * W * Tp;
             {   // dm = W_res^T dl -> dd through the gate derivative
                 TgArgs a = args(tl.res_t, dd, RD, 0, W);
@@ -745,13 +712,12 @@ int it_reverse_run(wn_handle* h, const char* fn, const void* tape, const ItLayou
                     dw[tap] = b.add(dd, W, RD, slot(li), W, RS, IAF_LP - (long long)(2 - tap) * tl.dilation);
                 const long long cw = b.add(dd, W, RD, enc, Cd, TL.TE, TL.c0);
                 const long long db = b.add(dd, W, RD, aux, TW_AUXC, Tp, 0);
-                b.red(rw, H, W, W, wn_grad_off(tab, p + "res_" + n + "/W"), W);
-                b.red(rb + 3 * W, 1, W, W, wn_grad_off(tab, p + "res_" + n + "/biases"), W);
-                for (int tap = 0; tap < 3; ++tap)
-                    b.red(dw[tap], W, W, W, wn_grad_off(tab, p + "dilated_conv_" + n + "/W") + (size_t)tap * W * W, W);
-                b.red(cw, Cd, W, W, wn_grad_off(tab, p + "mel_cond_" + n + "/W"), W);
-                b.red(db + 3 * W, 1, W, W, wn_grad_off(tab, p + "dilated_conv_" + n + "/biases"), W);
-                b.red(db + 3 * W, 1, W, W, wn_grad_off(tab, p + "mel_cond_" + n + "/biases"), W);
+                b.red(rw, H, W, W, lo.res.W, W);
+                b.red(rb + 3 * W, 1, W, W, lo.res.b, W);
+                for (int tap = 0; tap < 3; ++tap) b.red(dw[tap], W, W, W, lo.dil.W + (size_t)tap * W * W, W);
+                b.red(cw, Cd, W, W, lo.cond.W, W);
+                b.red(db + 3 * W, 1, W, W, lo.dil.b, W);
+                b.red(db + 3 * W, 1, W, W, lo.cond.b, W);
                 if (int rc = b.run(h, run, st)) return rc;
             }
             if (d_encoding) denc_gemm(tl.cond_t, dd, W, RD);
@@ -766,18 +732,16 @@ int it_reverse_run(wn_handle* h, const char* fn, const void* tape, const ItLayou
         if (wg) {   // dl = d l_0: the start conv's variables, and its transpose into d x_{k-1}
             TwBatch b;
             const long long cs = b.add(dl, W, Tp, aux, TW_AUXC, Tp, 0);
-            b.red(cs, 3, W, W, wn_grad_off(tab, p + "start_conv/W"), W);
-            b.red(cs + 3 * W, 1, W, W, wn_grad_off(tab, p + "start_conv/biases"), W);
+            b.red(cs, 3, W, W, lay.start.W, W);
+            b.red(cs + 3 * W, 1, W, W, lay.start.b, W);
             if (int rc = b.run(h, run, st)) return rc;
         }
         if (k > 0 || d_noise)   // flow 1's input is the noise
-            hipLaunchKernelGGL(it_dx_kernel, dim3((unsigned)((T + 63) / 64), B), dim3(256), 0, st, dl, h->d_blob + fl.start_off, scal,
-                               dx, W, (long long)T, Tp);
+            wn_tb_dx(dl, h->d_blob + fl.start_off, scal, dx, B, W, T, Tp, true, st);
         if (d_encoding) {
             // flows that share a stack accumulate into its slice: the last flow stores, the ones before it add
             const int add = c.share_deconv && k + 1 < NF;
-            hipLaunchKernelGGL(it_denc_kernel, dim3((unsigned)((TL.TE + 255) / 256), Cd / 8, B), dim3(256), 0, st, denc, scal,
-                               d_encoding + (size_t)fl.deconv_stack * B * TL.TE * Cd, TL.TE, RE, Cd, add);
+            wn_tw_denc(denc, scal, d_encoding + (size_t)fl.deconv_stack * B * TL.TE * Cd, B, TL.TE, RE, Cd, add, st);
         }
     }
     if (d_noise) {
@@ -799,14 +763,14 @@ int it_reverse(wn_handle* h, const char* fn, const void* tape, size_t tape_bytes
         return wn_fail(h, WN_EINVAL, "%s: bad argument", fn);
     const ItLayout TL = it_layout(h, B, F, T);
     if (int rc = it_tape_check(h, fn, tape, tape_bytes, TL, B, F, T)) return rc;
-    const std::vector<WnGradEntry> tab = wg ? it_grad_table(h) : std::vector<WnGradEntry>();
-    if (wg && grads_floats < wn_grad_floats(tab))
-        return wn_fail(h, WN_ENOMEM, "%s: grads holds %zu floats, the gradients need %zu", fn, grads_floats, wn_grad_floats(tab));
+    if (wg && grads_floats < h->iaf_train.lay.table.floats)
+        return wn_fail(h, WN_ENOMEM, "%s: grads holds %zu floats, the gradients need %zu", fn, grads_floats,
+                       h->iaf_train.lay.table.floats);
     const ItBwdLayout BL = it_bwd_layout(h, TL, B, wg);
     if (wg && (long long)B * BL.nchunk > 65535) return wn_fail(h, WN_EINVAL, "%s: B = %d needs more than 65535 slabs", fn, B);
     if (ws_bytes < BL.total) return wn_fail(h, WN_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, BL.total);
     const WnWork work(h);
-    return it_reverse_run(h, fn, tape, TL, BL, tab, d_x, d_mean_tot, d_scale_tot, B, T, grads, d_noise, d_encoding, ws, stream);
+    return it_reverse_run(h, fn, tape, TL, BL, d_x, d_mean_tot, d_scale_tot, B, T, grads, d_noise, d_encoding, ws, stream);
 }
 }  // namespace
 
@@ -824,8 +788,8 @@ const float* wn_iaf_tape_scale_prod(const wn_handle* h, const void* tape, int B,
 int wn_iaf_reverse_input_run(wn_handle* h, const char* fn, const void* tape, const float* d_x, const float* d_mean_tot,
                              const float* d_scale_tot, int B, int F, int64_t T, float* d_noise, void* ws, void* stream) {
     const ItLayout TL = it_layout(h, B, F, T);
-    return it_reverse_run(h, fn, tape, TL, it_bwd_layout(h, TL, B, false), std::vector<WnGradEntry>(), d_x, d_mean_tot, d_scale_tot,
-                          B, T, nullptr, d_noise, nullptr, ws, stream);
+    return it_reverse_run(h, fn, tape, TL, it_bwd_layout(h, TL, B, false), d_x, d_mean_tot, d_scale_tot, B, T, nullptr, d_noise,
+                          nullptr, ws, stream);
 }
 
 extern "C" int wn_iaf_backward_weights(wn_handle* h, const void* tape, size_t tape_bytes, const float* d_x,

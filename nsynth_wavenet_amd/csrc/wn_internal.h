@@ -26,6 +26,31 @@ struct HostTensor {
     bool set = false;
 };
 
+// ---- parameter layouts: the variables of one flat float32 parameter / gradient buffer.  Each is a function of the
+// configuration alone, built once at the end of wn_finalize (wn_*_build_layout) and read-only from then on: the re-packs
+// change values, never offsets.  The typed members and the named table come out of one walk. ----
+struct WnGradEntry {
+    std::string name;      // the TF variable
+    size_t off;            // first float inside the buffer
+    int64_t shape[4];      // the TF shape, ndim entries
+    int ndim;
+};
+struct WnConvOff {
+    size_t W, b;           // float offsets of <scope>/W and <scope>/biases (deconv stack: /kernel and /bias)
+};
+struct WnGradTable {
+    std::vector<WnGradEntry> entries;   // in the order weights.py lists the variables
+    size_t floats = 0;                  // the entries are contiguous from 0
+    // appends <scope>/<wname> [1][K][d2][d3] and <scope>/<bname> [cout]
+    WnConvOff conv(const std::string& scope, const char* wname, const char* bname, int K, int d2, int d3, int cout) {
+        WnConvOff o{floats, floats + (size_t)K * d2 * d3};
+        entries.push_back({scope + wname, o.W, {1, K, d2, d3}, 4});
+        entries.push_back({scope + bname, o.b, {cout, 0, 0, 0}, 1});
+        floats = o.b + (size_t)cout;
+        return o;
+    }
+};
+
 // ---- device-side parameter blocks (offsets in floats into wn_handle::d_blob) ----
 
 // One transposed-conv layer packed for the MFMA kernel (wn_deconv.hip).
@@ -57,6 +82,8 @@ struct DeconvLayerPack {
 struct DeconvStackPack {
     std::string prefix;                // "", "iaf_share", "iaf_k"
     std::vector<DeconvLayerPack> layers;
+    std::vector<WnConvOff> lay;        // parameter layout (wn_deconv_build_layout): trans_conv_j/kernel, /bias per layer
+    WnGradTable table;
 };
 
 // launch group of wn_iaf_g.hip
@@ -137,7 +164,16 @@ struct TeacherLayerPack {
     TeacherGemmPack cond_t;         // d enc (wn_teacher_backward_weights): mel_cond_i transposed, [deconv_width][gate]
     int dilation;
 };
+struct TeacherLayerOff {
+    WnConvOff dil, cond, res, skip;
+};
+struct TeacherParamLayout {                  // wn_teacher_build_layout (wn_teacher_wgrad.hip): residual stack and head
+    WnConvOff start, skip_start, out1, cond_out1, out2;
+    std::vector<TeacherLayerOff> layers;
+    WnGradTable table;
+};
 struct TeacherPack {
+    TeacherParamLayout lay;
     TeacherGemmPack skip_start, out1, out2;
     TeacherGemmPack skip_start_t, out1_t, out2_t;   // transposes: [width][skip], [skip][skip], [skip][out_width padded to 32]
     std::vector<TeacherLayerPack> layers;
@@ -163,7 +199,19 @@ struct IafTrainFlow {
     TeacherGemmPack cond_out1_t;          // [deconv_width][width]
     int deconv_stack;
 };
+struct IafLayerOff {
+    WnConvOff dil, cond, res;
+};
+struct IafFlowLayout {
+    WnConvOff start, out1, cond_out1, out2_mean, out2_scale;
+    std::vector<IafLayerOff> layers;
+};
+struct IafParamLayout {                        // wn_iaf_build_layout (wn_iaf_train.hip): every flow of a student
+    std::vector<IafFlowLayout> flows;
+    WnGradTable table;
+};
 struct IafTrainPack {
+    IafParamLayout lay;
     std::vector<IafTrainFlow> flows;
     bool ok = false;                      // the model is one the training calls accept: the packs exist
     uint64_t serial = 0;                  // identity of the handle in the tapes it writes
@@ -253,20 +301,9 @@ struct WnWork {
                            hipGetErrorString(e__), __FILE__, __LINE__);              \
     } while (0)
 
-// ---- gradient tables (wn_teacher_wgrad.hip, wn_deconv_bwd.hip): the variables of one flat float32 gradient buffer ----
-struct WnGradEntry {
-    std::string name;      // the TF variable
-    size_t off;            // first float inside the buffer
-    int64_t shape[4];      // the TF shape, ndim entries
-    int ndim;
-};
-// floats of the buffer: the entries are contiguous and the last one is a bias [shape[0]]
-inline size_t wn_grad_floats(const std::vector<WnGradEntry>& t) { return t.empty() ? 0 : t.back().off + (size_t)t.back().shape[0]; }
+// ---- gradient tables: the query calls' view of the layouts above ----
+int wn_iaf_train_check(wn_handle* h, const char* fn);                       // what the student's training calls refuse, by name
 // entry i for the *_grad_info calls (message prefix fn); refuses a bad index, a null output or a short name buffer
-std::vector<WnGradEntry> wn_teacher_grad_table(const wn_handle* h);        // wn_teacher_wgrad.hip: residual stack and head
-std::vector<WnGradEntry> wn_deconv_grad_table(const wn_handle* h, int si);   // wn_deconv_bwd.hip: stack si
-std::vector<WnGradEntry> wn_iaf_grad_table(const wn_handle* h);            // wn_iaf_train.hip: every flow of a student
-int wn_iaf_train_check(wn_handle* h, const char* fn);                       // ... and what its training calls refuse, by name
 int wn_grad_info(const wn_handle* h, const char* fn, const std::vector<WnGradEntry>& t, int i, char* name, size_t name_cap,
                  int64_t* offset, int64_t* shape4, int* ndim);
 // wn_iaf_train.hip for wn_iaf_adjoint (wn_iaf_nll.hip): the refusals of a reverse pass under the caller's name (handle and
@@ -315,6 +352,10 @@ int wn_pack_iaf(wn_handle* h, std::vector<float>& blob);
 int wn_pack_ar(wn_handle* h, std::vector<float>& blob);
 int wn_pack_teacher(wn_handle* h, std::vector<float>& blob);   // after wn_pack_ar (reuses its matrices)
 int wn_pack_iaf_train(wn_handle* h, std::vector<float>& blob);  // students the training calls accept (wn_iaf_train.hip)
+// the parameter layouts, after every pack (wn_teacher_wgrad.hip, wn_iaf_train.hip, wn_deconv_bwd.hip)
+void wn_teacher_build_layout(wn_handle* h);
+void wn_iaf_build_layout(wn_handle* h);
+void wn_deconv_build_layout(wn_handle* h);
 
 // What one wn_run_deconv call launches and where every layer's rows sit (dc_plan, wn_deconv.hip).  Fixed size, no heap: it
 // is filled inside every generate call.  Offsets are floats from the start of the scratch area.

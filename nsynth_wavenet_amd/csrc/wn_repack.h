@@ -128,15 +128,12 @@ __device__ inline void tr_tile_word(const TileArgs& a, size_t i) {
     a.dst[i] = (uint32_t)hh[0] | ((uint32_t)hh[1] << 16);
 }
 
-// ---- the upsampler's stack (wn_train.hip): what both calls run for one stack whose variables `up` hold, in the layout UT of
-// wn_deconv_grad_table.  amax / mx: one slot per layer.
+// ---- the upsampler's stack (wn_train.hip): what both calls run for one stack whose variables `up` hold, in the stack's own
+// layout (sp.lay).  amax / mx: one slot per layer.
 // the absolute maxima of the kernels, reduced into amax[j] (zeroed by the caller)
-void wn_repack_deconv_absmax(const DeconvStackPack& sp, const std::vector<WnGradEntry>& UT, const float* up, unsigned* amax,
-                             hipStream_t st);
+void wn_repack_deconv_absmax(const DeconvStackPack& sp, const float* up, unsigned* amax, hipStream_t st);
 // the fp32 fragments and the bias
-void wn_repack_deconv_plain(wn_handle* h, const DeconvStackPack& sp, const std::vector<WnGradEntry>& UT, const float* up,
-                            hipStream_t st);
+void wn_repack_deconv_plain(wn_handle* h, const DeconvStackPack& sp, const float* up, hipStream_t st);
 // the split-fp16, phase-group and transposed packs under pick_scale(mx[j]), and their scales in the host structs
-void wn_repack_deconv_split(wn_handle* h, DeconvStackPack& sp, const std::vector<WnGradEntry>& UT, const float* up, const float* mx,
-                            hipStream_t st);
+void wn_repack_deconv_split(wn_handle* h, DeconvStackPack& sp, const float* up, const float* mx, hipStream_t st);
 uint64_t wn_repack_serial_next();   // tape serials of re-packed handles: apart from wn_finalize's counter

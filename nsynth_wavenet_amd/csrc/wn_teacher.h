@@ -192,6 +192,9 @@ bool wn_tape_lookup(const void* tape, uint64_t* serial, int* B, long long* T, in
 // d out [B,T,ow] times scal[0] -> G4 rows of Kp channels, zero beyond ow and from column T on
 void wn_tb_dout(const float* dout, const float* scal, unsigned* g4, int B, long long T, long long Tp, int ow, int Kp,
                 hipStream_t st);
+// a start conv transposed (wb: w[3][W] | b[W]): dl0 G4 rows [B][W][Tp] times scal[1] -> dx [B][T], stored, or with `add` added
+void wn_tb_dx(const unsigned* dl, const float* wb, const float* scal, float* dx, int B, int W, long long T, long long Tp, bool add,
+              hipStream_t st);
 // what the VJP-side calls refuse (the distillation losses' own refusals, wn_distill.hip)
 int tb_check(wn_handle* h, const char* fn);
 // registry check shared by the reverse-pass calls; *F receives the frame count of a training tape (0: a plain tape)
@@ -265,14 +268,13 @@ inline void tw_chunks(int B, long long Tp, long long T, int* chunk, int* nchunk)
     *chunk = (int)((ntiles + want - 1) / want) * TG_TN;
     *nchunk = (int)((T + *chunk - 1) / *chunk);
 }
-constexpr size_t GRAD_NONE = ~(size_t)0;
 struct TwBatch {
     TwArgs a{};
     TwRedArgs r{};
     int nop = 0, nred = 0;
     long long used = 0;
     int max_tiles = 0;
-    bool bad = false;               // a table overflow or an unknown gradient name: nothing was written, run() refuses
+    bool bad = false;               // a table overflow: nothing was written, run() refuses
     // dY (M channels, rows of rowlen) x X (N channels): returns the slab offset of the [N][M] product
     long long add(const unsigned* dy, int M, long long dy_rowlen, const unsigned* x, int N, long long x_rowlen, long long x_col0) {
         if (nop >= TW_MAXOP) { bad = true; return 0; }
@@ -285,22 +287,20 @@ struct TwBatch {
         return o.out_off;
     }
     void red(long long src_off, int rows, int cols, int src_ld, size_t dst_off, int dst_ld) {
-        if (nred >= TW_MAXRED || dst_off == GRAD_NONE) { bad = true; return; }
+        if (nred >= TW_MAXRED) { bad = true; return; }
         TwRed& q = r.r[nred++];
         q.src_off = src_off; q.dst_off = (long long)dst_off; q.rows = rows; q.cols = cols; q.src_ld = src_ld; q.dst_ld = dst_ld;
     }
     int run(wn_handle* h, const TwRun& w, hipStream_t st);      // wn_teacher_wgrad.hip: the two launches
 };
-inline size_t wn_grad_off(const std::vector<WnGradEntry>& t, const std::string& name) {
-    for (const WnGradEntry& e : t)
-        if (e.name == name) return e.off;
-    return GRAD_NONE;       // an unknown name: TwBatch::red records it and run() refuses to launch
-}
 // accumulator-layout tape rows -> G4 activation rows of C channels, zero from column T on (mode 0: relu(src); 1: sigma * tanh
 // of a gate tape), and the aux rows [B][TW_AUXC][Tp] of an input row xs
 void wn_tw_act(const float* src, long long src_bs, int nmb, int hoff, unsigned* g4, int B, long long T, long long Tp, int C,
                int mode, hipStream_t st);
 void wn_tw_aux(const float* xs, unsigned* g4, int B, long long T, long long Tp, hipStream_t st);
+// d enc (wn_iaf_train.hip): G4 rows [B][Cd][RE] times scal[1] -> float32 [B][TE][Cd], stored, or with `add` added
+void wn_tw_denc(const unsigned* g4, const float* scal, float* out, int B, long long TE, long long RE, int Cd, int add,
+                hipStream_t st);
 
 // ---- wn_teacher_dropout.hip: the mask kernels ----
 uint32_t wn_dropout_threshold(double rate);     // min(2^32 - 1, floor(rate 2^32 + 0.5))

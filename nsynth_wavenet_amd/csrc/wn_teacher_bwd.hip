@@ -56,11 +56,13 @@ __global__ __launch_bounds__(256) void tb_dout_kernel(const float* __restrict__ 
     wn_g4_store(g4 + (size_t)b * Kp * Tp, NG, Tp, gr, c, hw, lw);
 }
 
-// conv_start transposed (tg_start_kernel: l0(t) = b + w0 x(t-3) + w1 x(t-2) + w2 x(t-1)):
-// d wav(t) = scal[1] sum_c (w0[c] dl0[c](t+3) + w1[c] dl0[c](t+2) + w2[c] dl0[c](t+1)); 64 columns x 4 waves of channels
+// a start conv transposed (tg_start_kernel: l0(t) = b + w0 x(t-3) + w1 x(t-2) + w2 x(t-1)):
+// dx(t) = scal[1] sum_c (w0[c] dl0[c](t+3) + w1[c] dl0[c](t+2) + w2[c] dl0[c](t+1)); 64 columns x 4 waves of channels.
+// ADD: added to dx (the student's running d x) instead of stored (the teacher's d wav)
+template <bool ADD>
 __global__ __launch_bounds__(256) void tb_dx_kernel(const unsigned* __restrict__ dl, const float* __restrict__ wb,
-                                                    const float* __restrict__ scal, float* __restrict__ dwav, int W,
-                                                    long long T, long long Tp) {
+                                                    const float* __restrict__ scal, float* __restrict__ dx, int W, long long T,
+                                                    long long Tp) {
     __shared__ float red[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.y, NG = W / 8;
     const long long t = (long long)blockIdx.x * 64 + lane;
@@ -86,7 +88,10 @@ __global__ __launch_bounds__(256) void tb_dx_kernel(const unsigned* __restrict__
     }
     red[wave][lane] = acc;
     __syncthreads();
-    if (wave == 0 && t < T) dwav[(size_t)b * T + t] = (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) * scal[1];
+    if (wave == 0 && t < T) {       // both forms as one expression: the sum's product with scal[1] contracts into the add
+        if (ADD) dx[(size_t)b * T + t] += (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) * scal[1];
+        else dx[(size_t)b * T + t] = (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) * scal[1];
+    }
 }
 }  // namespace
 
@@ -105,6 +110,12 @@ void wn_tb_dout(const float* dout, const float* scal, unsigned* g4, int B, long 
                 hipStream_t st) {
     hipLaunchKernelGGL(tb_dout_kernel, dim3((unsigned)((Tp + 255) / 256), Kp / 8, B), dim3(256), 0, st, dout, scal, g4, T, Tp,
                        ow, Kp);
+}
+void wn_tb_dx(const unsigned* dl, const float* wb, const float* scal, float* dx, int B, int W, long long T, long long Tp, bool add,
+              hipStream_t st) {
+    const dim3 grid((unsigned)((T + 63) / 64), B);
+    if (add) hipLaunchKernelGGL(tb_dx_kernel<true>, grid, dim3(256), 0, st, dl, wb, scal, dx, W, T, Tp);
+    else hipLaunchKernelGGL(tb_dx_kernel<false>, grid, dim3(256), 0, st, dl, wb, scal, dx, W, T, Tp);
 }
 
 BLayout b_layout(const wn_handle* h, int B, long long T) {
@@ -277,9 +288,7 @@ int tb_reverse(wn_handle* h, const void* tape, const float* d_out_params, int B,
     if (drop_all) wn_dropout_g4(w.dl, w.dl, B, W, Tp, 0, T, dr, 0, st);         // skip_start read the masked l_0
     if (wg)
         if (int rc = tw_tail(h, *wg, st)) return rc;
-    if (d_wav)
-        hipLaunchKernelGGL(tb_dx_kernel, dim3((unsigned)((T + 63) / 64), B), dim3(256), 0, st, w.dl,
-                           h->d_blob + h->ar.start_off, w.scal, d_wav, W, (long long)T, Tp);
+    if (d_wav) wn_tb_dx(w.dl, h->d_blob + h->ar.start_off, w.scal, d_wav, B, W, T, Tp, false, st);
     WN_HIP(h, hipGetLastError());
     return WN_OK;
 }

@@ -182,25 +182,6 @@ __global__ __launch_bounds__(256) void tw_aux_kernel(const float* __restrict__ x
     wn_g4_store(g4 + (size_t)b * TW_AUXC * Tp, NG, Tp, gr, t, hw, lw);
 }
 
-// d enc: G4 rows [B][Cd][RE] (scaled) -> float32 [B][TE][Cd]
-__global__ __launch_bounds__(256) void tw_denc_kernel(const unsigned* __restrict__ g4, const float* __restrict__ scal,
-                                                      float* __restrict__ out, long long TE, long long RE, int Cd) {
-    const int b = blockIdx.z, gr = blockIdx.y, NG = Cd / 8;
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= TE) return;
-    wn_u4 hw, lw;
-    wn_g4_load(g4 + (size_t)b * Cd * RE, NG, RE, gr, t, hw, lw);
-    const float sc = scal[1];
-    float* o = out + ((size_t)b * TE + t) * Cd;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float v0, v1;
-        wn_join_pair(hw[i], lw[i], v0, v1);
-        const int ch = wn_g4_channel(gr, i);
-        o[ch] = v0 * sc;
-        o[ch + 1] = v1 * sc;
-    }
-}
 }  // namespace
 
 struct TrainLayout {
@@ -266,39 +247,35 @@ static WLayout w_layout(const wn_handle* h, int B, int F, long long T) {
 }
 
 // the gradients in one flat float32 buffer: the variables of the residual stack and head in the order weights.py lists them
-static std::vector<WnGradEntry> grad_table(const wn_handle* h) {
+void wn_teacher_build_layout(wn_handle* h) {
     const wn_config& c = h->cfg;
     const int W = c.width, S = c.skip_width, G = c.gate_width, H = G / 2, Cd = c.deconv_width, OW = c.out_width;
-    std::vector<WnGradEntry> t;
-    size_t off = 0;
+    TeacherParamLayout L;
     auto conv = [&](const std::string& scope, int K, int cin, int cout) {
-        t.push_back({scope + "/W", off, {1, K, cin, cout}, 4});
-        off += (size_t)K * cin * cout;
-        t.push_back({scope + "/biases", off, {cout, 0, 0, 0}, 1});
-        off += cout;
+        return L.table.conv(scope, "/W", "/biases", K, cin, cout, cout);
     };
-    conv("conv_start", 3, 1, W);
-    conv("skip_start", 1, W, S);
+    L.start = conv("conv_start", 3, 1, W);
+    L.skip_start = conv("skip_start", 1, W, S);
     for (size_t i = 0; i < h->teacher.layers.size(); ++i) {
         const std::string n = std::to_string(i + 1);
-        conv("dilated_conv_" + n, 3, W, G);
-        conv("mel_cond_" + n, 1, Cd, G);
-        conv("res_" + n, 1, H, W);
-        conv("skip_" + n, 1, H, S);
+        TeacherLayerOff o;
+        o.dil = conv("dilated_conv_" + n, 3, W, G);
+        o.cond = conv("mel_cond_" + n, 1, Cd, G);
+        o.res = conv("res_" + n, 1, H, W);
+        o.skip = conv("skip_" + n, 1, H, S);
+        L.layers.push_back(o);
     }
-    conv("out1", 1, S, S);
-    conv("mel_cond_out1", 1, Cd, S);
-    conv("out2", 1, S, OW);
-    return t;
+    L.out1 = conv("out1", 1, S, S);
+    L.cond_out1 = conv("mel_cond_out1", 1, Cd, S);
+    L.out2 = conv("out2", 1, S, OW);
+    h->teacher.lay = std::move(L);
 }
-static size_t grad_off(const std::vector<WnGradEntry>& t, const std::string& name) { return wn_grad_off(t, name); }
 
 struct TwCtx {
     int B;
     long long T;
     WLayout L;
     TrainLayout TR;
-    std::vector<WnGradEntry> tab;
     TbWork rw;                      // workspace of the reverse pass: the cotangents
     unsigned *aux, *xa, *xb, *denc; // workspace of the weight side
     float* slab;
@@ -313,8 +290,7 @@ struct TwCtx {
 
 // one batch of products and the reduction of their slabs
 int TwBatch::run(wn_handle* h, const TwRun& w, hipStream_t st) {
-    if (bad || used > (long long)w.slab_floats)
-        return wn_fail(h, WN_EIO, "%s: internal product table overflow or unknown gradient name", w.fn);
+    if (bad || used > (long long)w.slab_floats) return wn_fail(h, WN_EIO, "%s: internal product table overflow", w.fn);
     a.slab = w.slab; a.slab_stride = (long long)w.slab_floats; a.T = w.T; a.nchunk = w.nchunk; a.chunk = w.chunk;
     hipLaunchKernelGGL(tw_gemm_kernel, dim3(max_tiles, nop, w.B * w.nchunk), dim3(256), 0, st, a);
     r.slab = w.slab; r.slab_stride = a.slab_stride; r.nslab = w.B * w.nchunk; r.scal = w.scal; r.grads = w.grads;
@@ -370,12 +346,13 @@ int tw_head(wn_handle* h, const TwCtx& w, hipStream_t st, int stage) {
     const long long o1w = k.add(w.rw.dh1, S, Tp, w.xb, S, Tp, 0);
     const long long c1w = k.add(w.rw.dh1, S, Tp, w.enc(), Cd, w.L.TE, w.L.c0);
     const long long o1b = k.add(w.rw.dh1, S, Tp, w.aux, TW_AUXC, Tp, 0);
-    k.red(o2w, S, OW, Kp, grad_off(w.tab, "out2/W"), OW);
-    k.red(o2b + 3 * Kp, 1, OW, Kp, grad_off(w.tab, "out2/biases"), OW);
-    k.red(o1w, S, S, S, grad_off(w.tab, "out1/W"), S);
-    k.red(c1w, Cd, S, S, grad_off(w.tab, "mel_cond_out1/W"), S);
-    k.red(o1b + 3 * S, 1, S, S, grad_off(w.tab, "out1/biases"), S);
-    k.red(o1b + 3 * S, 1, S, S, grad_off(w.tab, "mel_cond_out1/biases"), S);
+    const TeacherParamLayout& lay = h->teacher.lay;
+    k.red(o2w, S, OW, Kp, lay.out2.W, OW);
+    k.red(o2b + 3 * Kp, 1, OW, Kp, lay.out2.b, OW);
+    k.red(o1w, S, S, S, lay.out1.W, S);
+    k.red(c1w, Cd, S, S, lay.cond_out1.W, S);
+    k.red(o1b + 3 * S, 1, S, S, lay.out1.b, S);
+    k.red(o1b + 3 * S, 1, S, S, lay.cond_out1.b, S);
     if (int rc = k.run(h, w.run(), st)) return rc;
     if (w.want_denc) tw_denc_gemm(h, w, h->teacher.cond_out1_t, w.rw.dh1, S, Tp, st);
     return WN_OK;
@@ -386,7 +363,7 @@ int tw_layer(wn_handle* h, const TwCtx& w, size_t li, hipStream_t st) {
     const int W = c.width, S = c.skip_width, G = c.gate_width, H = G / 2, Cd = c.deconv_width;
     const long long Tp = w.L.Tp, RS = w.TR.RS;
     const TeacherLayerPack& tl = h->teacher.layers[li];
-    const std::string n = std::to_string(li + 1);
+    const TeacherLayerOff& lo = h->teacher.lay.layers[li];
     // m_i = sigma * tanh of the gate tape
     hipLaunchKernelGGL(tw_act_kernel, dim3((unsigned)(Tp / 256), H / 8, w.B), dim3(256), 0, st,
                        w.tp.g + li * (size_t)w.B * G * Tp, (long long)G * Tp, G / 16, H / 16, w.xa, w.T, Tp, H, 1);
@@ -400,15 +377,14 @@ int tw_layer(wn_handle* h, const TwCtx& w, size_t li, hipStream_t st) {
     for (int tap = 0; tap < 3; ++tap) dw[tap] = k.add(w.rw.dd, G, w.rw.RD, l, W, RS, IAF_LP - (long long)(2 - tap) * tl.dilation);
     const long long cw = k.add(w.rw.dd, G, w.rw.RD, w.enc(), Cd, w.L.TE, w.L.c0);
     const long long db = k.add(w.rw.dd, G, w.rw.RD, w.aux, TW_AUXC, Tp, 0);
-    k.red(rw, H, W, W, grad_off(w.tab, "res_" + n + "/W"), W);
-    k.red(sw, H, S, S, grad_off(w.tab, "skip_" + n + "/W"), S);
-    k.red(rb + 3 * W, 1, W, W, grad_off(w.tab, "res_" + n + "/biases"), W);
-    k.red(sb + 3 * S, 1, S, S, grad_off(w.tab, "skip_" + n + "/biases"), S);
-    for (int tap = 0; tap < 3; ++tap)
-        k.red(dw[tap], W, G, G, grad_off(w.tab, "dilated_conv_" + n + "/W") + (size_t)tap * W * G, G);
-    k.red(cw, Cd, G, G, grad_off(w.tab, "mel_cond_" + n + "/W"), G);
-    k.red(db + 3 * G, 1, G, G, grad_off(w.tab, "dilated_conv_" + n + "/biases"), G);
-    k.red(db + 3 * G, 1, G, G, grad_off(w.tab, "mel_cond_" + n + "/biases"), G);
+    k.red(rw, H, W, W, lo.res.W, W);
+    k.red(sw, H, S, S, lo.skip.W, S);
+    k.red(rb + 3 * W, 1, W, W, lo.res.b, W);
+    k.red(sb + 3 * S, 1, S, S, lo.skip.b, S);
+    for (int tap = 0; tap < 3; ++tap) k.red(dw[tap], W, G, G, lo.dil.W + (size_t)tap * W * G, G);
+    k.red(cw, Cd, G, G, lo.cond.W, G);
+    k.red(db + 3 * G, 1, G, G, lo.dil.b, G);
+    k.red(db + 3 * G, 1, G, G, lo.cond.b, G);
     if (int rc = k.run(h, w.run(), st)) return rc;
     if (w.want_denc) tw_denc_gemm(h, w, tl.cond_t, w.rw.dd, G, w.rw.RD, st);
     return WN_OK;
@@ -424,10 +400,11 @@ int tw_tail(wn_handle* h, const TwCtx& w, hipStream_t st) {
     const long long sw = k.add(w.rw.ds, S, Tp, w.tp.lraw ? w.tp.lraw : w.tp.l, W, RS, IAF_LP);
     const long long sb = k.add(w.rw.ds, S, Tp, w.aux, TW_AUXC, Tp, 0);
     const long long cs = k.add(w.rw.dl, W, Tp, w.aux, TW_AUXC, Tp, 0);
-    k.red(sw, W, S, S, grad_off(w.tab, "skip_start/W"), S);
-    k.red(sb + 3 * S, 1, S, S, grad_off(w.tab, "skip_start/biases"), S);
-    k.red(cs, 3, W, W, grad_off(w.tab, "conv_start/W"), W);
-    k.red(cs + 3 * W, 1, W, W, grad_off(w.tab, "conv_start/biases"), W);
+    const TeacherParamLayout& lay = h->teacher.lay;
+    k.red(sw, W, S, S, lay.skip_start.W, S);
+    k.red(sb + 3 * S, 1, S, S, lay.skip_start.b, S);
+    k.red(cs, 3, W, W, lay.start.W, W);
+    k.red(cs + 3 * W, 1, W, W, lay.start.b, W);
     return k.run(h, w.run(), st);
 }
 
@@ -439,23 +416,21 @@ static int tw_check(wn_handle* h, const char* fn) {
     return WN_OK;
 }
 
-std::vector<WnGradEntry> wn_teacher_grad_table(const wn_handle* h) { return grad_table(h); }
-
 extern "C" int wn_teacher_grad_count(const wn_handle* h) {
     if (!h || !h->finalized || h->cfg.kind != WN_KIND_TEACHER) return 0;
-    return (int)grad_table(h).size();
+    return (int)h->teacher.lay.table.entries.size();
 }
 
 extern "C" int wn_teacher_grad_info(const wn_handle* h, int i, char* name, size_t name_cap, int64_t* offset, int64_t* shape4,
                                     int* ndim) {
     if (!h || !h->finalized || h->cfg.kind != WN_KIND_TEACHER)
         return wn_fail(h, WN_EINVAL, "wn_teacher_grad_info: needs a finalized teacher handle");
-    return wn_grad_info(h, "wn_teacher_grad_info", grad_table(h), i, name, name_cap, offset, shape4, ndim);
+    return wn_grad_info(h, "wn_teacher_grad_info", h->teacher.lay.table.entries, i, name, name_cap, offset, shape4, ndim);
 }
 
 extern "C" size_t wn_teacher_grad_floats(const wn_handle* h) {
     if (!h || !h->finalized || h->cfg.kind != WN_KIND_TEACHER) return 0;
-    return wn_grad_floats(grad_table(h));
+    return h->teacher.lay.table.floats;
 }
 
 // the work calls' refusals (tw_check) without a message: the size queries return 0 for what they would refuse
@@ -538,9 +513,9 @@ extern "C" int wn_teacher_backward_weights(wn_handle* h, const void* tape, size_
     if (tape_bytes < w.TR.total)
         return wn_fail(h, WN_EINVAL, "%s: a tape of %zu bytes cannot hold the training tape of B = %d, F = %d, T = %lld "
                        "(%zu bytes)", fn, tape_bytes, B, F, (long long)T, w.TR.total);
-    w.tab = grad_table(h);
-    if (grads_floats < wn_grad_floats(w.tab))
-        return wn_fail(h, WN_ENOMEM, "%s: grads holds %zu floats, the gradients need %zu", fn, grads_floats, wn_grad_floats(w.tab));
+    if (grads_floats < h->teacher.lay.table.floats)
+        return wn_fail(h, WN_ENOMEM, "%s: grads holds %zu floats, the gradients need %zu", fn, grads_floats,
+                       h->teacher.lay.table.floats);
     if (d_encoding && !h->teacher.denc_ok)
         return wn_fail(h, WN_EINVAL, "%s: d_encoding needs deconv_width %d to be a multiple of 64", fn, h->cfg.deconv_width);
     w.L = w_layout(h, B, F, T);
@@ -560,10 +535,7 @@ extern "C" int wn_teacher_backward_weights(wn_handle* h, const void* tape, size_
     w.want_denc = d_encoding != nullptr;
     if (int rc = tb_reverse(h, tape, d_out_params, B, T, d_wav, ws, stream, &w, dr)) return rc;
     if (d_encoding) {
-        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-        const int Cd = h->cfg.deconv_width;
-        hipLaunchKernelGGL(tw_denc_kernel, dim3((unsigned)((w.L.TE + 255) / 256), Cd / 8, B), dim3(256), 0, st, w.denc, w.rw.scal,
-                           d_encoding, w.L.TE, w.L.RE, Cd);
+        wn_tw_denc(w.denc, w.rw.scal, d_encoding, B, w.L.TE, w.L.RE, h->cfg.deconv_width, 0, reinterpret_cast<hipStream_t>(stream));
         WN_HIP(h, hipGetLastError());
     }
     return WN_OK;

@@ -266,34 +266,6 @@ __global__ __launch_bounds__(TR_NT) void tr_deconv_t_kernel(const float* __restr
 // ---------------------------------------------------------------------------------------------------------------------
 // host side of the re-pack
 // ---------------------------------------------------------------------------------------------------------------------
-// The variables of the flat parameter buffer, resolved once per call from the gradient table's fixed order (grad_table of
-// wn_teacher_wgrad.hip): conv_start, skip_start, per layer dilated_conv / mel_cond / res / skip, then out1, mel_cond_out1, out2,
-// each as W then biases.
-struct ConvP {
-    const float *W, *b;
-};
-struct TeacherParams {
-    ConvP start, skip_start, out1, cond_out1, out2;
-    std::vector<ConvP> dil, cond, res, skip;
-};
-bool resolve_params(const std::vector<WnGradEntry>& tab, const float* params, size_t nl, TeacherParams& q) {
-    if (tab.size() != 2 * (5 + 4 * nl) || tab.front().name != "conv_start/W" || tab.back().name != "out2/biases") return false;
-    size_t k = 0;
-    auto next = [&]() { ConvP c{params + tab[k].off, params + tab[k + 1].off}; k += 2; return c; };
-    q.start = next();
-    q.skip_start = next();
-    for (size_t i = 0; i < nl; ++i) {
-        q.dil.push_back(next());
-        q.cond.push_back(next());
-        q.res.push_back(next());
-        q.skip.push_back(next());
-    }
-    q.out1 = next();
-    q.cond_out1 = next();
-    q.out2 = next();
-    return true;
-}
-
 // what the weight-gradient calls support (tw_supported of wn_teacher_wgrad.hip): only such a handle has a parameter layout
 bool train_supported(const wn_handle* h) {
     const wn_config& c = h->cfg;
@@ -330,34 +302,31 @@ inline void absmax_launch(const float* x, size_t n, unsigned* out, hipStream_t s
 
 uint64_t wn_repack_serial_next() { return g_repack_serial++; }
 
-// ---- one upsampler stack (wn_repack.h): kernel, then bias per layer (dgrad_table of wn_deconv_bwd.hip)
-void wn_repack_deconv_absmax(const DeconvStackPack& sp, const std::vector<WnGradEntry>& UT, const float* up, unsigned* amax,
-                             hipStream_t st) {
+// ---- one upsampler stack (wn_repack.h): kernel, then bias per layer (sp.lay, wn_deconv_build_layout)
+void wn_repack_deconv_absmax(const DeconvStackPack& sp, const float* up, unsigned* amax, hipStream_t st) {
     for (size_t j = 0; j < sp.layers.size(); ++j) {
         const DeconvLayerPack& lp = sp.layers[j];
-        absmax_launch(up + UT[2 * j].off, (size_t)lp.K * lp.cout * lp.cin, amax + j, st);
+        absmax_launch(up + sp.lay[j].W, (size_t)lp.K * lp.cout * lp.cin, amax + j, st);
     }
 }
 
-void wn_repack_deconv_plain(wn_handle* h, const DeconvStackPack& sp, const std::vector<WnGradEntry>& UT, const float* up,
-                            hipStream_t st) {
+void wn_repack_deconv_plain(wn_handle* h, const DeconvStackPack& sp, const float* up, hipStream_t st) {
     float* blob = h->d_blob;
     for (size_t j = 0; j < sp.layers.size(); ++j) {
         const DeconvLayerPack& lp = sp.layers[j];
         const size_t total = (size_t)lp.S * lp.taps * (lp.cin / 16) * (lp.cout / 16) * 256;
-        hipLaunchKernelGGL(tr_deconv_frag_kernel, dim3(tr_blocks(total)), dim3(TR_NT), 0, st, up + UT[2 * j].off, blob + lp.w_off,
+        hipLaunchKernelGGL(tr_deconv_frag_kernel, dim3(tr_blocks(total)), dim3(TR_NT), 0, st, up + sp.lay[j].W, blob + lp.w_off,
                            lp.S, lp.taps, lp.cin, lp.cout);
         hipLaunchKernelGGL(tr_scatter_kernel, dim3(tr_blocks((size_t)lp.cout)), dim3(TR_NT), 0, st,
-                           ScatterArgs{up + UT[2 * j + 1].off, blob + lp.b_off, 1, lp.cout, 1, 0});
+                           ScatterArgs{up + sp.lay[j].b, blob + lp.b_off, 1, lp.cout, 1, 0});
     }
 }
 
-void wn_repack_deconv_split(wn_handle* h, DeconvStackPack& sp, const std::vector<WnGradEntry>& UT, const float* up, const float* mx,
-                            hipStream_t st) {
+void wn_repack_deconv_split(wn_handle* h, DeconvStackPack& sp, const float* up, const float* mx, hipStream_t st) {
     float* blob = h->d_blob;
     for (size_t j = 0; j < sp.layers.size(); ++j) {
         DeconvLayerPack& lp = sp.layers[j];
-        const float* W = up + UT[2 * j].off;
+        const float* W = up + sp.lay[j].W;
         const float sc = pick_scale(mx + j, 1);
         if (lp.w_off_h) {
             lp.inv_scale_h = 1.0f / sc;
@@ -449,20 +418,18 @@ extern "C" int wn_teacher_set_weights(wn_handle* h, const float* params, size_t 
         return wn_fail(h, WN_EINVAL, "%s: the handle has no parameter layout (mu-law, ce and weight-norm teachers have no weight "
                        "gradients)", fn);
     if (!params || !ws) return wn_fail(h, WN_EINVAL, "%s: null argument", fn);
-    const std::vector<WnGradEntry> PT = wn_teacher_grad_table(h);
-    if (params_floats != wn_grad_floats(PT))
+    const TeacherParamLayout& Q = h->teacher.lay;
+    if (params_floats != Q.table.floats)
         return wn_fail(h, WN_EINVAL, "%s: params holds %zu floats, the layout of wn_teacher_grad_info has %zu", fn, params_floats,
-                       wn_grad_floats(PT));
-    std::vector<WnGradEntry> UT;
+                       Q.table.floats);
     if (up_params) {
         if (c.use_resize_conv)
             return wn_fail(h, WN_EINVAL, "%s: use_resize_conv: the resize-conv upsampler has no parameter layout; pass no up_params", fn);
         if (wn_deconv_grad_floats(h, "") == 0)
             return wn_fail(h, WN_EINVAL, "%s: the upsampler has no parameter layout (wn_deconv_grad_floats is 0)", fn);
-        UT = wn_deconv_grad_table(h, 0);
-        if (up_floats != wn_grad_floats(UT) || UT.size() != 2 * h->stacks[0].layers.size())
+        if (up_floats != h->stacks[0].table.floats)
             return wn_fail(h, WN_EINVAL, "%s: up_params holds %zu floats, the layout of wn_deconv_grad_info has %zu", fn, up_floats,
-                           wn_grad_floats(UT));
+                           h->stacks[0].table.floats);
     }
     const size_t need = wn_teacher_set_weights_workspace_bytes(h);
     if (ws_bytes < need) return wn_fail(h, WN_EINVAL, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
@@ -490,42 +457,40 @@ extern "C" int wn_teacher_set_weights(wn_handle* h, const float* params, size_t 
                            Kc);
     };
     const size_t nl = A.layers.size();
-    TeacherParams Q;
-    if (!resolve_params(PT, params, nl, Q)) return wn_fail(h, WN_EINVAL, "%s: the parameter layout is not the model's", fn);
     // From here on the handle changes: tapes written under the old weights are refused, also after a failure below
     T.serial = wn_repack_serial_next();
 
     // ---- 1. absolute maxima of the sources of every split pack
     WN_HIP(h, hipMemsetAsync(amax, 0, (size_t)SL.total() * sizeof(unsigned), st));
-    absmax(Q.skip_start.W, (size_t)W * S, SL.wss());
-    absmax(Q.out1.W, (size_t)S * S, SL.wo1a());
-    absmax(Q.cond_out1.W, (size_t)Cd * S, SL.wo1b());
-    absmax(Q.out2.W, (size_t)S * OW, SL.wo2());
+    absmax(params + Q.skip_start.W, (size_t)W * S, SL.wss());
+    absmax(params + Q.out1.W, (size_t)S * S, SL.wo1a());
+    absmax(params + Q.cond_out1.W, (size_t)Cd * S, SL.wo1b());
+    absmax(params + Q.out2.W, (size_t)S * OW, SL.wo2());
     for (size_t i = 0; i < nl; ++i) {
-        absmax(Q.dil[i].W, (size_t)3 * W * G, SL.dil((int)i));
-        absmax(Q.cond[i].W, (size_t)Cd * G, SL.cond((int)i));
-        absmax(Q.res[i].W, (size_t)H * W, SL.res((int)i));
-        absmax(Q.skip[i].W, (size_t)H * S, SL.skip((int)i));
+        absmax(params + Q.layers[i].dil.W, (size_t)3 * W * G, SL.dil((int)i));
+        absmax(params + Q.layers[i].cond.W, (size_t)Cd * G, SL.cond((int)i));
+        absmax(params + Q.layers[i].res.W, (size_t)H * W, SL.res((int)i));
+        absmax(params + Q.layers[i].skip.W, (size_t)H * S, SL.skip((int)i));
     }
     DeconvStackPack* sp = up_params ? &h->stacks[0] : nullptr;
-    if (sp) wn_repack_deconv_absmax(*sp, UT, up_params, amax + SL.up(0), st);
+    if (sp) wn_repack_deconv_absmax(*sp, up_params, amax + SL.up(0), st);
 
     // ---- 2. the plain fp32 matrices and biases (wn_pack_ar), the composites, the fp32 fragments
-    copy(Q.start.W, A.start_off, 3 * W);
-    copy(Q.start.b, A.start_off + 3 * (size_t)W, W);
-    scatter(Q.skip_start.W, A.wss_off, W, S, W, 0);
-    copy(Q.skip_start.b, A.bss_off, S);
+    copy(params + Q.start.W, A.start_off, 3 * W);
+    copy(params + Q.start.b, A.start_off + 3 * (size_t)W, W);
+    scatter(params + Q.skip_start.W, A.wss_off, W, S, W, 0);
+    copy(params + Q.skip_start.b, A.bss_off, S);
     for (size_t i = 0; i < nl; ++i) {
         ArLayerPack& lp = A.layers[i];
-        const float* wd = Q.dil[i].W;
+        const float* wd = params + Q.layers[i].dil.W;
         for (int tap = 0; tap < 3; ++tap) scatter(wd + (size_t)tap * W * G, lp.wd_off, W, G, K, tap * W);
-        scatter(Q.cond[i].W, lp.wd_off, Cd, G, K, 3 * W);
-        add(Q.dil[i].b, Q.cond[i].b, lp.bd_off, G);
-        copy(Q.cond[i].b, lp.bc_off, G);
-        scatter(Q.res[i].W, lp.wrs_off, H, W, H, 0);
-        scatter(Q.skip[i].W, lp.wrs_off + (size_t)W * H, H, S, H, 0);
-        copy(Q.res[i].b, lp.brs_off, W);
-        copy(Q.skip[i].b, lp.brs_off + W, S);
+        scatter(params + Q.layers[i].cond.W, lp.wd_off, Cd, G, K, 3 * W);
+        add(params + Q.layers[i].dil.b, params + Q.layers[i].cond.b, lp.bd_off, G);
+        copy(params + Q.layers[i].cond.b, lp.bc_off, G);
+        scatter(params + Q.layers[i].res.W, lp.wrs_off, H, W, H, 0);
+        scatter(params + Q.layers[i].skip.W, lp.wrs_off + (size_t)W * H, H, S, H, 0);
+        copy(params + Q.layers[i].res.b, lp.brs_off, W);
+        copy(params + Q.layers[i].skip.b, lp.brs_off + W, S);
         if (i > 0) {
             const ArLayerPack& pv = A.layers[i - 1];
             hipLaunchKernelGGL(tr_bm_kernel, dim3(tr_blocks(G)), dim3(TR_NT), 0, st, blob + lp.wd_off, blob + lp.bd_off,
@@ -533,12 +498,12 @@ extern "C" int wn_teacher_set_weights(wn_handle* h, const float* params, size_t 
         }
     }
     wn_ar_compose(h, st);        // composite matrices and the [wd | wcomp] fragments: wn_finalize's own launches, on this stream
-    scatter(Q.out1.W, A.wo1_off, S, S, S + Cd, 0);
-    scatter(Q.cond_out1.W, A.wo1_off, Cd, S, S + Cd, S);
-    add(Q.out1.b, Q.cond_out1.b, A.bo1_off, S);
-    copy(Q.cond_out1.b, A.bco1_off, S);
-    scatter(Q.out2.W, A.wo2_off, S, OW, S, 0);
-    copy(Q.out2.b, A.bo2_off, OW);
+    scatter(params + Q.out1.W, A.wo1_off, S, S, S + Cd, 0);
+    scatter(params + Q.cond_out1.W, A.wo1_off, Cd, S, S + Cd, S);
+    add(params + Q.out1.b, params + Q.cond_out1.b, A.bo1_off, S);
+    copy(params + Q.cond_out1.b, A.bco1_off, S);
+    scatter(params + Q.out2.W, A.wo2_off, S, OW, S, 0);
+    copy(params + Q.out2.b, A.bo2_off, OW);
     if (A.wss_b_off) {           // the batched step's A-fragment copies exist
         frag(A.wss_off, A.wss_b_off, S, W);
         for (size_t i = 0; i < nl; ++i) {
@@ -551,7 +516,7 @@ extern "C" int wn_teacher_set_weights(wn_handle* h, const float* params, size_t 
         frag(A.wo1_off, A.wo1_b_off, S, S + Cd);
         frag(A.wo2_off, A.wo2_b_off, OW, S);
     }
-    if (sp) wn_repack_deconv_plain(h, *sp, UT, up_params, st);
+    if (sp) wn_repack_deconv_plain(h, *sp, up_params, st);
 
     // ---- 3. the maxima come back (the call's one read-back: it synchronises the stream); pick_scale on the host
     std::vector<float> mx(SL.total());
@@ -603,7 +568,7 @@ extern "C" int wn_teacher_set_weights(wn_handle* h, const float* params, size_t 
         }
         if (T.denc_ok) tile(T.cond_out1_t, scale_of({SL.wo1b()}), A.wo1_off, S + Cd, ROW_IDENT, Cd, SRC_T, S, S);
     }
-    if (sp) wn_repack_deconv_split(h, *sp, UT, up_params, mx.data() + SL.up(0), st);
+    if (sp) wn_repack_deconv_split(h, *sp, up_params, mx.data() + SL.up(0), st);
     WN_HIP(h, hipGetLastError());
     return WN_OK;
 }

@@ -38,7 +38,8 @@ class Engine(object):
         self.device = torch.device(device if device is not None else 'cuda:{}'.format(torch.cuda.current_device()))
         self.n_mel = n_mel
         self._hbox = [ctypes.c_void_p(0)]   # the C handle, shared with the engine's forks (fork())
-        self._shared = {'ar_graph': None}   # handle-wide switch states the forks must agree on
+        self._shared = {'ar_graph': None,   # handle-wide switch states the forks must agree on
+                        'grad_tables': {}}  # (which, scope) -> the handle's gradient tables (_grad_table)
         self._is_fork = False
         self._ws = None
         self._ar_stream = None
@@ -113,6 +114,7 @@ class Engine(object):
             self.set_weight(name, weights[name])
         with torch.cuda.device(self.device):
             self._check(self.lib.wn_finalize(self._h))
+        self._shared['grad_tables'].clear()
         self._finalized = True
         return self
 
@@ -570,15 +572,22 @@ class Engine(object):
         return dwav
 
     # ---- gradient tables of the weight-gradient calls: one flat float32 buffer, one entry per TF variable ----
-    def _grad_table(self, count, info, *prefix_args):
+    def _grad_table(self, key, count, info, *prefix_args):
         """[(tf variable name, float offset, TF shape)] from a wn_*_grad_count / wn_*_grad_info pair (prefix_args: what the
-        pair takes between the handle and the index)."""
+        pair takes between the handle and the index).  The layout of a finalized handle is fixed, so its table is walked
+        once and kept under `key` for the handle's forks too; the caller gets a list of its own.  Nothing is kept of an
+        engine that is not finalized or of a model the calls refuse."""
+        tables = self._shared['grad_tables']
+        if key in tables:
+            return list(tables[key])
         out = []
         name = ctypes.create_string_buffer(160)
         off, nd, shape = ctypes.c_int64(0), ctypes.c_int(0), (ctypes.c_int64 * 4)()
         for i in range(int(count(self._h, *prefix_args))):
             self._check(info(self._h, *prefix_args, i, name, 160, ctypes.byref(off), shape, ctypes.byref(nd)))
             out.append((name.value.decode(), int(off.value), tuple(int(shape[k]) for k in range(nd.value))))
+        if self._finalized and out:
+            tables[key] = tuple(out)
         return out
 
     @staticmethod
@@ -592,7 +601,7 @@ class Engine(object):
 
     def teacher_grad_table(self):
         """[(tf variable name, float offset, TF shape)] of the flat gradient buffer, in the library's fixed order."""
-        return self._grad_table(self.lib.wn_teacher_grad_count, self.lib.wn_teacher_grad_info)
+        return self._grad_table(('teacher', ''), self.lib.wn_teacher_grad_count, self.lib.wn_teacher_grad_info)
 
     DROPOUT_MODES = {'dropout_inputs': 1, 'dropout_all': 2}        # WN_DROPOUT_INPUTS, WN_DROPOUT_ALL
 
@@ -672,7 +681,7 @@ class Engine(object):
         """[(tf variable name, float offset, TF shape)] of iaf_backward_weights' flat gradient buffer: every variable of every
         flow in the order weights.expected_variables lists them (the upsampler's are deconv_backward's).  Empty for a
         model the training calls refuse."""
-        return self._grad_table(self.lib.wn_iaf_grad_count, self.lib.wn_iaf_grad_info)
+        return self._grad_table(('iaf', ''), self.lib.wn_iaf_grad_count, self.lib.wn_iaf_grad_info)
 
     def iaf_train_tape_bytes(self, B, F):
         return int(self.lib.wn_iaf_train_tape_bytes(self._h, int(B), int(F), self.iaf_length(F)))
@@ -821,7 +830,7 @@ class Engine(object):
         """[(tf variable name, float offset, TF shape)] of deconv_backward's flat gradient buffer: per layer
         '<scope/>trans_conv_j/kernel' [1,K,Cout,Cin], then '<scope/>trans_conv_j/bias' [Cout].  Empty for a stack the call
         refuses."""
-        return self._grad_table(self.lib.wn_deconv_grad_count, self.lib.wn_deconv_grad_info, scope.encode())
+        return self._grad_table(('deconv', scope), self.lib.wn_deconv_grad_count, self.lib.wn_deconv_grad_info, scope.encode())
 
     def deconv_backward(self, mel, d_encoding, scope=''):
         """VJP of deconv(mel, scope) with respect to the stack's variables: mel [B,F,n_mel] and a cotangent d_encoding
